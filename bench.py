@@ -2,6 +2,13 @@
 """bench.py -- publish-topic matches/s of the MI355X engine on BASELINE.json's workload.
 
   python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --full                               (+ every other leg: CPU baseline and parity, host-visible path, extras, ...)
+  python bench.py ... --dump-outputs DIR                   (+ the last timed step's results as DIR/*.npy, see dump_outputs)
+
+A plain run sets up, warms up, times the K steps and prints the line; everything the line carries beyond the timed steps (the CPU
+baseline and its parity check, the host-visible path, the fan-out grouping, the batching front, the pass without kernel timing, the
+other exchange form and the node-wide batch of N > 1, the C1 / C2 / C4 / C5 / compaction / ordered-batch legs under `extra`, the PMC
+traffic of the roofline) is measured with --full only.
 
 A "step" is one pass of the hot path over one batch of synthetic publishes: tokenise + trie walk + CSR expand of
 --topics (default 1M) publish topics against this rank's shard of the filter index, inputs resident in HBM, results
@@ -76,10 +83,20 @@ def main():
     ap.add_argument("--batcher-topics", type=int, default=200_000)
     ap.add_argument("--cpu-sample-tenants", type=int, default=1_000_000, help="the CPU baseline / parity leg takes the publishes of the first N tenants (default: all of them, the whole batch)")
     ap.add_argument("--cpu-sample-topics", type=int, default=1_000_000)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the timed steps (the options above that configure such a leg act with --full only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the CSR the last timed step returned as DIR/*.npy (float64; a fixed seeded sample, at most ~49 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.ordered_only:
+        args.full = True
         args.no_host_path = args.no_cpu_baseline = True
         args.batcher_threads = 0
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the line
+        args.no_host_path = args.no_cpu_baseline = args.no_extras = args.no_churn = True
+        args.batcher_threads = args.csr_exchange_steps = args.node_batch_steps = 0
 
     import numpy
     import torch
@@ -139,9 +156,9 @@ def main():
                    dedup_min_topics=1 if args.dedup else 0)
     kb, ko = w.keys_packed()
     # bmq_rebuild, three times each way (a fresh box's first call pays for page faults of the staging copy and the first builder launches;
-    # the docs quoted a best run, the driver saw 3-5x more): min and median are reported
+    # the docs quoted a best run, the driver saw 3-5x more): min and median are reported (--full; a plain run loads once)
     t_builds = []
-    for _ in range(3 if world == 1 else 1):
+    for _ in range(3 if world == 1 and args.full else 1):
         t0 = time.time()
         eng.rebuild_raw(kb.ctypes.data, ko.ctypes.data, w.n_keys)
         t_builds.append(time.time() - t0)
@@ -351,6 +368,9 @@ def main():
         n_slow += st.n_slow_topics
     barrier()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs and rank == 0:  # (before any other leg reuses the buffers)
+        k_last = (args.steps - 1) % NBUF
+        dump_outputs(args.dump_outputs, d_row[k_last], d_ids[k_last], n, torch, np)
     if dist is not None:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -377,21 +397,23 @@ def main():
         node = node_batch(args, rank, world, local_rank, dev, dist, total_tenants, per_tenant, mode, seed)
     # The engine's production default records no events between its kernels (they cost ~4 us each, ~16 us per batch): the same
     # K steps once more without them.  `value` above keeps the events on, because the roofline wants the kernel time of exactly the
-    # timed steps; this figure is what a caller that does not ask for kernel times gets.
-    eng.set_kernel_timing(False)
-    for i in range(min(args.warmup, 2)):
-        step(i)
-    barrier()
-    t1 = time.perf_counter()
-    for i in range(args.steps):
-        step(i)
-    barrier()
-    elapsed_plain = time.perf_counter() - t1
-    if dist is not None:
-        tmax = torch.tensor([elapsed_plain], dtype=torch.float64, device=dev)
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        elapsed_plain = float(tmax.item())
-    eng.set_kernel_timing(True)
+    # timed steps; this figure is what a caller that does not ask for kernel times gets.  (--full)
+    elapsed_plain = None
+    if args.full:
+        eng.set_kernel_timing(False)
+        for i in range(min(args.warmup, 2)):
+            step(i)
+        barrier()
+        t1 = time.perf_counter()
+        for i in range(args.steps):
+            step(i)
+        barrier()
+        elapsed_plain = time.perf_counter() - t1
+        if dist is not None:
+            tmax = torch.tensor([elapsed_plain], dtype=torch.float64, device=dev)
+            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+            elapsed_plain = float(tmax.item())
+        eng.set_kernel_timing(True)
     # Per rank, next to the whole-job value: with the index sharded N ways every rank's k_walk runs over 1 / N of the
     # 10 M route keys -- it hits its L2 more often, and a curve that reads super-linear explains itself only with these beside it.
     per_rank = None
@@ -453,8 +475,8 @@ def main():
             "note": "ms per step (match + exchange, max over ranks) with the fan-out exchange (all-gather of 4 B per topic) and with the "
                     "all-gatherv of the complete CSR (totals, row pointers, then one exact-size broadcast per rank in one group); the first "
                     "is the timed region of `value`, the second a few extra steps"},
-        "value_without_kernel_timing": world * n * steps / elapsed_plain if not args.churn else None,
-        "ms_per_step_without_kernel_timing": elapsed_plain / steps * 1e3 if not args.churn else None,
+        "value_without_kernel_timing": world * n * steps / elapsed_plain if elapsed_plain and not args.churn else None,
+        "ms_per_step_without_kernel_timing": elapsed_plain / steps * 1e3 if elapsed_plain and not args.churn else None,
         "p99_batch_ms": float(np.percentile(lat, 99)),
         "p50_batch_ms": float(np.percentile(lat, 50)),
         "routes_per_topic": n_match / (n * steps),
@@ -470,7 +492,8 @@ def main():
                    "rebuild_from_pinned_keys": float(np.median(t_builds_pinned)) if t_builds_pinned else None,
                    "rebuild_from_pinned_keys_min": float(np.min(t_builds_pinned)) if t_builds_pinned else None,
                    "note": "bmq_rebuild = upload of the route keys + the GPU builder kernels (bulk load); wall time of the C-ABI call, median / min "
-                           "of 3 calls each (pageable, then page-locked keys); rebuild_first_call = the very first one on the fresh process"},
+                           "of %d call(s) each (pageable, then page-locked keys with --full); rebuild_first_call = the very first one on the fresh process"
+                           % len(t_builds)},
         "roofline": {"bound": "hbm", "kernel": dom_name, "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
                      "frac": achieved / 8000.0, "traffic": None,
                      "own_algorithmic_bytes_per_launch": own[dom_name],
@@ -483,7 +506,9 @@ def main():
                      "algorithmic_bytes_per_launch": float(np.mean(alg_bytes)),
                      "kernel_own_frac": {k: own[k] / (max(v, 1e-9) * 1e-3) / 8e12 for k, v in (("k_walk", k_walk_ms), ("k_expand", k_exp_ms))}},
     }
-    if args.topics == 1_000_000 and not args.ungrouped and not args.dedup and not args.churn:
+    if not args.full:
+        out["roofline"]["traffic_source"] = "the PMC traffic files are looked up with --full only"
+    elif args.topics == 1_000_000 and not args.ungrouped and not args.dedup and not args.churn:
         attach_traffic(out, args.workload, world)
     else:  # the counter passes ran the default batch: their bytes per launch say nothing about another batch size / order
         out["roofline"]["traffic_source"] = "profiles/traffic_*.json was measured with the default batch (1 M grouped publishes, no churn): not reported for this run"
@@ -722,7 +747,7 @@ def extra_legs(args, eng, w, step, torch, np, fetch_csr=None, tickets=None):
         try:
             t0 = time.perf_counter()
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", wl, "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                                "--no-host-path", "--no-extras"], capture_output=True, text=True, timeout=240)
+                                "--no-host-path", "--no-extras", "--full"], capture_output=True, text=True, timeout=240)
             d = json.loads(r.stdout.strip().splitlines()[-1])
             keep = ("metric", "value", "unit", "ms_per_step", "kernel_ms", "roofline", "routes_per_topic", "topics_per_filter", "churn", "limited", "compaction")
             extra[wl] = {k: d[k] for k in keep if k in d}
@@ -1454,6 +1479,29 @@ def kernel_sources_sha():
     return h.hexdigest()[:16]
 
 
+def dump_outputs(dirname, d_row, d_ids, n, torch, np):
+    """--dump-outputs DIR: the CSR the last timed step handed its caller (row pointers + route / topic ids, ascending inside a row) as
+    float64 .npy files -- every value is an integer far below 2^53, so exact -- on rows picked by a fixed seed, at most ~49 MB in all:
+      count_rows.npy   the rows whose id counts are written: all of them up to 2^20 rows, else a seeded sample of 2^20
+      match_counts.npy the number of ids of each of those rows
+      id_rows.npy      a seeded sample of 2^16 rows (a subset of count_rows), ascending
+      route_ids.npy    the ids of those rows, row after row (at most 2^22 values: a longer list is cut there)"""
+    os.makedirs(dirname, exist_ok=True)
+    rp = d_row[:n + 1].cpu().numpy().view(np.uint32).astype(np.int64)
+    perm = np.random.default_rng(0xB1F2D0).permutation(n)
+    count_rows = np.arange(n) if n <= 1 << 20 else np.sort(perm[:1 << 20])
+    id_rows = np.sort(perm[:1 << 16])
+    counts = rp[1:] - rp[:-1]
+    lens = counts[id_rows]
+    firsts = np.concatenate([[0], np.cumsum(lens)[:-1]])
+    pos = (np.repeat(rp[id_rows] - firsts, lens) + np.arange(int(lens.sum()), dtype=np.int64))[:1 << 22]
+    if len(pos) and (int(pos.max()) >= d_ids.numel() or rp[-1] > d_ids.numel()):
+        raise RuntimeError("--dump-outputs: the row pointers reach past the id buffer (%d > %d)" % (rp[-1], d_ids.numel()))
+    ids = d_ids[torch.from_numpy(pos).to(d_ids.device)].cpu().numpy().view(np.uint32)
+    for name, a in (("count_rows", count_rows), ("match_counts", counts[count_rows]), ("id_rows", id_rows), ("route_ids", ids)):
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float64))
+
+
 def emit_json(out):
     """ONE JSON line, and the last thing on stdout: flush the C runtime's buffer first (RCCL prints its version banner
     through it) so that nothing lands after the line."""
@@ -1464,13 +1512,9 @@ def emit_json(out):
         pass
     sys.stdout.flush()
     print(json.dumps(out), flush=True)
-    # The line is out and every engine object has been closed explicitly.  What is left is the interpreter's shutdown of the HIP / RCCL /
-    # OpenMP runtimes the process loaded (PyTorch's, the library's, the oracle's), whose at-exit handlers race each other once in a while
-    # (seen once in round 3 as a glibc "double free" AFTER the line, rc != 0): leave without running them.
+    # The line is out and every engine object has been closed explicitly (callers close theirs before this).  The process then takes the
+    # normal way out: the exit handlers and destructors of the libraries it loaded run (a profiler's tool library writes its output there).
     sys.stderr.flush()
-    profiled = any("rocprof" in os.environ.get(k, "").lower() for k in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "HSA_TOOLS_LIB"))
-    if not profiled:  # (a profiler's tool library writes its output in an exit handler: under rocprofv3 the normal way out is taken)
-        os._exit(0)
 
 
 def bench_retain(args, rank, world, local_rank, dev, dist):
@@ -1549,6 +1593,8 @@ def bench_retain(args, rank, world, local_rank, dev, dist):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_row, d_ids, n, torch, np)
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -1564,7 +1610,7 @@ def bench_retain(args, rank, world, local_rank, dev, dist):
     exp_bytes = 4.0 * n_match / args.steps
     achieved = (walk_bytes if dom_name == "k_retain_walk" else exp_bytes) / (k_ms * 1e-3) / 1e9
     limited = None
-    if world == 1:  # (before the churn leg: the index as loaded)
+    if world == 1 and args.full:  # (before the churn leg: the index as loaded)
         limited = {"clean": retain_limited_leg(eng, w, batches[0][3], base_ms + 95_000, np)}
     churn = retain_churn_leg(eng, w, data, off, n_topics, step, torch, np) if world == 1 and not args.no_churn else None
     if limited is not None and churn is not None:
@@ -1595,7 +1641,10 @@ def bench_retain(args, rank, world, local_rank, dev, dist):
                         "algorithmic_bytes_per_launch": float(np.mean(alg)),
                         "kernel_own_frac": {"k_retain_walk": walk_bytes / (max(kw, 1e-9) * 1e-3) / 8e12, "k_expand": exp_bytes / (max(ke, 1e-9) * 1e-3) / 8e12}},
            "churn": churn, "limited": limited, "compaction": compaction}
-    attach_traffic(out, "c4", world)
+    if args.full:
+        attach_traffic(out, "c4", world)
+    else:
+        out["roofline"]["traffic_source"] = "the PMC traffic files are looked up with --full only"
     if not args.no_cpu_baseline and world == 1:
         from oracle import oracle as O
         lt = O.LevelTrie(1)
@@ -1610,6 +1659,7 @@ def bench_retain(args, rank, world, local_rank, dev, dist):
         out["cpu_baseline"] = {"value": m / sec, "unit": "filters/s", "cores": cores, "logical_cpus_visible": os.cpu_count(), "kind": "port",
                                "sample": "first %d filters of batch 0 against the full 1M-topic TopicLevelTrie restatement on "
                                          "%d threads; %.1f s" % (m, cores, sec)}
+    eng.close()  # (as in main(): every engine object is closed before the line goes out)
     if world > 1:
         dist.destroy_process_group()
     emit_json(out)

@@ -18,7 +18,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = dict(os.environ, BMQ_BENCH_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29613",
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--topics", "100000", "--no-cpu-baseline", "--csr-exchange-steps", "2",
-           "--node-batch-steps", "2"]
+           "--node-batch-steps", "2", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1]

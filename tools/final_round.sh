@@ -12,7 +12,7 @@ T0=$SECONDS
 timeout 480 python -m pytest tests -m gpu -q --durations=12 > $O/pytest_gpu.log 2>&1
 grep -E "passed|failed|error" $O/pytest_gpu.log | tail -3
 echo "[final_round] pytest done at $((SECONDS - T0)) s"
-timeout 360 python bench.py > $O/bench_c3.json 2> $O/bench_c3.err
+timeout 360 python bench.py --full > $O/bench_c3.json 2> $O/bench_c3.err
 tail -c 600 $O/bench_c3.json
 echo "[final_round] bench done at $((SECONDS - T0)) s"
 P="--ordered-only --steps 5 --warmup 2"

@@ -10,9 +10,9 @@ if [ -z "$SKIP_PYTEST" ]; then
   timeout 900 python -m pytest tests -m gpu -x -q --durations=12 > $O/pytest_gpu.log 2>&1; grep -E "passed|failed|error" $O/pytest_gpu.log | tail -2
 fi
 # the driver's command (N = 1): default workload C3 + the compact C2 / C4 / C5 / batching-front legs under "extra"
-timeout 300 python bench.py > $O/bench_c3.json 2> $O/bench_c3.err; tail -c 300 $O/bench_c3.json
-timeout 300 python bench.py --workload c2 --cpu-sample-topics 20000 --no-extras > $O/bench_c2.json 2> $O/bench_c2.err
-timeout 300 python bench.py --workload c4 --no-extras > $O/bench_c4.json 2> $O/bench_c4.err
+timeout 300 python bench.py --full > $O/bench_c3.json 2> $O/bench_c3.err; tail -c 300 $O/bench_c3.json
+timeout 300 python bench.py --full --workload c2 --cpu-sample-topics 20000 --no-extras > $O/bench_c2.json 2> $O/bench_c2.err
+timeout 300 python bench.py --full --workload c4 --no-extras > $O/bench_c4.json 2> $O/bench_c4.err
 P="--no-cpu-baseline --no-extras --batcher-threads 0"
 for w in c3 c2 c4; do
   # (--no-host-path: only the timed loop launches the match kernels, so that the trace's AVERAGE is the average of the same launches the

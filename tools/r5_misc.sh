@@ -21,7 +21,7 @@ PY
 done
 unset BMQ_LIB
 for ch in 65536 524288; do
-  timeout 300 python bench.py --no-cpu-baseline --no-host-path --steps 10 --warmup 3 --batcher-threads 0 --compact-chunk $ch > $O/compact_$ch.json 2> $O/compact_$ch.err
+  timeout 300 python bench.py --full --no-cpu-baseline --no-host-path --steps 10 --warmup 3 --batcher-threads 0 --compact-chunk $ch > $O/compact_$ch.json 2> $O/compact_$ch.err
   python - <<PY
 import json
 try:
