@@ -714,6 +714,13 @@ BMQ_HD void bulk_counts_one(const OpBatch& ob, uint32_t t, uint32_t n_ten, const
 // A delete that found its filter in phase 3 found what phase 1 would have found (nodes are never removed); in the common batch -- unsubscribes
 // of filters that exist -- phase 4 finds nothing to do (round 5: two full passes of ~60 us each over a 100 k-op batch).
 constexpr unsigned long long TARGET_RETRY = ~0ull - 1;
+// An op whose path runs through node `node` (slot `slot_abs`) may change what lies below it: a tail record beside it becomes a tombstone
+// (bmq_layout.h).  Records are written by an earlier kernel (the tail pass) and only ever change into tombstones here: a plain look, then a CAS.
+BMQ_HD void tail_invalidate(const DistIndexMut& ix, uint32_t node, unsigned long long slot_abs) {
+    uint64_t* k = reinterpret_cast<uint64_t*>(ix.trie + (size_t)(slot_abs ^ 1ull));
+    const uint64_t rec = (uint64_t)node | ((uint64_t)TOK_TAIL << 32);
+    if (peek_load(k) == rec) atom_cas(k, rec, (uint64_t)node | ((uint64_t)TOK_TOMB << 32));
+}
 BMQ_HD void locate_one(const DistIndexMut& ix, const OpBatch& ob, uint32_t i, uint32_t phase) {
     if (phase == 4) {
         if (ob.target[i] != TARGET_RETRY) return;
@@ -760,6 +767,7 @@ BMQ_HD void locate_one(const DistIndexMut& ix, const OpBatch& ob, uint32_t i, ui
         slot_abs = sa;
         bloom = &ix.trie[sa].lit_bloom;
         at_root = false;
+        tail_invalidate(ix, child, sa);
         return true;
     });
     if (!ok) {
@@ -1002,13 +1010,13 @@ BMQ_HD bool rehash_place(const DistIndexMut& ix, TrieSlot* d, const TrieSlot& sr
 }
 BMQ_HD void rehash_one(const DistIndexMut& ix, uint32_t old_base, uint32_t new_base, uint32_t new_buckets, uint32_t s, uint32_t pass, uint32_t d) {
     const TrieSlot src = ix.trie[(size_t)old_base + s];
-    if (src.parent == NONE) return;
+    if (!slot_is_node(src)) return; // free, a tail record or a tombstone: records are not carried into the new region
     const uint64_t key = (uint64_t)src.parent | ((uint64_t)src.token << 32);
     bool beside = false; // this is a '+' child and the other slot of its line holds its parent
     TrieSlot par{};
     if (src.token == TOK_PLUS && src.parent != 0) {
         par = ix.trie[(size_t)old_base + (s ^ 1u)];
-        beside = par.parent != NONE && par.node == src.parent;
+        beside = slot_is_node(par) && par.node == src.parent;
     }
     if ((pass == 1) != beside) return;
     if (beside) { // where did pass 0 put the parent?
@@ -1044,6 +1052,70 @@ BMQ_HD void rehash_one(const DistIndexMut& ix, uint32_t old_base, uint32_t new_b
     atom_or(&ix.bc->err, (uint32_t)ERR_REGION_FULL);
 }
 constexpr TrieSlot FREE_SLOT{NONE, 0, 0, 0, 0, 0, NONE, 0};
+// ------------------------------------------------------------------------------------------------------------
+// tail pass: a record beside every node whose subtree is a short unary chain (bmq_layout.h), after a bulk load / a compaction
+// ------------------------------------------------------------------------------------------------------------
+// Two passes, one lane per slot of the slot table.  Count: every node adds itself to its parent's child count, the first one leaves its
+// slot there (read only where the count is 1).  Place: a node with one child and a free slot beside it follows the chain; if it ends within TAIL_K
+// levels at a leaf whose routes are of one kind, with no routes above it, the record goes into the free slot -- the neighbour of this node
+// only, so no two lanes write one slot.  The scratch is per node id: node v of region r is cnt / kid[r.nbase + v].
+struct TailRegion {
+    uint32_t base, slots;  // the region: slot table [base, base + slots)
+    uint32_t nbase, n_ids; // the tenant's node ids 0 .. n_ids-1 in the scratch arrays
+};
+struct TailPass {
+    const TailRegion* regs; // ascending by base
+    uint32_t n_regs;
+    uint32_t* cnt; // children per node
+    uint32_t* kid; // slot (region-relative) of a child
+};
+BMQ_HD const TailRegion* tail_region(const TailPass& tp, uint32_t g) {
+    uint32_t lo = 0, hi = tp.n_regs; // the last region with base <= g
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (tp.regs[mid].base <= g) lo = mid;
+        else hi = mid;
+    }
+    const TailRegion* r = tp.regs + lo;
+    return tp.n_regs != 0 && g >= r->base && g - r->base < r->slots ? r : nullptr;
+}
+BMQ_HD void tail_count_one(const DistIndexMut& ix, const TailPass& tp, uint32_t g) {
+    const TailRegion* r = tail_region(tp, g);
+    if (!r) return;
+    const TrieSlot c = ix.trie[g];
+    if (!slot_is_node(c) || c.parent == 0 || c.parent >= r->n_ids) return;
+    if (atom_add(tp.cnt + r->nbase + c.parent, 1u) == 0u) tp.kid[r->nbase + c.parent] = g - r->base; // (the first child only: one writer)
+}
+BMQ_HD void tail_place_one(const DistIndexMut& ix, const TailPass& tp, uint32_t g) {
+    const TailRegion* r = tail_region(tp, g);
+    if (!r) return;
+    const TrieSlot x = ix.trie[g];
+    if (!slot_is_node(x) || x.node >= r->n_ids || ix.trie[g ^ 1u].parent != NONE) return;
+    if (tp.cnt[r->nbase + x.node] != 1u) return;
+    uint32_t toks[TAIL_K] = {NONE, NONE, NONE, NONE};
+    uint32_t rel = tp.kid[r->nbase + x.node];
+    for (uint32_t k = 0; k < TAIL_K; k++) {
+        if (rel >= r->slots) return;
+        const TrieSlot c = ix.trie[(size_t)r->base + rel];
+        if (!slot_is_node(c) || c.node >= r->n_ids) return;
+        toks[k] = c.token;
+        const uint32_t n = tp.cnt[r->nbase + c.node];
+        if (n == 0) { // the leaf: routes of one kind
+            if ((c.own_count != 0) == (c.hash_count != 0) || ((c.own_count | c.hash_count) & TAIL_HASH)) return;
+            TrieSlot rec;
+            rec.parent = x.node;
+            rec.token = TOK_TAIL;
+            rec.own_begin = c.own_count != 0 ? c.own_begin : c.hash_begin;
+            rec.own_count = c.own_count != 0 ? c.own_count : (c.hash_count | TAIL_HASH);
+            rec.hash_begin = toks[0], rec.hash_count = toks[1], rec.node = toks[2], rec.lit_bloom = toks[3];
+            ix.trie[g ^ 1u] = rec;
+            return;
+        }
+        if (n != 1u || c.own_count != 0 || c.hash_count != 0) return;
+        rel = tp.kid[r->nbase + c.node];
+    }
+}
+
 
 // ------------------------------------------------------------------------------------------------------------
 // read-only helpers (inspection: bmq_index_find, bmq_route_key)

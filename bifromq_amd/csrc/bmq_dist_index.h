@@ -13,7 +13,7 @@
 //   bool copy_out(dst, src, n) [blocking, after everything queued before]   bool copy(dst, src, n)   bool zero(p, n)   bool sync()
 //   bool fill_slots(TrieSlot*, n), iota(uint32_t*, n)
 //   bool prepare(ix, ob), prepare_check(ix, ob, n_dir), bulk_prepare(ix, ob), scan_flags(in, out, n), bulk_tenants(ix, ob, scan),
-//        locate(ix, ob), sort_targets(ob), group(ix, ob), rehash(ix, old_base, old_slots, new_base, new_buckets),
+//        locate(ix, ob), sort_targets(ob), group(ix, ob), rehash(ix, old_base, old_slots, new_base, new_buckets), tails(ix, tail_pass, n_slots),
 //        dict_rehash(old, old_slots, ix), find(ix, query, tenant_len, filter_len, out, cap), gather_refs(ix, ids, n, out_refs),
 //        gather_bytes(ix, refs, offs, n, out)
 //   std::string err;
@@ -80,6 +80,7 @@ public:
     bool built = false, broken = false;
     uint64_t generation = 0; // bumped by every rebuild: ids of different generations are unrelated
     uint32_t slack_num = BMQ_REGION_SLACK_NUM; // region size = nodes * (1 + slack_num / 4) buckets (bmq_config.region_slack)
+    bool tail_records = true; // the tail pass after a bulk load / before a compacted generation serves (bmq_config.tail_records)
     bool tiny = false;       // test knob (tools/host_fuzz.cpp): minimal initial capacities, so that every growth path runs all the time
 
     // ---- arrays in exec memory ----
@@ -365,6 +366,35 @@ public:
         kb.resize(kb.size() + 16, 0);
         return rebuild(kb.data(), ko.data(), (uint32_t)ko.size() - 1); // not ascending any more after churn: sorted on the host
     }
+
+    // ---- tail records (bmq_layout.h): two passes over the slot table with per-node scratch (8 bytes per node, released at once) ----
+    bool form_tails() {
+        if (!tail_records || !built_regions()) return true;
+        std::vector<TenantSlot> d(dir_slots);
+        if (!x.copy_out(d.data(), dir, sizeof(TenantSlot) * (size_t)dir_slots)) return xfail();
+        std::vector<TailRegion> regs;
+        uint64_t ids = 0;
+        for (const TenantSlot& t : d) {
+            if (!(t.hash_lo | t.hash_hi) || t.buckets == 0) continue;
+            regs.push_back({t.base, 2u * t.buckets, (uint32_t)ids, t.n_nodes + 1u});
+            ids += (uint64_t)t.n_nodes + 1u;
+        }
+        if (regs.empty()) return true;
+        if (ids >= 0xFFFFFFF0ull) return true; // (no records: the index still answers every lookup)
+        std::sort(regs.begin(), regs.end(), [](const TailRegion& a, const TailRegion& b) { return a.base < b.base; });
+        TailRegion* d_regs = (TailRegion*)x.alloc(sizeof(TailRegion) * regs.size());
+        uint32_t* scratch = (uint32_t*)x.alloc(sizeof(uint32_t) * 2 * (size_t)ids);
+        bool ok = d_regs && scratch;
+        if (ok) {
+            TailPass tp{d_regs, (uint32_t)regs.size(), scratch, scratch + ids};
+            ok = x.copy_in(d_regs, regs.data(), sizeof(TailRegion) * regs.size()) && x.zero(scratch, sizeof(uint32_t) * (size_t)ids) &&
+                 x.tails(mut(), tp, (uint32_t)trie_used) && x.sync();
+        }
+        if (d_regs) x.release(d_regs);
+        if (scratch) x.release(scratch);
+        return ok ? true : (d_regs && scratch ? xfail() : fail("out of memory (tail records)"));
+    }
+    bool built_regions() const { return trie != nullptr && trie_used != 0 && trie_used < 0xFFFFFFFFull; }
 
     // ---- id -> key ----
     // false + empty error: no such route (never existed or deleted)
@@ -1021,6 +1051,8 @@ private:
             while (want < (uint64_t)hbc.n_tokens * 4) want <<= 1;
             if (want != dict_slots && !grow_dict(want, dpool_cap)) return false;
         }
+        if (!form_tails()) return false;
+        pt.lap("rebuild: tail records");
         if (!x.sync()) return xfail();
         release_scratch();
         pt.lap("rebuild: dictionary resize, cleanup");

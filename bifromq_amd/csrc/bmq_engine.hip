@@ -815,7 +815,7 @@ int bmq_engine_create(const bmq_config* cfg, bmq_engine** out) {
     if (const char* v = bmq_env("BMQ_QCAP")) c.wave_queue_cap = (uint32_t)atoi(v); // profiling experiments
     if (const char* v = bmq_env("BMQ_PCAP")) c.wave_pair_cap = (uint32_t)atoi(v);
     if ((c.wave_queue_cap != 0 && c.wave_queue_cap != 128) || (c.wave_pair_cap != 0 && c.wave_pair_cap != 128)) return BMQ_E_INVAL;
-    if (c.region_slack > 64) return BMQ_E_INVAL;
+    if (c.region_slack > 64 || c.tail_records > 1) return BMQ_E_INVAL;
     const bool smallest = c.wave_queue_cap == 128 || c.wave_pair_cap == 128;
     c.wave_queue_cap = smallest ? WALK_QC_SMALLEST : WALK_QC_DEFAULT; // (what bmq_config reports back / BatchArgs carries: the geometry in use)
     c.wave_pair_cap = smallest ? WALK_PC_SMALLEST : WALK_PC_DEFAULT;
@@ -857,10 +857,12 @@ int bmq_engine_create(const bmq_config* cfg, bmq_engine** out) {
         e->dx.stream = e->dxi[0].stream = e->stream;
         e->dix = std::make_unique<DistIndex<DevExec>>(e->dxi[0]);
         if (c.region_slack) e->dix->slack_num = c.region_slack;
+        e->dix->tail_records = c.tail_records == 0;
         e->drt = std::make_unique<RetainDyn<DevExec>>(e->dx);
     } else {
         e->hix = std::make_unique<DistIndex<HostExec>>(e->hx);
         if (c.region_slack) e->hix->slack_num = c.region_slack;
+        e->hix->tail_records = c.tail_records == 0;
         e->hrt = std::make_unique<RetainDyn<HostExec>>(e->hx);
     }
     *out = e.release();
@@ -1055,10 +1057,12 @@ int bmq_compact_begin(bmq_engine* e) {
         e->cmp.bx = bx;
         e->cmp.next_d = std::make_unique<DistIndex<DevExec>>(*bx);
         e->cmp.next_d->slack_num = e->dix->slack_num;
+        e->cmp.next_d->tail_records = e->dix->tail_records;
         // the sizes below are read through the serving generation's executor: behind what the engine stream holds
     } else {
         e->cmp.next_h = std::make_unique<DistIndex<HostExec>>(e->hx);
         e->cmp.next_h->slack_num = e->hix->slack_num;
+        e->cmp.next_h->tail_records = e->hix->tail_records;
     }
     std::string msg;
     if (!with_generations(e, [&](auto& cur, auto& next) {
@@ -1131,6 +1135,15 @@ int bmq_compact_swap(bmq_engine* e, uint64_t* out_carried, uint64_t* out_replaye
     if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
     poller_stop_locked(e); // (the generations change places below)
     if (int rc = replay_log(e, 0)) return rc; // what the serving generation was told since bmq_compact_begin, in order
+    {
+        std::string msg; // the tail records of the new generation (bulk loads form them in rebuild; the carry-over came through the apply path)
+        if (!with_generations(e, [&](auto&, auto& next) {
+                const bool r = next.form_tails();
+                if (!r) msg = next.error;
+                return r;
+            }))
+            return index_error(e, msg, false, c.bx);
+    }
     if (e->dix) {
         HIPCHK(e, hipStreamSynchronize(e->s_build));
         HIPCHK(e, hipStreamSynchronize(e->stream));

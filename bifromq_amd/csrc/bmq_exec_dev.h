@@ -73,6 +73,14 @@ __global__ __launch_bounds__(BK) void k_b_rehash(DistIndexMut ix, uint32_t old_b
     const uint32_t s = blockIdx.x * BK + threadIdx.x;
     if (s < old_slots) rehash_one(ix, old_base, new_base, new_buckets, s, pass, d);
 }
+__global__ __launch_bounds__(BK) void k_b_tail_count(DistIndexMut ix, TailPass tp, uint32_t n_slots) {
+    const uint32_t g = blockIdx.x * BK + threadIdx.x;
+    if (g < n_slots) tail_count_one(ix, tp, g);
+}
+__global__ __launch_bounds__(BK) void k_b_tail_place(DistIndexMut ix, TailPass tp, uint32_t n_slots) {
+    const uint32_t g = blockIdx.x * BK + threadIdx.x;
+    if (g < n_slots) tail_place_one(ix, tp, g);
+}
 __global__ __launch_bounds__(BK) void k_b_dict_rehash(const DictSlot* old, uint32_t old_slots, DistIndexMut ix) {
     const uint32_t i = blockIdx.x * BK + threadIdx.x;
     if (i < old_slots) dict_rehash_one(old, i, ix);
@@ -311,6 +319,11 @@ struct DevExec {
     bool rehash(const DistIndexMut& ix, uint32_t old_base, uint32_t old_slots, uint32_t new_base, uint32_t new_buckets, uint32_t d) {
         hipLaunchKernelGGL(k_b_rehash, grid(old_slots, BK), dim3(BK), 0, stream, ix, old_base, old_slots, new_base, new_buckets, 0u, d);
         hipLaunchKernelGGL(k_b_rehash, grid(old_slots, BK), dim3(BK), 0, stream, ix, old_base, old_slots, new_base, new_buckets, 1u, d); // ('+' children beside their parents)
+        return launched();
+    }
+    bool tails(const DistIndexMut& ix, const TailPass& tp, uint32_t n_slots) {
+        hipLaunchKernelGGL(k_b_tail_count, grid(n_slots, BK), dim3(BK), 0, stream, ix, tp, n_slots);
+        hipLaunchKernelGGL(k_b_tail_place, grid(n_slots, BK), dim3(BK), 0, stream, ix, tp, n_slots);
         return launched();
     }
     bool dict_rehash(const DictSlot* old, uint32_t old_slots, const DistIndexMut& ix) {

@@ -119,6 +119,11 @@ struct HostExec {
         for (uint32_t pass = 0; pass < 2; pass++) par(old_slots, [&](size_t s) { rehash_one(ix, old_base, new_base, new_buckets, (uint32_t)s, pass, d); });
         return true;
     }
+    bool tails(const DistIndexMut& ix, const TailPass& tp, uint32_t n_slots) {
+        par(n_slots, [&](size_t g) { tail_count_one(ix, tp, (uint32_t)g); });
+        par(n_slots, [&](size_t g) { tail_place_one(ix, tp, (uint32_t)g); });
+        return true;
+    }
     bool dict_rehash(const DictSlot* old, uint32_t old_slots, const DistIndexMut& ix) {
         par(old_slots, [&](size_t i) { dict_rehash_one(old, (uint32_t)i, ix); });
         return true;

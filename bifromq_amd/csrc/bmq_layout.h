@@ -17,7 +17,14 @@
 //     '+' children, and a walk that has fetched X's line then has X/+ with it -- no second line, no second round.  The '+' child of a
 //     tenant ROOT sits at its hashed home and the directory entry remembers where (TenantSlot.root_plus);
 //   * '#' children are never nodes: the routes of "<path>/#" hang off the parent (hash_*);
-//   * the tenant root is not a slot: its payload lives in the directory entry the walk reads anyway.
+//   * the tenant root is not a slot: its payload lives in the directory entry the walk reads anyway;
+//   * TAIL RECORDS: when the subtree of node X is a unary chain X -> c1 -> ... -> ck (one child per level, k <= TAIL_K, routes only at ck, and
+//     those of ONE kind: own or '#') and the other slot of X's line is free, the builder's tail pass puts a record there: edge key
+//     (X, TOK_TAIL), then (begin, count | TAIL_HASH?) of ck's payload, then the tokens of c1..ck (TOK_PLUS allowed; NONE behind the last).  The
+//     chain stays in the trie -- the record only lets a walk that has fetched X's line resolve c1..ck without fetching them.  Any put / delete
+//     whose path runs through X turns the record into a TOMBSTONE (key (X, TOK_TOMB): matches nothing, is not free -- lookups stop at the first
+//     bucket with a free slot, so an occupied slot is never freed); a region growth drops records and tombstones; rebuild and compaction form
+//     them again (bmq_config.tail_records).
 // Route ids: after bmq_rebuild the id of a route is the rank of its KV key (keys arrive sorted from the KV iterator);
 // routes added later by bmq_routes_apply get the next unused ids.  An id never changes and is never reused until the
 // next bmq_rebuild; per id the key store holds (offset, length) of the key bytes and a hash of the key's tail.
@@ -46,6 +53,10 @@ constexpr uint32_t NONE = 0xFFFFFFFFu;        // empty slot / no child / node id
 constexpr uint32_t TOK_UNKNOWN = 0;           // level string not in the dictionary
 constexpr uint32_t TOK_PLUS = 1;              // the '+' edge
 constexpr uint32_t TOK_FIRST = 2;             // first dictionary token
+constexpr uint32_t TOK_TOMB = 0xFFFFFFFDu;    // key token of an invalidated tail record (no real edge, no lookup produces it)
+constexpr uint32_t TOK_TAIL = 0xFFFFFFFEu;    // key token of a tail record (ditto); every token >= TOK_TOMB marks a slot that is not a node
+constexpr uint32_t TAIL_K = 4;                // levels a tail record holds at most
+constexpr uint32_t TAIL_HASH = 0x40000000u;   // tail record count flag: the payload is ck's '#' routes (else its own routes)
 #ifndef BMQ_FAST_LEVELS
 #define BMQ_FAST_LEVELS 16
 #endif
@@ -66,6 +77,9 @@ struct alignas(32) TrieSlot {
     uint32_t lit_bloom;   // bits 0-30: Bloom mask over the literal children's tokens; bit 31: a '+' child exists
 };
 static_assert(sizeof(TrieSlot) == 32, "TrieSlot must be 32 bytes");
+// A tail record in a TrieSlot: parent = X's node id, token = TOK_TAIL, own_begin / own_count = ck's payload (count | TAIL_HASH for '#' routes),
+// hash_begin, hash_count, node, lit_bloom = the tokens of c1 .. c4 (NONE behind ck).
+BMQ_HD bool slot_is_node(const TrieSlot& s) { return s.parent != NONE && s.token < TOK_TOMB; }
 
 // Tenant directory entry = the tenant's region of the slot table + the payload of the tenant's ROOT node (every topic of the
 // tenant starts there, so the walk takes it from the directory entry it reads anyway: no line fetch, no round).

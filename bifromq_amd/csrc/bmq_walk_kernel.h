@@ -69,6 +69,7 @@ template <int TC, int QC, int PC, bool MIXED> struct WalkLds { // byte offsets i
 #ifdef BMQ_WAVE_EMU
 struct WalkCoverage {
     unsigned long long flushes = 0, parks = 0, restores = 0;
+    unsigned long long tails = 0, tail_levels = 0, tail_leaves = 0; // tail records read, chain levels they resolved, leaves they reached
 };
 inline WalkCoverage walk_cov;
 #define BMQ_WALK_COV(field) do { if (threadIdx.x == 0) walk_cov.field++; } while (0)
@@ -347,29 +348,58 @@ __device__ __forceinline__ void walk_wave(const BatchArgs& a, const uint32_t blo
             // token --: no item, no line, no round of its own.  Otherwise (the slot holds some other edge) the '+' child sits at its hashed home.
             const uint32_t o_parent = m1 ? line.a0.x : line.b0.x, o_token = m1 ? line.a0.y : line.b0.y;
             const bool plus_here = (int32_t)bloom_in < 0 && o_parent == child && o_token == TOK_PLUS;
-            // (P's payload leaves the line's registers HERE, in front of the first sink: with the whole line alive across it the compiler
-            // spilled 30 vector registers of the 64 that 8 waves per SIMD allow)
+            // Or the other slot holds the found node's TAIL RECORD (bmq_layout.h): its subtree is the chain c1..ck whose tokens the record
+            // holds.  The topic's next levels are compared with them right here ('+' matches any level); j leading levels match = j chain nodes
+            // discovered; ck's payload is emitted by the second part below if the topic reaches ck (own routes: if it also ends there).  No child
+            // is probed for.  (A node has a '+' child beside it or a record there, never both.)
+            const bool tail_here = found && !last && o_parent == child && o_token == TOK_TAIL;
+            // (P's payload -- or the record -- leaves the line's registers HERE, in front of the first sink: with the whole line alive across it the
+            // compiler spilled 30 vector registers of the 64 that 8 waves per SIMD allow)
             const uint32_t p_own_begin = m1 ? line.a0.z : line.b0.z, p_own_count = m1 ? line.a0.w : line.b0.w;
-            const uint32_t p_hash_begin = m1 ? line.a1.x : line.b1.x, p_hash_count = m1 ? line.a1.y : line.b1.y;
-            const uint32_t p_node = m1 ? line.a1.z : line.b1.z, p_bloom = m1 ? line.a1.w : line.b1.w;
-            if (found) atomicAdd(&cnt_visit[tl], plus_here ? 2u : 1u); // (LDS, no return value)
+            uint32_t p_hash_begin = m1 ? line.a1.x : line.b1.x, p_hash_count = m1 ? line.a1.y : line.b1.y;
+            const uint32_t p_node = m1 ? line.a1.z : line.b1.z;
+            uint32_t p_bloom = m1 ? line.a1.w : line.b1.w;
+            const bool p_last = rem == 1; // P's level is the topic's last
+            uint32_t q_own_count = (plus_here && p_last) ? p_own_count : 0u, n_tail = 0;
+            if (tail_here) { // record: (begin, count | TAIL_HASH, c1, c2, c3, c4) with NONE behind ck
+                const uint32_t tp = (meta >> 6) & 1023u;
+                const uint32_t r0 = p_hash_begin, r1 = p_hash_count, r2 = p_node, r3 = p_bloom;
+                const uint32_t k = 1u + (r1 != NONE ? 1u : 0u) + (r2 != NONE ? 1u : 0u) + (r3 != NONE ? 1u : 0u);
+                bool ok = (r0 == TOK_PLUS || r0 == tnext);
+                n_tail = ok ? 1u : 0u;
+                ok = ok && rem > 1u && (r1 == TOK_PLUS || r1 == tnext2);
+                n_tail += ok ? 1u : 0u;
+                ok = ok && rem > 2u && (r2 == TOK_PLUS || r2 == tokens[tp + 3]);
+                n_tail += ok ? 1u : 0u;
+                ok = ok && rem > 3u && (r3 == TOK_PLUS || r3 == tokens[tp + 4]);
+                n_tail += ok ? 1u : 0u;
+                const bool reach = n_tail == k, is_hash = (p_own_count & TAIL_HASH) != 0;
+                const uint32_t cnt = p_own_count & ~TAIL_HASH;
+                q_own_count = (reach && !is_hash && rem == k) ? cnt : 0u;
+                p_hash_begin = p_own_begin, p_hash_count = (reach && is_hash) ? cnt : 0u, p_bloom = 0u;
+            } else {
+                p_hash_count = plus_here ? p_hash_count : 0u;
+                p_bloom = (plus_here && !p_last) ? p_bloom : 0u;
+            }
+            if (found) atomicAdd(&cnt_visit[tl], (plus_here ? 2u : 1u) + n_tail); // (LDS, no return value)
+#ifdef BMQ_WAVE_EMU
+            if (tail_here) walk_cov.tails++, walk_cov.tail_levels += n_tail, walk_cov.tail_leaves += (q_own_count | p_hash_count) != 0;
+#endif
             // the literal child: the next token is known to the dictionary (TOK_UNKNOWN = 0: min() drops it) and the node's Bloom word has its bit
             // ONE sink body run once or twice (not two copies of it: the second copy cost 11 spilled vector registers): first the found node,
-            // then -- if some lane of the wave has one -- the '+' child P beside it.  (P's own '+' child cannot lie beside P -- that slot
-            // holds P's parent --: it is at its hashed home, an ordinary '+' probe.)
+            // then -- if some lane of the wave has one -- the '+' child P beside it or the leaf of a tail record.  (P's own '+' child cannot lie
+            // beside P -- that slot holds P's parent --: it is at its hashed home, an ordinary '+' probe.)
             uint32_t e_own_begin = own_begin, e_own_count = (found && last) ? own_count : 0u, e_hash_begin = hash_begin;
             uint32_t e_hash_count = found ? hash_count : 0u; // "<path>/#" matches whatever follows, also nothing
-            uint32_t e_lit = min((bloom_in >> bloom_bit(tnext)) & 1u, tnext), e_bloom = plus_here ? 0u : bloom_in, e_child = child, e_meta = cmeta;
-            const bool second = ballot64(plus_here) != 0;
+            uint32_t e_lit = tail_here ? 0u : min((bloom_in >> bloom_bit(tnext)) & 1u, tnext), e_bloom = (plus_here || tail_here) ? 0u : bloom_in;
+            uint32_t e_child = child, e_meta = cmeta;
+            const bool second = ballot64(plus_here || tail_here) != 0;
 #pragma clang loop unroll(disable)
             for (uint32_t part = 0;; part++) {
                 sink(e_own_begin, e_own_count, e_hash_begin, e_hash_count, e_lit, e_bloom, e_child, e_meta, tl, ln);
                 if (part == 1 || !second) break;
-                const bool p_last = rem == 1; // P's level is the topic's last
-                const uint32_t p_bloom_in = (plus_here && !p_last) ? p_bloom : 0u;
-                e_own_begin = p_own_begin, e_own_count = (plus_here && p_last) ? p_own_count : 0u, e_hash_begin = p_hash_begin;
-                e_hash_count = plus_here ? p_hash_count : 0u;
-                e_lit = min((p_bloom_in >> bloom_bit(tnext2)) & 1u, tnext2), e_bloom = p_bloom_in, e_child = p_node, e_meta = cmeta + WALK_META_CHILD;
+                e_own_begin = p_own_begin, e_own_count = q_own_count, e_hash_begin = p_hash_begin, e_hash_count = p_hash_count;
+                e_lit = min((p_bloom >> bloom_bit(tnext2)) & 1u, tnext2), e_bloom = p_bloom, e_child = p_node, e_meta = cmeta + WALK_META_CHILD;
             }
         }
     };

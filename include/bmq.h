@@ -82,7 +82,13 @@ typedef struct bmq_config {
                                /* 0 = default = 6 (load factor 0.2, 160 bytes of region per trie node); 1 = load factor 0.4 (64 + 16 bytes  */
                                /* per node: the layout of rounds 2-5; k_walk is 8 % slower on the survey's workload -- more second probes), */
                                /* up to 64.  A memory / speed trade, nothing else depends on it                                            */
-    uint32_t reserved[4];
+    uint32_t tail_records;     /* 0 = default = on: after a bulk load and before a compacted generation serves, a node whose subtree is a   */
+                               /* unary chain of <= 4 levels with the routes at its end gets a 32-byte TAIL RECORD in the free slot of its   */
+                               /* line (the chain's tokens + its leaf's payload): the walk resolves the chain from the line it already has. */
+                               /* A put / delete whose path runs through the node invalidates the record (a tombstone); a region growth     */
+                               /* drops it; the next rebuild / compaction forms records again.  1 = off (no records).  Results are the same */
+                               /* either way                                                                           */
+    uint32_t reserved[3];
 } bmq_config;
 
 /* Counters of the last completed match batch (for roofline accounting). */

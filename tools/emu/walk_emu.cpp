@@ -367,6 +367,8 @@ int main(int argc, char** argv) {
                                                                                          (unsigned long long)cov.split_blocks, (unsigned long long)cov.split_overflow, (unsigned long long)cov.split_adj);
     printf("k_walk's work stack and range buffer: the range buffer flushed %llu times, the stack parked %llu times, %llu chunks taken back\n", walk_cov.flushes, walk_cov.parks, walk_cov.restores);
     if (rounds >= 8 && (walk_cov.flushes < 20 || walk_cov.parks < 20 || walk_cov.restores < 20)) FAIL("the cases hardly touched the cold paths of k_walk's lists\n");
+    printf("tail records: %llu read, %llu chain levels resolved from them, %llu leaves reached\n", walk_cov.tails, walk_cov.tail_levels, walk_cov.tail_leaves);
+    if (rounds >= 8 && (walk_cov.tails < 100 || walk_cov.tail_leaves == 0)) FAIL("the cases hardly read a tail record\n");
     if (rounds >= 8 && (!cov.mixed || !cov.slow_rows || !cov.spills || !cov.adj_slow || cov.adj_walked >= cov.adj_rows)) FAIL("the cases missed a path: mixed %llu slow %llu spills %llu\n", (unsigned long long)cov.mixed, (unsigned long long)cov.slow_rows, (unsigned long long)cov.spills);
     return 0;
 }
