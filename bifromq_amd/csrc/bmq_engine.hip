@@ -33,6 +33,7 @@
 #include "bmq_retain.h"
 #include "bmq_retain_dyn.h"
 #include "bmq_retain_kernels.h"
+#include "bmq_share.h"
 
 using namespace bmq;
 
@@ -206,6 +207,10 @@ struct bmq_engine {
     std::unique_ptr<Fanout<DevExec>> dfo;
     std::unique_ptr<Fanout<HostExec>> hfo;
     DevBuf fo_buf; // staging of bmq_fanout_group
+    // receivers of shared subscriptions (bmq_share.h): member tables + resolve scratch, created by the first call
+    std::unique_ptr<Share<DevExec>> dsh;
+    std::unique_ptr<Share<HostExec>> hsh;
+    DevBuf sh_buf; // staging of bmq_share_resolve
     // multi-GPU exchange inside the library (bmq_exchange.inc): RCCL communicator of this rank, its own stream
     void* comm = nullptr;
     int comm_world = 0, comm_rank = 0;
@@ -907,6 +912,7 @@ void bmq_engine_destroy(bmq_engine* e) {
         if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
         if (e->ev_join) (void)hipEventDestroy(e->ev_join);
         e->dfo.reset();
+        e->dsh.reset();
         e->drt.reset();
         e->dix.reset(); // frees the HBM arrays while the stream still exists
         e->dx.release(e->dx.tmp);
@@ -1870,4 +1876,5 @@ int32_t bmq_java_string_hash(const uint8_t* utf8, uint32_t len) { return java_st
 #include "bmq_range_engine.inc"
 #include "bmq_exchange.inc"
 #include "bmq_fanout_engine.inc"
+#include "bmq_share_engine.inc"
 #include "bmq_formats.inc"

@@ -16,6 +16,7 @@
 #include "bmq_fanout_core.h"
 #include "bmq_fanout_kernels.h"
 #include "bmq_retain_core.h"
+#include "bmq_share_kernels.h"
 
 namespace bmq {
 
@@ -206,6 +207,8 @@ struct DevExec {
         if (pinned) (void)hipHostFree(pinned);
         if (ev_up) (void)hipEventDestroy(ev_up);
         if (ev_back) (void)hipEventDestroy(ev_back);
+        for (auto& m : marks)
+            if (m) (void)hipEventDestroy(m);
     }
     bool sync() { return BMQ_X(hipStreamSynchronize(stream)); }
     bool copy_in_async(void* d, const void* s, size_t n) { return n == 0 || BMQ_X(hipMemcpyAsync(d, s, n, hipMemcpyHostToDevice, stream)); }
@@ -405,6 +408,48 @@ struct DevExec {
                     f.n_tiles, t[0], t[1], t[2], t[3]);
             for (auto& e : ev) (void)hipEventDestroy(e);
         }
+        return launched();
+    }
+    // ---- optional HIP-event marks between the steps of a pipeline (bmq_set_kernel_timing) ----
+    bool marks_on = false;
+    hipEvent_t marks[8] = {};
+    void mark(int i) {
+        if (!marks_on) return;
+        if (!marks[i] && hipEventCreate(&marks[i]) != hipSuccess) return;
+        (void)hipEventRecord(marks[i], stream);
+    }
+    float mark_ms(int a, int b) { // after a sync of the stream
+        float t = 0;
+        if (!marks_on || !marks[a] || !marks[b] || hipEventElapsedTime(&t, marks[a], marks[b]) != hipSuccess) return 0;
+        return t;
+    }
+    // ---- receivers of shared subscriptions (bmq_share.h; kernels: bmq_share_kernels.h) ----
+    bool sh_count(const DistIndexMut& ix, const ShareTables& T, const ShareBatch& b) {
+        hipLaunchKernelGGL(k_sh_count, grid(b.n_pairs, SH_BLOCK), dim3(SH_BLOCK), 0, stream, ix, T, b);
+        return launched();
+    }
+    bool sh_rows(const ShareTables& T, const ShareBatch& b) {
+        hipLaunchKernelGGL(k_sh_rows, grid(b.n_rows, SH_BLOCK), dim3(SH_BLOCK), 0, stream, T, b);
+        return launched();
+    }
+    // width: lanes per row (8, 16 or 64); at most 2^24 rows per launch, so that a launch stays below 2^32 threads
+    bool sh_resolve(const ShareTables& T, const ShareBatch& b, uint32_t width) {
+        const uint32_t chunk = 1u << 24;
+        for (uint32_t row0 = 0; row0 < b.n_rows; row0 += chunk) {
+            const uint32_t n = std::min(chunk, b.n_rows - row0);
+            const dim3 g = grid((unsigned long long)n * width, SH_BLOCK);
+            if (width == 8) hipLaunchKernelGGL(k_sh_resolve<8>, g, dim3(SH_BLOCK), 0, stream, T, b, row0, n);
+            else if (width == 16) hipLaunchKernelGGL(k_sh_resolve<16>, g, dim3(SH_BLOCK), 0, stream, T, b, row0, n);
+            else hipLaunchKernelGGL(k_sh_resolve<64>, g, dim3(SH_BLOCK), 0, stream, T, b, row0, n);
+        }
+        return launched();
+    }
+    bool sh_heads(const ShareBatch& b, bool emit) {
+        hipLaunchKernelGGL(k_sh_heads, grid(b.n_rows, SH_BLOCK), dim3(SH_BLOCK), 0, stream, b, emit ? 1 : 0);
+        return launched();
+    }
+    bool sh_groups(const ShareTables& T, const ShareBatch& b) {
+        hipLaunchKernelGGL(k_sh_groups, grid(b.n_rows, SH_BLOCK), dim3(SH_BLOCK), 0, stream, T, b);
         return launched();
     }
     // ---- retain direction (bmq_retain_core.h) ----

@@ -15,6 +15,7 @@
 #include "bmq_build_core.h"
 #include "bmq_fanout_core.h"
 #include "bmq_retain_core.h"
+#include "bmq_share_core.h"
 
 namespace bmq {
 
@@ -174,6 +175,37 @@ struct HostExec {
     }
     bool gather_bytes(const DistIndexMut& ix, const unsigned long long* refs, const uint64_t* offs, uint32_t n, uint8_t* out) {
         par(n, [&](size_t i) { gather_bytes_one(ix, refs, offs, (uint32_t)i, out); });
+        return true;
+    }
+    // ---- receivers of shared subscriptions (bmq_share.h) ----
+    void mark(int) {} // (HIP-event marks of the device executor)
+    float mark_ms(int, int) { return 0; }
+    bool sh_count(const DistIndexMut& ix, const ShareTables& T, const ShareBatch& b) {
+        par(b.n_pairs, [&](size_t i) {
+            unsigned long long scores = 0;
+            const unsigned long long rows = sh_count_one(ix, T, b, (uint32_t)i, scores);
+            __atomic_fetch_add(b.totals, rows, __ATOMIC_RELAXED);
+            __atomic_fetch_add(b.totals + 1, scores, __ATOMIC_RELAXED);
+        });
+        return true;
+    }
+    bool sh_rows(const ShareTables& T, const ShareBatch& b) {
+        par(b.n_rows, [&](size_t r) { sh_row_one(T, b, (uint32_t)r); });
+        return true;
+    }
+    bool sh_resolve(const ShareTables& T, const ShareBatch& b, uint32_t /*width*/) {
+        par(b.n_rows, [&](size_t r) { sh_resolve_one(T, b, (uint32_t)r); });
+        return true;
+    }
+    bool sh_heads(const ShareBatch& b, bool emit) {
+        par(b.n_rows, [&](size_t j) {
+            sh_head_one(b, (uint32_t)j);
+            if (emit) sh_emit_one(b, (uint32_t)j);
+        });
+        return true;
+    }
+    bool sh_groups(const ShareTables& T, const ShareBatch& b) {
+        par(b.n_rows, [&](size_t j) { sh_group_one(T, b, (uint32_t)j); });
         return true;
     }
     // ---- retain direction (bmq_retain_core.h) ----

@@ -1,0 +1,166 @@
+// bmq_share_engine.inc -- bmq_share_members_apply / bmq_share_resolve / bmq_share_resolve_dev / bmq_share_member / bmq_share_info_get: the
+// receivers of shared subscriptions (bmq_share_core.h says what they replace in the reference).  Included at the end of bmq_engine.hip.
+namespace {
+// the engine's Share over whichever executor it has, created by the first call.  A buffer that grows is freed first, and a free waits for
+// every stream of the device: the persistent matcher leaves before (it is back with the next singleton call).
+template <class F> int with_share(bmq_engine* e, F&& f) {
+    if (e->device < 0) {
+        if (!e->hsh) e->hsh = std::make_unique<Share<HostExec>>(e->hx);
+        return f(*e->hsh, *e->hix);
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    if (!e->dsh) {
+        e->dsh = std::make_unique<Share<DevExec>>(e->dx);
+        e->dsh->before_free = [e] { poller_stop_locked(e); };
+    }
+    e->dx.marks_on = e->kernel_events;
+    return f(*e->dsh, *e->dix);
+}
+template <class S> int share_error(bmq_engine* e, const S& s) { return index_error(e, s.error, s.invalid); }
+int share_result(bmq_engine* e, const ShareResult& r, uint32_t* out_n_rows, uint32_t* out_n_groups, uint32_t* out_special) {
+    if (out_n_rows) *out_n_rows = r.n_rows;
+    if (out_n_groups) *out_n_groups = r.n_groups;
+    if (out_special) *out_special = r.special;
+    return r.overflow ? set_err(e, BMQ_E_NOSPACE, "row buffers or group table too small") : BMQ_OK;
+}
+} // namespace
+
+extern "C" int bmq_share_members_apply(bmq_engine* e, const uint32_t* route_ids, uint32_t n, const uint32_t* member_off, const uint8_t* urls,
+                                       const uint32_t* url_off) {
+    if (!e) return BMQ_E_INVAL;
+    if (n && (!route_ids || !member_off || !url_off || (member_off[n] && !urls))) return set_err(e, BMQ_E_INVAL, "null pointer");
+    std::unique_lock<std::recursive_mutex> api_lock(e->api);
+    std::lock_guard<std::mutex> g(e->mu);
+    if (int rc_open = complete_apply(e)) return rc_open; // (a batch handed over with bmq_routes_apply_async first)
+    if (!e->built) return set_err(e, BMQ_E_STATE, "no index");
+    if (e->device >= 0) poller_stop_locked(e); // (the mutation path allocates and frees)
+    return with_share(e, [&](auto& sh, auto& ix) { return sh.apply(ix, route_ids, n, member_off, urls, url_off) ? (int)BMQ_OK : share_error(e, sh); });
+}
+
+extern "C" int bmq_share_resolve_dev(bmq_engine* e, const uint32_t* d_pair_topic, const uint32_t* d_pair_route, uint32_t n_pairs,
+                                     const uint32_t* d_sender_off, const int32_t* d_sender_hash, uint32_t n_topics, uint32_t n_senders, uint64_t nonce,
+                                     uint32_t* d_out_pair, uint32_t* d_out_sender, uint32_t* d_out_member, uint32_t row_cap, uint32_t* d_out_group_off,
+                                     uint32_t group_cap, uint32_t* out_n_rows, uint32_t* out_n_groups, uint32_t* out_special) {
+    if (!e) return BMQ_E_INVAL;
+    if (e->device < 0) return set_err(e, BMQ_E_NODEVICE, "engine is host-only");
+    if (!d_out_group_off || !d_sender_off || (n_pairs && (!d_pair_topic || !d_pair_route)) || (n_senders && !d_sender_hash) ||
+        (row_cap && (!d_out_pair || !d_out_sender || !d_out_member)))
+        return set_err(e, BMQ_E_INVAL, "null pointer");
+    std::unique_lock<std::recursive_mutex> api_lock(e->api);
+    std::lock_guard<std::mutex> g(e->mu);
+    if (int rc_open = complete_apply(e)) return rc_open; // (a batch handed over with bmq_routes_apply_async first)
+    if (!e->built) return set_err(e, BMQ_E_STATE, "no index");
+    ShareResult r;
+    const int rc = with_share(e, [&](auto& sh, auto& ix) {
+        return sh.resolve(ix, d_pair_topic, d_pair_route, n_pairs, d_sender_off, (const uint32_t*)d_sender_hash, n_topics, n_senders, nonce, d_out_pair,
+                          d_out_sender, d_out_member, row_cap, d_out_group_off, group_cap, r)
+                   ? (int)BMQ_OK
+                   : share_error(e, sh);
+    });
+    return rc ? rc : share_result(e, r, out_n_rows, out_n_groups, out_special);
+}
+
+extern "C" int bmq_share_resolve(bmq_engine* e, const uint32_t* pair_topic, const uint32_t* pair_route, uint32_t n_pairs, const uint32_t* sender_off,
+                                 const int32_t* sender_hash, uint32_t n_topics, uint64_t nonce, uint32_t* out_pair, uint32_t* out_sender,
+                                 uint32_t* out_member, uint32_t row_cap, uint32_t* out_group_off, uint32_t group_cap, uint32_t* out_n_rows,
+                                 uint32_t* out_n_groups, uint32_t* out_special) {
+    if (!e) return BMQ_E_INVAL;
+    if (!out_group_off || !sender_off || (n_pairs && (!pair_topic || !pair_route)) || (row_cap && (!out_pair || !out_sender || !out_member)))
+        return set_err(e, BMQ_E_INVAL, "null pointer");
+    if (sender_off[0] != 0) return set_err(e, BMQ_E_INVAL, "sender_off[0] != 0");
+    for (uint32_t t = 0; t < n_topics; t++)
+        if (sender_off[t + 1] < sender_off[t]) return set_err(e, BMQ_E_INVAL, "sender_off not ascending");
+    const uint32_t n_senders = sender_off[n_topics];
+    if (n_senders && !sender_hash) return set_err(e, BMQ_E_INVAL, "null pointer");
+    std::unique_lock<std::recursive_mutex> api_lock(e->api);
+    std::lock_guard<std::mutex> g(e->mu);
+    if (int rc_open = complete_apply(e)) return rc_open; // (a batch handed over with bmq_routes_apply_async first)
+    if (!e->built) return set_err(e, BMQ_E_STATE, "no index");
+    ShareResult r;
+    if (e->device < 0) { // host-only engine: the same per-item functions on host threads, straight on the caller's buffers
+        const int rc = with_share(e, [&](auto& sh, auto& ix) {
+            return sh.resolve(ix, pair_topic, pair_route, n_pairs, sender_off, (const uint32_t*)sender_hash, n_topics, n_senders, nonce, out_pair, out_sender,
+                              out_member, row_cap, out_group_off, group_cap, r)
+                       ? (int)BMQ_OK
+                       : share_error(e, sh);
+        });
+        return rc ? rc : share_result(e, r, out_n_rows, out_n_groups, out_special);
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    // staging: [pair_topic | pair_route | sender_off | sender_hash | out_pair | out_sender | out_member | group_off]
+    size_t o = 0;
+    auto take = [&](size_t words) {
+        const size_t at = o;
+        o += (words * 4 + 15) & ~(size_t)15;
+        return at;
+    };
+    const size_t o_pt = take(n_pairs), o_pr = take(n_pairs), o_so = take((size_t)n_topics + 1), o_sh = take(n_senders), o_op = take(row_cap),
+                 o_os = take(row_cap), o_om = take(row_cap), o_go = take((size_t)group_cap + 1);
+    if (o + 16 > e->sh_buf.cap) poller_stop_locked(e);
+    HIPCHK(e, e->sh_buf.ensure(o + 16));
+    uint8_t* d = e->sh_buf.as<uint8_t>();
+    hipStream_t s = e->stream;
+    if (n_pairs) {
+        HIPCHK(e, hipMemcpyAsync(d + o_pt, pair_topic, 4 * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+        HIPCHK(e, hipMemcpyAsync(d + o_pr, pair_route, 4 * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(e, hipMemcpyAsync(d + o_so, sender_off, 4 * ((size_t)n_topics + 1), hipMemcpyHostToDevice, s));
+    if (n_senders) HIPCHK(e, hipMemcpyAsync(d + o_sh, sender_hash, 4 * (size_t)n_senders, hipMemcpyHostToDevice, s));
+    const int rc = with_share(e, [&](auto& sh, auto& ix) {
+        return sh.resolve(ix, (const uint32_t*)(d + o_pt), (const uint32_t*)(d + o_pr), n_pairs, (const uint32_t*)(d + o_so), (const uint32_t*)(d + o_sh),
+                          n_topics, n_senders, nonce, (uint32_t*)(d + o_op), (uint32_t*)(d + o_os), (uint32_t*)(d + o_om), row_cap, (uint32_t*)(d + o_go),
+                          group_cap, r)
+                   ? (int)BMQ_OK
+                   : share_error(e, sh);
+    });
+    if (rc) return rc;
+    if (!r.overflow) {
+        if (r.n_rows) {
+            HIPCHK(e, hipMemcpyAsync(out_pair, d + o_op, 4 * (size_t)r.n_rows, hipMemcpyDeviceToHost, s));
+            HIPCHK(e, hipMemcpyAsync(out_sender, d + o_os, 4 * (size_t)r.n_rows, hipMemcpyDeviceToHost, s));
+            HIPCHK(e, hipMemcpyAsync(out_member, d + o_om, 4 * (size_t)r.n_rows, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(e, hipMemcpyAsync(out_group_off, d + o_go, 4 * ((size_t)r.n_groups + 1), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(e, hipStreamSynchronize(s));
+    return share_result(e, r, out_n_rows, out_n_groups, out_special);
+}
+
+extern "C" int bmq_share_member(const bmq_engine* ce, uint32_t route_id, uint32_t index, uint8_t* out_url, uint32_t cap, uint32_t* out_len) {
+    bmq_engine* e = const_cast<bmq_engine*>(ce);
+    if (!e || !out_len || (cap && !out_url)) return BMQ_E_INVAL;
+    std::unique_lock<std::recursive_mutex> api_lock(e->api);
+    std::lock_guard<std::mutex> g(e->mu);
+    if (int rc_open = complete_apply(e)) return rc_open;
+    if (!e->built) return set_err(e, BMQ_E_STATE, "no index");
+    std::string url;
+    const int rc = with_share(e, [&](auto& sh, auto& ix) { return sh.member(ix, route_id, index, url) ? (int)BMQ_OK : share_error(e, sh); });
+    if (rc) return rc;
+    *out_len = (uint32_t)url.size();
+    if (url.size() > cap) return set_err(e, BMQ_E_NOSPACE, "url buffer too small");
+    memcpy(out_url, url.data(), url.size());
+    return BMQ_OK;
+}
+
+extern "C" int bmq_share_info_get(const bmq_engine* ce, bmq_share_info* out) {
+    bmq_engine* e = const_cast<bmq_engine*>(ce);
+    if (!e || !out) return BMQ_E_INVAL;
+    std::unique_lock<std::recursive_mutex> api_lock(e->api);
+    std::lock_guard<std::mutex> g(e->mu);
+    if (int rc_open = complete_apply(e)) return rc_open;
+    memset(out, 0, sizeof(*out));
+    ShareInfo si;
+    const int rc = with_share(e, [&](auto& sh, auto& ix) { return sh.info(ix, si) ? (int)BMQ_OK : share_error(e, sh); });
+    if (rc) return rc;
+    out->n_tables = si.n_tables;
+    out->n_members = si.n_members;
+    out->n_deliverers = si.n_deliverers;
+    out->device_bytes = e->device >= 0 ? si.bytes : 0;
+    out->generation = si.generation;
+    out->ms_count = si.ms[0];
+    out->ms_rows = si.ms[1];
+    out->ms_resolve = si.ms[2];
+    out->ms_sort = si.ms[3];
+    out->ms_group = si.ms[4];
+    return BMQ_OK;
+}

@@ -534,6 +534,68 @@ class Engine:
             raise err
         return ng.value, sp.value
 
+    # ---- receivers of shared subscriptions (DeliverExecutorGroup.send(GroupMatching, ...)) --------------------------------------------
+    def share_members_apply(self, tables):
+        """bmq_share_members_apply.  tables: {route id: [receiverUrl, ...]} (or a sequence of such pairs); the list order is the
+        reference's receiverList order, an empty list removes the route's table."""
+        items = list(tables.items()) if hasattr(tables, "items") else list(tables)
+        ids = np.array([i for i, _ in items], dtype=np.uint32)
+        moff = np.zeros(len(items) + 1, dtype=np.uint32)
+        moff[1:] = np.cumsum([len(m) for _, m in items])
+        data, off = pack([_b(u) for _, m in items for u in m])
+        self._check(_lib.lib().bmq_share_members_apply(self.h, _ptr(ids), len(items), _ptr(moff), _ptr(data), _ptr(off)))
+        return self
+
+    def share_resolve(self, pair_topic, pair_route, sender_off, sender_hash, nonce: int, row_cap: Optional[int] = None, group_cap: int = 256):
+        """bmq_share_resolve -> (out_pair, out_sender, out_member, group_off, special): delivery rows ordered by (share-deliverer number,
+        pair, sender); group g owns rows group_off[g] .. group_off[g + 1]; special bit 0: the last group holds the unresolved rows."""
+        pt = np.ascontiguousarray(pair_topic, dtype=np.uint32)
+        pr = np.ascontiguousarray(pair_route, dtype=np.uint32)
+        so = np.ascontiguousarray(sender_off, dtype=np.uint32)
+        sh = np.ascontiguousarray(sender_hash, dtype=np.int32)
+        if row_cap is None:
+            row_cap = max(len(pt), 1)
+        nr, ng, sp = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        while True:
+            op, os_, om = (np.zeros(max(row_cap, 1), dtype=np.uint32) for _ in range(3))
+            goff = np.zeros(group_cap + 1, dtype=np.uint32)
+            rc = _lib.lib().bmq_share_resolve(self.h, _ptr(pt), _ptr(pr), len(pt), _ptr(so), _ptr(sh), len(so) - 1, nonce & 0xFFFFFFFFFFFFFFFF,
+                                              _ptr(op), _ptr(os_), _ptr(om), row_cap, _ptr(goff), group_cap, C.byref(nr), C.byref(ng), C.byref(sp))
+            if rc == -3 and (nr.value > row_cap or ng.value > group_cap):
+                row_cap, group_cap = max(row_cap, nr.value), max(group_cap, ng.value)
+                continue
+            self._check(rc)
+            return op[:nr.value], os_[:nr.value], om[:nr.value], goff[:ng.value + 1], sp.value
+
+    def share_resolve_device(self, d_pair_topic, d_pair_route, n_pairs, d_sender_off, d_sender_hash, n_topics, n_senders, nonce: int,
+                             d_out_pair, d_out_sender, d_out_member, row_cap, d_group_off, group_cap):
+        """All d_* are device pointers (ints).  -> (n_rows, n_groups, special); BmqError -3 (.needed = (rows, groups)) if a capacity is too small."""
+        nr, ng, sp = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        rc = _lib.lib().bmq_share_resolve_dev(self.h, d_pair_topic, d_pair_route, n_pairs, d_sender_off, d_sender_hash, n_topics, n_senders,
+                                              nonce & 0xFFFFFFFFFFFFFFFF, d_out_pair, d_out_sender, d_out_member, row_cap, d_group_off, group_cap,
+                                              C.byref(nr), C.byref(ng), C.byref(sp))
+        if rc:
+            err = BmqError(rc, (_lib.lib().bmq_last_error(self.h) or b"").decode())
+            err.needed = (nr.value, ng.value)
+            raise err
+        return nr.value, ng.value, sp.value
+
+    def share_member(self, route_id: int, index: int) -> bytes:
+        """bmq_share_member: receiverUrl of member `index` of the route's table"""
+        n = C.c_uint32()
+        buf = C.create_string_buffer(512)
+        rc = _lib.lib().bmq_share_member(self.h, int(route_id), int(index), buf, len(buf), C.byref(n))
+        if rc == -3:
+            buf = C.create_string_buffer(n.value)
+            rc = _lib.lib().bmq_share_member(self.h, int(route_id), int(index), buf, len(buf), C.byref(n))
+        self._check(rc)
+        return buf.raw[:n.value]
+
+    def share_info(self) -> _lib.ShareInfo:
+        out = _lib.ShareInfo()
+        self._check(_lib.lib().bmq_share_info_get(self.h, C.byref(out)))
+        return out
+
     def finish(self) -> int:
         total = C.c_uint64()
         self._check(_lib.lib().bmq_match_finish(self.h, C.byref(total)))

@@ -544,7 +544,8 @@ int bmq_routes_cap(bmq_engine* e, const uint32_t* row_ptr, const uint32_t* route
  *        out_group_off[*out_n_groups + 1]: group g owns the pairs out_group_off[g] .. out_group_off[g + 1];
  *        out_group_rep[g]: a route id of the group (bmq_route_key of it gives the group's subBrokerId and delivererKey: the first
  *        and the third NUL-separated part of its receiverUrl, SCHEMA/KVSchemaUtil.java:56-58), 0xFFFFFFFE for the group of
- *        shared-subscription routes (flag 2 / 3: DeliverExecutorGroup.java:243-279 picks the receiver per message), 0xFFFFFFFF for
+ *        shared-subscription routes (flag 2 / 3: DeliverExecutorGroup.java:243-279 picks the receiver per message; bmq_share_resolve
+ *        below does that for the group's pairs on the device), 0xFFFFFFFF for
  *        the group of ids whose route has been deleted since the match.
  * A group = one DelivererKey, exactly (key bytes are compared, not only hashes).  The normal groups come first, in no particular
  * order (the reference's batcher map is a HashMap), then the shared-subscription group (*out_special bit 0), then the dead group
@@ -560,6 +561,73 @@ int bmq_fanout_group(bmq_engine* e, const uint32_t* row_ptr, const uint32_t* rou
 int bmq_fanout_group_dev(bmq_engine* e, const uint32_t* d_row_ptr, const uint32_t* d_route_ids, uint32_t n_topics, uint64_t total,
                          uint32_t* d_out_topic, uint32_t* d_out_route, uint32_t* d_out_group_off, uint32_t* d_out_group_rep,
                          uint32_t group_cap, uint32_t* out_n_groups, uint32_t* out_special);
+
+/* ---- receivers of shared subscriptions: the step behind the fan-out grouping ------------------------------------------------------ */
+/* DeliverExecutorGroup.send(GroupMatching, ...) (bifromq-dist/bifromq-dist-worker/src/main/java/org/apache/bifromq/dist/worker/
+ * DeliverExecutorGroup.java:242-278) turns every route of a shared subscription into deliveries to MEMBERS of the group; the members
+ * are the `members: receiverUrl -> incarnation` of the group route's value, receiverList = that map in entry order (bifromq-dist/
+ * bifromq-dist-worker-schema/src/main/java/org/apache/bifromq/dist/worker/schema/cache/GroupMatching.java:41-50):
+ *   unordered share ($share, route-key flag 2): the topic's whole message pack goes to ONE member, picked uniformly at random;
+ *   ordered share ($oshare, flag 3): per publisher of the pack, the member with the highest score wins (base-util/src/main/java/org/
+ *     apache/bifromq/base/util/RendezvousHash.java:45-61), score = murmur3_128(seed 0) over [int32 little-endian sender hash][UTF-8
+ *     receiverUrl], asLong() = h1 of MurmurHash3_x64_128 compared as a SIGNED 64-bit value, strict '>' in list order (the first of equal
+ *     scores wins).  The sender hash is ClientInfo.hashCode(): only the JVM can compute it, it is an input here.  (The reference caches
+ *     the winner per (filter, sender) and drops the cache when the group mutates: recomputing per batch gives the same answer.)
+ * The chosen member is a NormalMatching of its own receiverUrl "<subBrokerId> NUL <receiverId> NUL <delivererKey>": it is sent like any
+ * normal route, under ITS DelivererKey(subBrokerId, delivererKey).
+ *
+ * bmq_share_members_apply: replaces the member list of each of the n named group routes by the URLs member_off[i] .. member_off[i + 1]
+ *   of (urls, url_off[member_off[n] + 1]), in that order (= receiverList order); an empty list removes the route's table.  Before anything
+ *   changes it is checked (BMQ_E_INVAL) that every id is a live route of flag 2 or 3, that every URL has exactly the three NUL-separated
+ *   parts, and that no list has more than 65 535 members.  Ordered or not comes from the route key's flag.  The tables live in device
+ *   memory (bmq_share_info.device_bytes), pre-mixed for the hash (bifromq_amd/csrc/bmq_share_core.h).  They are keyed by route id, so they
+ *   belong to ONE generation of the route index: bmq_rebuild, bmq_compact and bmq_compact_swap drop them all (the caller reloads the KV
+ *   range then anyway), and bmq_share_info.generation says which generation the tables belong to.  A route deleted by bmq_routes_apply
+ *   leaves its table unreachable (its id is dead).  Every distinct (subBrokerId, delivererKey) among the members of a generation gets a
+ *   dense share-deliverer number (exact byte comparison); members that differ only in receiverId share one.
+ *
+ * bmq_share_resolve: in : n_pairs (topic index, route id) pairs -- typically the slice out_group_off[g] .. out_group_off[g + 1] of the
+ *        0xFFFFFFFE group of bmq_fanout_group / bmq_match_wait_grouped, but any pair list is accepted --; the publishers of each topic's
+ *        message pack as sender_off[n_topics + 1], sender_hash[sender_off[n_topics]]; a nonce, fresh per batch.
+ *   out: delivery rows (out_pair[r], out_sender[r], out_member[r]), r < *out_n_rows:
+ *        unordered route: one row, out_sender = 0xFFFFFFFF (the whole pack), out_member = the picked index into the route's list:
+ *            x = fmix64((nonce ^ ((uint64_t)route_id << 32 | topic_index)) + 0x9E3779B97F4A7C15), 64-bit wrap-around, where fmix64 is
+ *            MurmurHash3's finalizer (k ^= k >> 33; k *= 0xff51afd7ed558ccd; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53; k ^= k >> 33);
+ *            member = (uint32_t)(((x >> 32) * n_members) >> 32);
+ *        ordered route: one row per sender of the pair's topic (none if it has none), out_sender = index into sender_hash, out_member =
+ *            the rendezvous winner;
+ *        a pair whose route has no table, is dead, or is no shared route: one row with out_member = 0xFFFFFFFF.
+ *        out_pair is the index into the pair list.  Rows are ordered by (share-deliverer number, pair, sender); group g owns the rows
+ *        out_group_off[g] .. out_group_off[g + 1] and its DelivererKey is that of its first row's member (bmq_share_member gives the URL);
+ *        the unresolved rows form the last group (*out_special bit 0).
+ *   BMQ_E_NOSPACE: row_cap < *out_n_rows or group_cap < *out_n_groups; both counts are reported, nothing else is valid.
+ *   Fewer than 2^31 pairs and rows per call.  Works on a host-only engine too (the same per-item functions on host threads).
+ * _dev: every array is a device pointer (the pairs may be those bmq_fanout_group_dev left in HBM), n_senders = the length of
+ *   d_sender_hash; runs on the engine stream and returns when the rows are complete. */
+typedef struct bmq_share_info {
+    uint64_t n_tables;     /* group routes with a member table */
+    uint64_t n_members;    /* members in all of them */
+    uint64_t n_deliverers; /* share-deliverer numbers handed out in this generation */
+    uint64_t device_bytes; /* tables and resolve scratch in device memory (0: host-only engine) */
+    uint64_t generation;   /* generation of the route index the tables belong to (bmq_index_info.generation) */
+    /* HIP-event times of the last resolve on the device while bmq_set_kernel_timing is on (else 0): rows per pair + scan, the rows'
+     * pairs and senders, the resolve kernel, the sort by share-deliverer number, group heads + scan + offsets */
+    float ms_count, ms_rows, ms_resolve, ms_sort, ms_group;
+    uint32_t reserved0;
+} bmq_share_info;
+int bmq_share_members_apply(bmq_engine* e, const uint32_t* route_ids, uint32_t n, const uint32_t* member_off, const uint8_t* urls,
+                            const uint32_t* url_off);
+int bmq_share_resolve(bmq_engine* e, const uint32_t* pair_topic, const uint32_t* pair_route, uint32_t n_pairs, const uint32_t* sender_off,
+                      const int32_t* sender_hash, uint32_t n_topics, uint64_t nonce, uint32_t* out_pair, uint32_t* out_sender,
+                      uint32_t* out_member, uint32_t row_cap, uint32_t* out_group_off, uint32_t group_cap, uint32_t* out_n_rows,
+                      uint32_t* out_n_groups, uint32_t* out_special);
+int bmq_share_resolve_dev(bmq_engine* e, const uint32_t* d_pair_topic, const uint32_t* d_pair_route, uint32_t n_pairs,
+                          const uint32_t* d_sender_off, const int32_t* d_sender_hash, uint32_t n_topics, uint32_t n_senders, uint64_t nonce,
+                          uint32_t* d_out_pair, uint32_t* d_out_sender, uint32_t* d_out_member, uint32_t row_cap, uint32_t* d_out_group_off,
+                          uint32_t group_cap, uint32_t* out_n_rows, uint32_t* out_n_groups, uint32_t* out_special);
+/* receiverUrl of member `index` of the route's table -> out_url[*out_len]; BMQ_E_INVAL: no such table / member; BMQ_E_NOSPACE: cap < *out_len */
+int bmq_share_member(const bmq_engine* e, uint32_t route_id, uint32_t index, uint8_t* out_url, uint32_t cap, uint32_t* out_len);
+int bmq_share_info_get(const bmq_engine* e, bmq_share_info* out);
 
 /* ---- dist-server side range pruning ---------------------------------------------------------------------- */
 /* TenantRangeLookupCache.lookup (bifromq-dist/bifromq-dist-server/src/main/java/org/apache/bifromq/dist/server/scheduler/
