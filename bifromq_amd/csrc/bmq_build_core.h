@@ -762,6 +762,15 @@ BMQ_HD void locate_one(const DistIndexMut& ix, const OpBatch& ob, uint32_t i, ui
         if (created) {
             const uint32_t bit = tok == TOK_PLUS ? BLOOM_PLUS : (1u << bloom_bit(tok));
             if (!(atom_load(bloom) & bit)) atom_or(bloom, bit);
+            // the parent's child filter words (bmq_layout.h): the begin word of each of its EMPTY ranges.  Counts are written by the group step
+            // only, behind a kernel boundary: a plain look at the count, then an atomic OR on the begin word -- no lane of this kernel changes a
+            // count, so a word that is a filter now stays one until the locate passes are over.  (The tenant root has no such words.)
+            if (tok != TOK_PLUS && !at_root) {
+                TrieSlot& ps = ix.trie[slot_abs];
+                const uint32_t b_own = 1u << filter_bit_own(tok), b_hash = 1u << filter_bit_hash(tok);
+                if (shared_load(&ps.own_count) == 0 && !(atom_load(&ps.own_begin) & b_own)) atom_or(&ps.own_begin, b_own);
+                if (shared_load(&ps.hash_count) == 0 && !(atom_load(&ps.hash_begin) & b_hash)) atom_or(&ps.hash_begin, b_hash);
+            }
         }
         node = child;
         slot_abs = sa;
@@ -953,7 +962,6 @@ BMQ_HD void group_one(const DistIndexMut& ix, const OpBatch& ob, uint32_t p) {
             if (blk == 0 && !s.indirect() && (m == 0 || m == n - 1)) { // an end of a plain range
                 if (m == 0) s.begin++;
                 s.cf = n - 1;
-                if (s.cf == 0) s.begin = 0;
             } else if (blk == 0) {
                 if (!privatise(m)) break;
             } else {
@@ -965,6 +973,10 @@ BMQ_HD void group_one(const DistIndexMut& ix, const OpBatch& ob, uint32_t p) {
     }
     if (failed) return; // nothing shared was touched; the block request is on record (rp_need)
     if (s.indirect() && s.count() == 0) s = IdSet{0, 0}; // (its block becomes garbage below)
+    // An empty range of a node: its begin word is a child filter word (bmq_layout.h).  Empty before and after (a delete that found nothing, a put
+    // and its delete in one batch): the word as locate left it -- s0 was read behind the locate kernels, the bits of this batch's new children
+    // are in it.  Emptied by this group: the route ids overwrote the bits, all-ones = "no information".  The root's '#' range (kind 2): 0 as ever.
+    if (s.cf == 0) s.begin = kind == 2 ? 0u : (s0.cf == 0 ? s0.begin : FILTER_NONE);
     // ---- commit ----
     unsigned long long garbage = 0;
     if (s0.indirect() && (blk != 0 || !s.indirect())) garbage += (unsigned long long)ix.route_pos[s0.begin - 1] + 1;

@@ -81,6 +81,7 @@ public:
     uint64_t generation = 0; // bumped by every rebuild: ids of different generations are unrelated
     uint32_t slack_num = BMQ_REGION_SLACK_NUM; // region size = nodes * (1 + slack_num / 4) buckets (bmq_config.region_slack)
     bool tail_records = true; // the tail pass after a bulk load / before a compacted generation serves (bmq_config.tail_records)
+    bool child_filters = true; // the walk reads the child filter words of the nodes (bmq_config.child_filters); the builder keeps them either way
     bool tiny = false;       // test knob (tools/host_fuzz.cpp): minimal initial capacities, so that every growth path runs all the time
 
     // ---- arrays in exec memory ----
@@ -117,6 +118,7 @@ public:
         v.trie = trie;
         v.tenants = dir;
         v.tenant_mask = dir_slots - 1;
+        v.filter_off = child_filters ? 0u : 0xFFFFFFFFu;
         v.tenant_names = names;
         v.dict = dict;
         v.dict_group_mask = dict_slots / DICT_GROUP - 1;

@@ -820,7 +820,7 @@ int bmq_engine_create(const bmq_config* cfg, bmq_engine** out) {
     if (const char* v = bmq_env("BMQ_QCAP")) c.wave_queue_cap = (uint32_t)atoi(v); // profiling experiments
     if (const char* v = bmq_env("BMQ_PCAP")) c.wave_pair_cap = (uint32_t)atoi(v);
     if ((c.wave_queue_cap != 0 && c.wave_queue_cap != 128) || (c.wave_pair_cap != 0 && c.wave_pair_cap != 128)) return BMQ_E_INVAL;
-    if (c.region_slack > 64 || c.tail_records > 1) return BMQ_E_INVAL;
+    if (c.region_slack > 64 || c.tail_records > 1 || c.child_filters > 1) return BMQ_E_INVAL;
     const bool smallest = c.wave_queue_cap == 128 || c.wave_pair_cap == 128;
     c.wave_queue_cap = smallest ? WALK_QC_SMALLEST : WALK_QC_DEFAULT; // (what bmq_config reports back / BatchArgs carries: the geometry in use)
     c.wave_pair_cap = smallest ? WALK_PC_SMALLEST : WALK_PC_DEFAULT;
@@ -863,11 +863,13 @@ int bmq_engine_create(const bmq_config* cfg, bmq_engine** out) {
         e->dix = std::make_unique<DistIndex<DevExec>>(e->dxi[0]);
         if (c.region_slack) e->dix->slack_num = c.region_slack;
         e->dix->tail_records = c.tail_records == 0;
+        e->dix->child_filters = c.child_filters == 0;
         e->drt = std::make_unique<RetainDyn<DevExec>>(e->dx);
     } else {
         e->hix = std::make_unique<DistIndex<HostExec>>(e->hx);
         if (c.region_slack) e->hix->slack_num = c.region_slack;
         e->hix->tail_records = c.tail_records == 0;
+        e->hix->child_filters = c.child_filters == 0;
         e->hrt = std::make_unique<RetainDyn<HostExec>>(e->hx);
     }
     *out = e.release();
@@ -1064,11 +1066,13 @@ int bmq_compact_begin(bmq_engine* e) {
         e->cmp.next_d = std::make_unique<DistIndex<DevExec>>(*bx);
         e->cmp.next_d->slack_num = e->dix->slack_num;
         e->cmp.next_d->tail_records = e->dix->tail_records;
+        e->cmp.next_d->child_filters = e->dix->child_filters;
         // the sizes below are read through the serving generation's executor: behind what the engine stream holds
     } else {
         e->cmp.next_h = std::make_unique<DistIndex<HostExec>>(e->hx);
         e->cmp.next_h->slack_num = e->hix->slack_num;
         e->cmp.next_h->tail_records = e->hix->tail_records;
+        e->cmp.next_h->child_filters = e->hix->child_filters;
     }
     std::string msg;
     if (!with_generations(e, [&](auto& cur, auto& next) {

@@ -25,6 +25,15 @@
 //     whose path runs through X turns the record into a TOMBSTONE (key (X, TOK_TOMB): matches nothing, is not free -- lookups stop at the first
 //     bucket with a free slot, so an occupied slot is never freed); a region growth drops records and tombstones; rebuild and compaction form
 //     them again (bmq_config.tail_records).
+//   * CHILD FILTERS: the `begin` word of a node's EMPTY range (own_count == 0 -> own_begin, hash_count == 0 -> hash_begin) names no route and no
+//     reader of a range looks at it: there it is one more filter word over the node's literal children, 32 bits, one bit per child token
+//     (filter_bit_own / filter_bit_hash: two mixes of the token that share nothing with bloom_bit's).  The 31 bits of lit_bloom are saturated exactly
+//     where they are asked most -- below the wildcard branches ("l0_x/+", "+/l1_y": dozens of children, the topic's token usually not among them)
+//     -- and a probe for a child that does not exist is a line that misses L2 for nothing; nearly every such node has one or both ranges empty.
+//     A word is a SUPERSET of its children's bits: a node comes into being with both words 0 (no child), the builder ORs a bit in with every
+//     literal child it creates, and a range that loses its last route gets all-ones ("no information": the route ids overwrote the bits).  The
+//     walk may ignore the words (bmq_config.child_filters): they only ever spare a probe.  The tenant root has none (its payload is the
+//     directory entry's); tail records and tombstones are not nodes.
 // Route ids: after bmq_rebuild the id of a route is the rank of its KV key (keys arrive sorted from the KV iterator);
 // routes added later by bmq_routes_apply get the next unused ids.  An id never changes and is never reused until the
 // next bmq_rebuild; per id the key store holds (offset, length) of the key bytes and a hash of the key's tail.
@@ -70,8 +79,8 @@ struct alignas(32) TrieSlot {
     uint32_t parent;      // tenant-local node id of the parent (0 = tenant root); NONE = free slot
     uint32_t token;       // dictionary token of the edge label (TOK_PLUS for '+')
     uint32_t own_begin;   // routes whose filter ends at this node: ids own_begin .. +count-1, or
-    uint32_t own_count;   //   route_pos[own_begin ..] when (own_count & RANGE_INDIRECT)
-    uint32_t hash_begin;  // routes of "<this path>/#", same encoding
+    uint32_t own_count;   //   route_pos[own_begin ..] when (own_count & RANGE_INDIRECT); 0: own_begin is a child filter word (above)
+    uint32_t hash_begin;  // routes of "<this path>/#", same encoding (hash_count == 0: a child filter word)
     uint32_t hash_count;
     uint32_t node;        // this node's tenant-local id (>= 1); NONE until the inserting thread has published it
     uint32_t lit_bloom;   // bits 0-30: Bloom mask over the literal children's tokens; bit 31: a '+' child exists
@@ -158,6 +167,16 @@ BMQ_HD uint32_t bloom_bit(uint32_t token) {
     const uint32_t b = (token ^ (token >> 5) ^ (token >> 11)) & 31u;
     return b - (b == 31u ? 1u : 0u); // 31 -> 30
 }
+// Child filter words (the begin word of an empty range): bit of a literal child token in own_begin / in hash_begin.  One multiplicative mix of
+// the token, its top five bits and the five below them: bloom_bit folds the token's low 16 bits with XORs, these take the high end of a
+// product every bit of the token reaches -- the three indices of one token are as good as independent (tools/bloom_census.cpp measures it).
+// (One 32-bit multiply per probe decision: quarter rate, and the walk waits on memory, not on issue slots.)
+constexpr uint32_t FILTER_MUL = 0x9E3779B1u;
+constexpr uint32_t FILTER_NONE = 0xFFFFFFFFu; // "no information": every bit set
+BMQ_HD uint32_t filter_bit_own(uint32_t token) { return (token * FILTER_MUL) >> 27; }
+BMQ_HD uint32_t filter_bit_hash(uint32_t token) { return ((token * FILTER_MUL) >> 22) & 31u; }
+// the filter word a range contributes: its begin word if it is empty, else all-ones
+BMQ_HD uint32_t filter_word(uint32_t begin, uint32_t count) { return count == 0 ? begin : FILTER_NONE; }
 // 64-bit hash of a tenant id (FNV-1a over the bytes, then a finaliser); never 0
 BMQ_HD uint64_t tenant_hash_step(uint64_t h, uint32_t byte) { return (h ^ byte) * 0x100000001B3ull; }
 constexpr uint64_t TENANT_HASH_INIT = 0xCBF29CE484222325ull;
@@ -173,6 +192,7 @@ struct DistIndexView {
     const TrieSlot* trie;
     const TenantSlot* tenants;
     uint32_t tenant_mask;        // tenant directory slots - 1
+    uint32_t filter_off;         // 0: the walk reads the child filter words; all-ones: it ignores them (bmq_config.child_filters = 1)
     const uint8_t* tenant_names; // tenant id bytes (TenantSlot.name_off / name_len)
     const DictSlot* dict;
     uint32_t dict_group_mask;    // (dictionary slots / DICT_GROUP) - 1

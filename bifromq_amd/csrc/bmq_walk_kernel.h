@@ -140,11 +140,10 @@ __device__ __forceinline__ void walk_wave(const BatchArgs& a, const uint32_t blo
         const uint32_t n16 = (s_end - a0 + 15) >> 4;
         for (uint32_t o = lane; o < n16; o += 64) dst[o] = src[o];
     }
-    uint32_t nlev = 0, tbytes = 0, pos = 0, end = 0, ti = 0xFFFFFFFFu;
+    uint32_t nlev = 0, pos = 0, end = 0, ti = 0xFFFFFFFFu;
     if (valid) {
         pos = a.topic_off[t];
         end = a.topic_off[t + 1];
-        tbytes = end - pos;
         ti = a.topic_tenant[t];
     }
     // walked here: rows of tenants the batch names -- with in-batch de-duplication (k_dedup) only the representative of every (tenant, topic)
@@ -205,6 +204,7 @@ __device__ __forceinline__ void walk_wave(const BatchArgs& a, const uint32_t blo
     // (base, length; length 0 ends the chain), so the bookkeeping is two wave-uniform registers per chain.
     // Everything below that is named s_* or is a list fill level is WAVE-UNIFORM and kept so explicitly (sgpr()).
     uint32_t tail = 0, pcount = 0, rounds = 0, items = 0;
+    const uint32_t f_off = a.ix.filter_off; // all-ones: the child filter words are ignored (bmq_config.child_filters = 1)
     uint32_t fl_base = 0, fl_len = 0; // last flushed range chunk
     uint32_t qs_base = 0, qs_len = 0; // last parked stack chunk (LIFO)
     auto spill_alloc = [&](const BatchArgs& c, uint32_t ln, uint32_t n, uint32_t& base) -> bool { // wave-uniform; n payload records + header
@@ -378,8 +378,13 @@ __device__ __forceinline__ void walk_wave(const BatchArgs& a, const uint32_t blo
                 q_own_count = (reach && !is_hash && rem == k) ? cnt : 0u;
                 p_hash_begin = p_own_begin, p_hash_count = (reach && is_hash) ? cnt : 0u, p_bloom = 0u;
             } else {
+                // P's literal child is decided HERE, with P's Bloom word, its child filter words and the token behind P's level all at hand, and
+                // travels across the first sink in bit 0 of p_bloom (whose bit 31 is all the second part reads otherwise): no register more
+                // than before, and tnext2 and P's Bloom bits need not live across the sink
+                const uint32_t ph = tnext2 * FILTER_MUL;
+                const uint32_t pf = (((p_own_count | f_off) != 0 ? FILTER_NONE : p_own_begin) >> (ph >> 27)) & (((p_hash_count | f_off) != 0 ? FILTER_NONE : p_hash_begin) >> ((ph >> 22) & 31u));
                 p_hash_count = plus_here ? p_hash_count : 0u;
-                p_bloom = (plus_here && !p_last) ? p_bloom : 0u;
+                p_bloom = (plus_here && !p_last) ? ((p_bloom & BLOOM_PLUS) | min((p_bloom >> bloom_bit(tnext2)) & pf & 1u, tnext2)) : 0u;
             }
             if (found) atomicAdd(&cnt_visit[tl], (plus_here ? 2u : 1u) + n_tail); // (LDS, no return value)
 #ifdef BMQ_WAVE_EMU
@@ -391,7 +396,11 @@ __device__ __forceinline__ void walk_wave(const BatchArgs& a, const uint32_t blo
             // beside P -- that slot holds P's parent --: it is at its hashed home, an ordinary '+' probe.)
             uint32_t e_own_begin = own_begin, e_own_count = (found && last) ? own_count : 0u, e_hash_begin = hash_begin;
             uint32_t e_hash_count = found ? hash_count : 0u; // "<path>/#" matches whatever follows, also nothing
-            uint32_t e_lit = tail_here ? 0u : min((bloom_in >> bloom_bit(tnext)) & 1u, tnext), e_bloom = (plus_here || tail_here) ? 0u : bloom_in;
+            // ... AND the node's child filter words have theirs (bmq_layout.h: the begin word of an empty range; a range with routes, or the walk told to
+            // ignore the words -- f_off all-ones --, contributes all-ones).  The payload words are in registers here anyway.
+            const uint32_t fh = tnext * FILTER_MUL;
+            const uint32_t f_lit = (((own_count | f_off) != 0 ? FILTER_NONE : own_begin) >> (fh >> 27)) & (((hash_count | f_off) != 0 ? FILTER_NONE : hash_begin) >> ((fh >> 22) & 31u));
+            uint32_t e_lit = tail_here ? 0u : min((bloom_in >> bloom_bit(tnext)) & f_lit & 1u, tnext), e_bloom = (plus_here || tail_here) ? 0u : bloom_in;
             uint32_t e_child = child, e_meta = cmeta;
             const bool second = ballot64(plus_here || tail_here) != 0;
 #pragma clang loop unroll(disable)
@@ -399,7 +408,7 @@ __device__ __forceinline__ void walk_wave(const BatchArgs& a, const uint32_t blo
                 sink(e_own_begin, e_own_count, e_hash_begin, e_hash_count, e_lit, e_bloom, e_child, e_meta, tl, ln);
                 if (part == 1 || !second) break;
                 e_own_begin = p_own_begin, e_own_count = q_own_count, e_hash_begin = p_hash_begin, e_hash_count = p_hash_count;
-                e_lit = min((p_bloom >> bloom_bit(tnext2)) & 1u, tnext2), e_bloom = p_bloom, e_child = p_node, e_meta = cmeta + WALK_META_CHILD;
+                e_lit = p_bloom & 1u, e_bloom = p_bloom, e_child = p_node, e_meta = cmeta + WALK_META_CHILD; // (p_bloom: bit 0 = P's literal child, bit 31 = its '+' child)
             }
         }
     };
@@ -427,9 +436,12 @@ __device__ __forceinline__ void walk_wave(const BatchArgs& a, const uint32_t blo
             const uint32_t tk = tokens[actp ? tok_base + part : 0u]; // (a lane that is not active reads entry 0: its own tok_base may lie beyond the table)
             const bool root_sys = part == 0 && sys;                  // a first-level wildcard never matches a '$' topic
             const uint32_t bloom_in = (actp && nlev > part) ? bl : 0u; // children only while the topic has a level left
+            // the child filter words of P0 / PP0 (wave-uniform: scalar selects); the root has none
+            const uint32_t f_own = (part == 0 || (pl.y | f_off) != 0) ? FILTER_NONE : pl.x, f_hash = (part == 0 || (pl.w | f_off) != 0) ? FILTER_NONE : pl.z;
+            const uint32_t fh = tk * FILTER_MUL;
             if (part != 0 && actp) cnt_visit[ln] += 1u; // (the lane's own topic; the drain's atomics come later)
             sink(pl.x, (actp && nlev == part) ? pl.y : 0u /* (part 0: pl.y = 0: a topic has at least one level) */,
-                 pl.z, (actp && !root_sys) ? pl.w : 0u, min((bloom_in >> bloom_bit(tk)) & 1u, tk),
+                 pl.z, (actp && !root_sys) ? pl.w : 0u, min((bloom_in >> bloom_bit(tk)) & (f_own >> (fh >> 27)) & (f_hash >> ((fh >> 22) & 31u)) & 1u, tk),
                  (root_sys || part < rp.has) ? (bloom_in & ~BLOOM_PLUS) : bloom_in, // ('+' child resolved by the next part, or probed for at its hashed home)
                  nd, walk_meta(ln, tok_base + part, nlev - 1 - part), ln, ln);
             actp = actp && !root_sys && (int32_t)bloom_in < 0;
@@ -510,6 +522,11 @@ __device__ __forceinline__ void walk_wave(const BatchArgs& a, const uint32_t blo
     const unsigned long long clk2 = dbg_clock(dbg_w);
     const BatchArgs& d = a;
     const uint32_t l3 = lane_here();
+    // (the row index and the topic bytes are formed AGAIN here, from the opaque lane id and two scalar loads of the offsets the wave began with,
+    // instead of living in two vector registers across the walk: with the child filter tests in the loop those two were what the compiler
+    // spilled to scratch -- 9 spilled vector registers, 32 B/lane; so: 5 and 24 B/lane, fewer than before the tests came)
+    const uint32_t t3_first = blk << d.tpw_shift, t3 = t3_first + l3;
+    const bool valid3 = l3 < (1u << d.tpw_shift) && t3 < d.n_topics;
     cnt_pairs[l3] = 0;
     cnt_routes[l3] = 0;
     wave_sync();
@@ -575,21 +592,21 @@ __device__ __forceinline__ void walk_wave(const BatchArgs& a, const uint32_t blo
             d.pairs[base + dst] = MatchRange{r.x, r.y};
         }
     }
-    if (valid) {
-        d.pair_off[t] = (uint32_t)(base + excl); // pair_cap < 2^32 is enforced by the host
-        d.pair_cnt[t] = np;
-        d.route_cnt[t] = nr;
+    if (valid3) {
+        d.pair_off[t3] = (uint32_t)(base + excl); // pair_cap < 2^32 is enforced by the host
+        d.pair_cnt[t3] = np;
+        d.route_cnt[t3] = nr;
         if (flagged && ti < d.n_tenants) { // deeper than FAST_LEVELS: the per-lane walk of k_walk_slow
             const uint32_t sp = atomicAdd(&d.ctr->slow_count, 1u);
-            if (sp < d.slow_cap) d.slow_list[sp] = t;
+            if (sp < d.slow_cap) d.slow_list[sp] = t3;
             else atomicOr(&d.ctr->status, ST_NEED_SLOW);
         }
     }
     const uint32_t vis = cnt_visit[l3];
-    if (valid && d.visit_cnt) d.visit_cnt[t] = vis;
+    if (valid3 && d.visit_cnt) d.visit_cnt[t3] = vis;
     const unsigned long long wsum = wave_sum_u64(nr);
     const unsigned long long wvis = wave_sum_u64(vis);
-    const unsigned long long wbytes = wave_sum_u64(tbytes);
+    const unsigned long long wbytes = scalar_words(d.topic_off)[min(t3_first + (1u << d.tpw_shift), d.n_topics)] - scalar_words(d.topic_off)[t3_first]; // the wave's topics are contiguous
     if (l3 == 0) {
         if (d.rep == nullptr) { // (with in-batch de-duplication k_fill writes these, every duplicate row counted with its representative's figures)
             d.wave_sums[blk] = wsum;

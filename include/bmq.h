@@ -88,7 +88,11 @@ typedef struct bmq_config {
                                /* A put / delete whose path runs through the node invalidates the record (a tombstone); a region growth     */
                                /* drops it; the next rebuild / compaction forms records again.  1 = off (no records).  Results are the same */
                                /* either way                                                                           */
-    uint32_t reserved[3];
+    uint32_t child_filters;    /* 0 = default = on: the walk kernel also asks a node's CHILD FILTER WORDS -- the begin word of each of its    */
+                               /* empty route ranges, 32 more filter bits over its literal children that the index builder maintains --      */
+                               /* before it probes for a literal child: fewer probes for children that do not exist.  1 = the walk ignores    */
+                               /* the words (the builder keeps them all the same).  Results are the same either way    */
+    uint32_t reserved[2];
 } bmq_config;
 
 /* Counters of the last completed match batch (for roofline accounting). */
