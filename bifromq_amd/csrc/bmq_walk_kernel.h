@@ -70,6 +70,13 @@ template <int TC, int QC, int PC, bool MIXED> struct WalkLds { // byte offsets i
 struct WalkCoverage {
     unsigned long long flushes = 0, parks = 0, restores = 0;
     unsigned long long tails = 0, tail_levels = 0, tail_leaves = 0; // tail records read, chain levels they resolved, leaves they reached
+    // per record length k (1..TAIL_K) and leaf kind (0: own routes, 1: '#' routes): leaf reached and emitted; stopped by a token after j matched
+    // levels (j < k); the topic ran out after j matched levels (1 <= j < k)
+    unsigned long long tail_reach[TAIL_K + 1][2] = {}, tail_stop[TAIL_K + 1][2][TAIL_K] = {}, tail_short[TAIL_K + 1][2][TAIL_K] = {};
+    unsigned long long tail_plus[TAIL_K] = {}, tombs = 0; // a '+' of the record matched at level j; tombstones met beside a found node
+    // child filter words, per decision site (0: boot P0 / PP0, 1: drain node, 2: drain '+' sibling): probes the words spared (Bloom bit set, a filter
+    // bit clear); decisions that consulted an all-ones word (a range that lost its last route)
+    unsigned long long cf_spared[3] = {}, cf_ones[3] = {};
 };
 inline WalkCoverage walk_cov;
 #define BMQ_WALK_COV(field) do { if (threadIdx.x == 0) walk_cov.field++; } while (0)
@@ -353,6 +360,9 @@ __device__ __forceinline__ void walk_wave(const BatchArgs& a, const uint32_t blo
             // discovered; ck's payload is emitted by the second part below if the topic reaches ck (own routes: if it also ends there).  No child
             // is probed for.  (A node has a '+' child beside it or a record there, never both.)
             const bool tail_here = found && !last && o_parent == child && o_token == TOK_TAIL;
+#ifdef BMQ_WAVE_EMU
+            if (found && !last && o_parent == child && o_token == TOK_TOMB) walk_cov.tombs++;
+#endif
             // (P's payload -- or the record -- leaves the line's registers HERE, in front of the first sink: with the whole line alive across it the
             // compiler spilled 30 vector registers of the 64 that 8 waves per SIMD allow)
             const uint32_t p_own_begin = m1 ? line.a0.z : line.b0.z, p_own_count = m1 ? line.a0.w : line.b0.w;
@@ -377,12 +387,26 @@ __device__ __forceinline__ void walk_wave(const BatchArgs& a, const uint32_t blo
                 const uint32_t cnt = p_own_count & ~TAIL_HASH;
                 q_own_count = (reach && !is_hash && rem == k) ? cnt : 0u;
                 p_hash_begin = p_own_begin, p_hash_count = (reach && is_hash) ? cnt : 0u, p_bloom = 0u;
+#ifdef BMQ_WAVE_EMU
+                {
+                    const uint32_t kind = is_hash ? 1u : 0u, rr[TAIL_K] = {r0, r1, r2, r3};
+                    if (reach && (q_own_count | p_hash_count) != 0) walk_cov.tail_reach[k][kind]++;
+                    else if (n_tail < k) (rem == n_tail ? walk_cov.tail_short : walk_cov.tail_stop)[k][kind][n_tail]++;
+                    for (uint32_t j = 0; j < n_tail && j < TAIL_K; j++) walk_cov.tail_plus[j] += rr[j] == TOK_PLUS;
+                }
+#endif
             } else {
                 // P's literal child is decided HERE, with P's Bloom word, its child filter words and the token behind P's level all at hand, and
                 // travels across the first sink in bit 0 of p_bloom (whose bit 31 is all the second part reads otherwise): no register more
                 // than before, and tnext2 and P's Bloom bits need not live across the sink
                 const uint32_t ph = tnext2 * FILTER_MUL;
                 const uint32_t pf = (((p_own_count | f_off) != 0 ? FILTER_NONE : p_own_begin) >> (ph >> 27)) & (((p_hash_count | f_off) != 0 ? FILTER_NONE : p_hash_begin) >> ((ph >> 22) & 31u));
+#ifdef BMQ_WAVE_EMU
+                if (plus_here && !p_last && f_off == 0) {
+                    walk_cov.cf_spared[2] += tnext2 != 0 && ((p_bloom >> bloom_bit(tnext2)) & 1u) != 0 && (pf & 1u) == 0;
+                    walk_cov.cf_ones[2] += (p_own_count == 0 && p_own_begin == FILTER_NONE) || (p_hash_count == 0 && p_hash_begin == FILTER_NONE);
+                }
+#endif
                 p_hash_count = plus_here ? p_hash_count : 0u;
                 p_bloom = (plus_here && !p_last) ? ((p_bloom & BLOOM_PLUS) | min((p_bloom >> bloom_bit(tnext2)) & pf & 1u, tnext2)) : 0u;
             }
@@ -402,6 +426,12 @@ __device__ __forceinline__ void walk_wave(const BatchArgs& a, const uint32_t blo
             const uint32_t f_lit = (((own_count | f_off) != 0 ? FILTER_NONE : own_begin) >> (fh >> 27)) & (((hash_count | f_off) != 0 ? FILTER_NONE : hash_begin) >> ((fh >> 22) & 31u));
             uint32_t e_lit = tail_here ? 0u : min((bloom_in >> bloom_bit(tnext)) & f_lit & 1u, tnext), e_bloom = (plus_here || tail_here) ? 0u : bloom_in;
             uint32_t e_child = child, e_meta = cmeta;
+#ifdef BMQ_WAVE_EMU
+            if (found && !last && !tail_here && f_off == 0) {
+                walk_cov.cf_spared[1] += tnext != 0 && ((bloom_in >> bloom_bit(tnext)) & 1u) != 0 && (f_lit & 1u) == 0;
+                walk_cov.cf_ones[1] += (own_count == 0 && own_begin == FILTER_NONE) || (hash_count == 0 && hash_begin == FILTER_NONE);
+            }
+#endif
             const bool second = ballot64(plus_here || tail_here) != 0;
 #pragma clang loop unroll(disable)
             for (uint32_t part = 0;; part++) {
@@ -440,6 +470,13 @@ __device__ __forceinline__ void walk_wave(const BatchArgs& a, const uint32_t blo
             const uint32_t f_own = (part == 0 || (pl.y | f_off) != 0) ? FILTER_NONE : pl.x, f_hash = (part == 0 || (pl.w | f_off) != 0) ? FILTER_NONE : pl.z;
             const uint32_t fh = tk * FILTER_MUL;
             if (part != 0 && actp) cnt_visit[ln] += 1u; // (the lane's own topic; the drain's atomics come later)
+#ifdef BMQ_WAVE_EMU
+            if (part != 0 && actp && nlev > part && f_off == 0) {
+                const uint32_t s_own = fh >> 27, s_hash = (fh >> 22) & 31u;
+                walk_cov.cf_spared[0] += tk != 0 && ((bloom_in >> bloom_bit(tk)) & 1u) != 0 && (((f_own >> s_own) & (f_hash >> s_hash)) & 1u) == 0;
+                walk_cov.cf_ones[0] += (pl.y == 0 && pl.x == FILTER_NONE) || (pl.w == 0 && pl.z == FILTER_NONE);
+            }
+#endif
             sink(pl.x, (actp && nlev == part) ? pl.y : 0u /* (part 0: pl.y = 0: a topic has at least one level) */,
                  pl.z, (actp && !root_sys) ? pl.w : 0u, min((bloom_in >> bloom_bit(tk)) & (f_own >> (fh >> 27)) & (f_hash >> ((fh >> 22) & 31u)) & 1u, tk),
                  (root_sys || part < rp.has) ? (bloom_in & ~BLOOM_PLUS) : bloom_in, // ('+' child resolved by the next part, or probed for at its hashed home)

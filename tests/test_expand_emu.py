@@ -67,7 +67,9 @@ def test_the_match_kernels_of_the_dist_direction_under_the_wave_emulator(tmp_pat
     """tools/emu/walk_emu.cpp: k_walk<TC, QC, PC, MIXED> (the dominant kernel; both LDS geometries, the grouped and the MIXED instantiation), k_walk_slow
     and k_expand behind them, compiled by g++ from the product's sources (bmq_dist_kernels.h with its device-only pieces stepped aside: the library's
     machine code is unchanged, tools/kernel_isa.py) and run on indexes the product's own builder makes on the host -- fresh and after mutations -- against a
-    brute force over the model's route keys: '$' topics, empty levels, unknown tenants, waves that hold several tenants, batches in any order, topics and
+    brute force over the model's route keys and the count of discovered nodes of every batch against a model of the trie's nodes, through a sequence of index
+    states per round (a random batch, directed steps on a family of unary chains for the tail records, region growth, compaction; alternate rounds without records;
+    every batch with the child filter words read and ignored -- tests/test_walk_mutants.py keeps the harness honest): '$' topics, empty levels, unknown tenants, waves that hold several tenants, batches in any order, topics and
     filters deeper than FAST_LEVELS, spill chains of the stack and the range buffer, and ordered batches full of repeats through the whole
     bmq_config.dedup_sorted pipeline (neighbour compare -> dense batch -> walk kernels -> k_fill_adj -> k_expand), and k_expand's heavy blocks -- listed by
     k_walk / k_fill_adj, expanded by four waves each, the list overflowing; the harness fails if its cases miss one of those paths."""
