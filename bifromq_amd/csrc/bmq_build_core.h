@@ -1226,4 +1226,48 @@ BMQ_HD void gather_bytes_one(const DistIndexMut& ix, const unsigned long long* r
     for (unsigned long long k = 0; k < len; k++) out[offs[i] + k] = ix.kpool[off + k];
 }
 
+// ---- KV boundary of a range (IKVRangeCoProc.reset(Boundary), DW/DistWorkerCoProc.java:283-291): which keys a range owns ----
+// flags bit 0: a start key is present, bit 1: an end key is present (a present key may be empty).  The key bytes lie where the executor
+// reads them: exec memory, or the workgroup's LDS copy on the device (k_b_boundary).
+struct KeyBoundary {
+    const uint8_t* start;
+    const uint8_t* end;
+    uint32_t start_len, end_len;
+    uint32_t flags;
+};
+// unsigned lexicographic order of a[0, an) against b[0, bn), a proper prefix first: < 0, 0, > 0.  Eight bytes a step: the words are loaded
+// at whatever alignment the key has in the pool (memcpy: no alignment is assumed) and compared byte-swapped, i.e. as big-endian numbers;
+// the first step that differs decides -- route keys of different tenants differ within `00 | u16be(len) | tenant`.  The tail of fewer than
+// eight bytes goes byte by byte: nothing outside [a, a + an) and [b, b + bn) is read (the pool's pad belongs to the batch, not to the key).
+BMQ_HD int key_compare(const uint8_t* a, unsigned long long an, const uint8_t* b, unsigned long long bn) {
+    const unsigned long long m = an < bn ? an : bn;
+    unsigned long long p = 0;
+    for (; p + 8 <= m; p += 8) {
+        unsigned long long x, y;
+        __builtin_memcpy(&x, a + p, 8);
+        __builtin_memcpy(&y, b + p, 8);
+        if (x != y) return __builtin_bswap64(x) < __builtin_bswap64(y) ? -1 : 1;
+    }
+    for (; p < m; p++)
+        if (a[p] != b[p]) return a[p] < b[p] ? -1 : 1;
+    return an < bn ? -1 : (an > bn ? 1 : 0);
+}
+// BoundaryUtil.inRange (base-kv/.../utils/BoundaryUtil.java:241-252): (no start or key >= start) and (no end or key < end)
+BMQ_HD bool key_in_boundary(const uint8_t* kpool, unsigned long long ref, const KeyBoundary& b) {
+    const uint8_t* k = kpool + (ref & KREF_OFF_MASK);
+    const unsigned long long len = ref >> KREF_LEN_SHIFT;
+    if ((b.flags & 1u) && key_compare(k, len, b.start, b.start_len) < 0) return false;
+    if ((b.flags & 2u) && key_compare(k, len, b.end, b.end_len) >= 0) return false;
+    return true;
+}
+// one key reference of a chunk (import_snapshot's copy): a live key outside the boundary loses its length bits -- a dead id to whatever
+// reads the chunk next.  Returns the key's length if it is live and inside, 0 otherwise.
+BMQ_HD unsigned long long boundary_filter_one(const uint8_t* kpool, unsigned long long* refs, uint32_t i, const KeyBoundary& b) {
+    const unsigned long long r = refs[i];
+    if ((r >> KREF_LEN_SHIFT) == 0) return 0;
+    if (key_in_boundary(kpool, r, b)) return r >> KREF_LEN_SHIFT;
+    refs[i] = r & KREF_OFF_MASK;
+    return 0;
+}
+
 } // namespace bmq

@@ -52,6 +52,30 @@ struct DistIndexStats {
 struct ApplyResult {
     uint32_t added = 0, removed = 0, dups = 0;
 };
+// A KV boundary as the host holds it (IKVRangeCoProc.reset(Boundary), DW/DistWorkerCoProc.java:283-291).  flags bit 0: `start` is present,
+// bit 1: `end` is present; a present key may be empty.  Order: key_compare (unsigned bytes, a proper prefix first).
+struct Boundary {
+    uint8_t flags = 0;
+    std::string start, end;
+    static int cmp(std::string_view a, std::string_view b) {
+        return key_compare((const uint8_t*)a.data(), a.size(), (const uint8_t*)b.data(), b.size());
+    }
+    bool bounded() const { return (flags & 3u) != 0; }
+    bool valid() const { return (flags & 3u) != 3u || cmp(start, end) < 0; } // (no start, end = "": NULL_BOUNDARY, valid and empty)
+    // BoundaryUtil.inRange (base-kv/.../utils/BoundaryUtil.java:241-252)
+    bool contains(std::string_view k) const { return (!(flags & 1u) || cmp(k, start) >= 0) && (!(flags & 2u) || cmp(k, end) < 0); }
+    // no key that begins with `prefix` is inside: end <= prefix, or start >= upperBound(prefix) (the prefix with its last byte below 0xFF
+    // incremented and what follows it cut off; a prefix of 0xFF bytes only has no upper bound)
+    bool excludes_prefix(std::string_view prefix) const {
+        if ((flags & 2u) && cmp(end, prefix) <= 0) return true;
+        if (!(flags & 1u)) return false;
+        std::string ub(prefix);
+        while (!ub.empty() && (uint8_t)ub.back() == 0xFF) ub.pop_back();
+        if (ub.empty()) return false;
+        ub.back() = (char)((uint8_t)ub.back() + 1);
+        return cmp(start, ub) >= 0;
+    }
+};
 
 template <class Exec> class DistIndex {
     // BMQ_TIMING=1: phase times on stderr (each lap synchronises the exec first, so the numbers include the kernels)
@@ -455,11 +479,15 @@ public:
         imp.old_kpool = old.kpool;
         return true;
     }
-    bool import_apply(uint32_t& n_live) {
+    // sized = false: the batch of a bmq_routes_import -- keys of ANOTHER index, so tenants may be unknown and regions may grow; res counts
+    // what the puts did (keys this index already held: dups).  Behind set_import_boundary the chunk's references go through the boundary
+    // predicate first (on the device: k_b_boundary): a key outside is a dead id to everything below.
+    bool import_apply(uint32_t& n_live, bool sized = true, ApplyResult* res = nullptr) {
         n_live = 0;
         const uint32_t n = imp.n;
         if (n == 0) return true;
         imp.n = 0;
+        if (imp_bounded && !x.boundary_filter(g_refs, n, imp.old_kpool, imp_bnd.kb, imp_bnd.ctr())) return xfail();
         std::vector<unsigned long long> refs(n);
         if (!x.copy_out(refs.data(), g_refs, sizeof(unsigned long long) * (size_t)n)) return xfail();
         std::vector<uint64_t> offs((size_t)n + 1, 0);
@@ -478,7 +506,42 @@ public:
         if (!x.copy_in_async(g_offs, offs.data(), sizeof(uint64_t) * ((size_t)n + 1)) || !x.gather_bytes(m, g_refs, g_offs, n, g_bytes) || !x.sync()) return xfail();
         n_live = (uint32_t)live_off.size() - 1;
         const std::vector<uint8_t> puts(n_live, 0);
-        return apply_begin(g_bytes, live_off.data(), puts.data(), n_live, true) && apply_end(nullptr);
+        return apply_begin(g_bytes, live_off.data(), puts.data(), n_live, sized) && apply_end(res);
+    }
+    // The generation being built takes only the keys inside `b` from here on (bmq_compact_begin_in); bmq_routes_import sets it per call.
+    bool set_import_boundary(const Boundary& b) {
+        if (b.bounded() && !built && !reset_empty()) return false; // (an index that never held a route: its first reset drops every buffer)
+        imp_bounded = b.bounded();
+        return !imp_bounded || stage_boundary(imp_bnd, b);
+    }
+    // bmq_routes_import: `snap` holds n key references of ANOTHER index of the same executor kind (a copy in exec memory), src_kpool its
+    // key pool (kept readable by that index's defer_release).  The live keys inside the import boundary go through the ordinary apply path.
+    bool import_refs(const unsigned long long* snap, uint32_t n, const uint8_t* src_kpool, ApplyResult& res) {
+        error.clear();
+        imp = Import{};
+        if (n == 0) return true;
+        if (!built && !reset_empty()) return false; // (before the chunk is staged: the first reset of an index drops every buffer)
+        if (!ensure_buf(g_refs, g_refs_cap, n)) return false;
+        if (!x.copy(g_refs, snap, sizeof(unsigned long long) * (size_t)n)) return xfail();
+        imp.n = n;
+        imp.old_kpool = src_kpool;
+        uint32_t n_live = 0;
+        return import_apply(n_live, false, &res);
+    }
+    // live routes inside `b` and the sum of their key lengths (reader.size(boundary), DW/hinter/FanoutSplitHinter.java:175-178): one pass
+    // of the predicate over a scratch copy of kref[0, next_id); the index is not changed
+    bool count_in(const Boundary& b, uint64_t& routes, uint64_t& bytes) {
+        error.clear();
+        routes = bytes = 0;
+        if (!built || next_id == 0) return true;
+        if (!ensure_buf(g_refs, g_refs_cap, next_id) || !stage_boundary(q_bnd, b)) return false;
+        unsigned long long c[2] = {0, 0};
+        if (!x.copy(g_refs, kref, sizeof(unsigned long long) * (size_t)next_id) || !x.boundary_filter(g_refs, next_id, kpool, q_bnd.kb, q_bnd.ctr()) ||
+            !x.copy_out(c, q_bnd.ctr(), sizeof(c)))
+            return xfail();
+        routes = c[0];
+        bytes = c[1];
+        return true;
     }
     // The buffers a chunk of `n` ids / `bytes` key bytes of a generation change goes through, taken NOW: the first bmq_compact_poll used to
     // allocate them -- a dozen device allocations beside a saturated matcher, the one batch of a compaction that took 10 ms instead of 0.35.
@@ -497,16 +560,28 @@ public:
     // Room for everything a generation change is about to hand over, taken once: every tenant of `old` that has routes gets its region at
     // the size its trie had there (dead nodes included: an upper bound), the trie pool, the dictionary, the id-list pool, the key store
     // and the id tables likewise.  The batches that carry the keys over then meet no unknown tenant and grow nothing.
-    bool reserve_like(DistIndex& old) {
+    // bound: the next generation keeps the keys inside it only (bmq_compact_begin_in).  A tenant whose key prefix `00 | u16be(len) | tenant`
+    // lies wholly outside gets no region and no directory entry; the key store and the id tables take what is inside.
+    bool reserve_like(DistIndex& old, const Boundary* bound = nullptr) {
         error.clear();
         if (!built && !reset_empty()) return false;
         if (!old.built) return true;
         if (!old.read_counters()) return fail(old.x.err);
+        const bool bounded = bound && bound->bounded();
+        uint64_t in_routes = 0, in_bytes = 0;
+        if (bounded && !old.count_in(*bound, in_routes, in_bytes)) return fail(old.error);
+        auto leaves = [&](const TenantSlot& t) {
+            if (!bounded) return false;
+            std::string prefix(3, '\0');
+            prefix[1] = (char)(t.name_len >> 8), prefix[2] = (char)(t.name_len & 0xFF);
+            prefix.append((const char*)old.names_h.data() + t.name_off, t.name_len);
+            return bound->excludes_prefix(prefix);
+        };
         std::vector<TenantSlot> d(old.dir_slots);
         if (old.dir_slots && !old.x.copy_out(d.data(), old.dir, sizeof(TenantSlot) * (size_t)old.dir_slots)) return fail(old.x.err);
         uint64_t slots = 0, n_ten = 0;
         for (auto& t : d)
-            if ((t.hash_lo | t.hash_hi) && t.n_routes) slots += 2ull * buckets_for((uint64_t)t.n_nodes + 1), n_ten++;
+            if ((t.hash_lo | t.hash_hi) && t.n_routes && !leaves(t)) slots += 2ull * buckets_for((uint64_t)t.n_nodes + 1), n_ten++;
         if (trie_used + slots > trie_cap) {
             if (trie_used + slots >= 0xFFFFFFF0ull) return fail("trie too large (2^32 slots)");
             const uint64_t cap = std::min<uint64_t>(trie_used + slots + (tiny ? 0 : slots / 8 + (1u << 16)), 0xFFFFFFF0ull);
@@ -516,13 +591,15 @@ public:
         }
         if (!ensure_directory(tenant_slot.size() + n_ten)) return false;
         for (auto& t : d)
-            if ((t.hash_lo | t.hash_hi) && t.n_routes &&
+            if ((t.hash_lo | t.hash_hi) && t.n_routes && !leaves(t) &&
                 !create_tenant(std::string((const char*)old.names_h.data() + t.name_off, t.name_len), (uint64_t)t.n_nodes + 1, 0))
                 return false;
         if (!flush_directory()) return false;
         if (old.dict_slots > dict_slots && !grow_dict(old.dict_slots, old.dpool_cap)) return false;
         if (!grow_route_pos(old.hbc.rp_used + 1024)) return false; // (lists are handed out in blocks: the old pool's size, not the live words)
-        return ensure_keys(old.kpool_used) && ensure_ids(std::min<uint64_t>((uint64_t)next_id + old.next_id + 64, 0xFFFFFFF0ull));
+        // (bounded: every chunk of the carry-over pads its keys to 16 bytes, a chunk may be one key; what the log replays grows the store)
+        const uint64_t key_room = bounded ? std::min<uint64_t>(old.kpool_used, in_bytes + 16 * in_routes + 16) : old.kpool_used;
+        return ensure_keys(key_room) && ensure_ids(std::min<uint64_t>((uint64_t)next_id + (bounded ? in_routes : old.next_id) + 64, 0xFFFFFFF0ull));
     }
     // exact lookup (inspection only -- never used for matching): ids stored under (tenant, MQTT filter)
     bool find(std::string_view tenant, std::string_view filter, std::vector<uint32_t>& ids) {
@@ -584,7 +661,9 @@ public:
         rel(trie); rel(dir); rel(names); rel(dict); rel(dpool); rel(route_pos); rel(kref); rel(khash); rel(kpool); rel(bc);
         rel(s_key_off); rel(s_op); rel(s_put_rank); rel(s_dir_slot); rel(s_nn); rel(s_flag); rel(s_target); rel(s_order);
         rel(s_sorted_target); rel(s_group_done); rel(s_unknown); rel(s_grow); rel(s_bt_first); rel(s_bt_nodes); rel(s_bt_keys); rel(s_bt_dir);
-        rel(g_ids); rel(g_refs); rel(g_offs); rel(g_bytes);
+        rel(g_ids); rel(g_refs); rel(g_offs); rel(g_bytes); rel(q_bnd.buf); rel(imp_bnd.buf);
+        q_bnd = imp_bnd = StagedBoundary{};
+        imp_bounded = false;
         trie_cap = trie_used = 0; dir_slots = 0; names_cap = names_used = 0; dict_slots = 0; dpool_cap = 0; rp_cap = 0; id_cap = next_id = 0;
         kpool_cap = kpool_used = 0; s_cap = 0; s_bt_cap = 0; s_grow_cap = 0; g_ids_cap = g_refs_cap = g_offs_cap = g_bytes_cap = 0;
         tenant_slot.clear(); free_regions.clear(); dir_h.clear(); names_h.clear(); trie_garbage = 0;
@@ -603,6 +682,28 @@ private:
     uint64_t* g_offs = nullptr;
     uint8_t* g_bytes = nullptr;
     size_t g_ids_cap = 0, g_refs_cap = 0, g_offs_cap = 0, g_bytes_cap = 0;
+    // a boundary in exec memory: [inside keys, their bytes: two 64-bit counters][start key][end key]
+    struct StagedBoundary {
+        uint8_t* buf = nullptr;
+        size_t cap = 0;
+        KeyBoundary kb{};
+        unsigned long long* ctr() const { return reinterpret_cast<unsigned long long*>(buf); }
+    } q_bnd, imp_bnd; // of count_in / of the import path: a count between two chunks of an import must not replace the import's
+    bool imp_bounded = false;
+    bool stage_boundary(StagedBoundary& s, const Boundary& b) { // (counters zeroed)
+        const size_t need = 16 + b.start.size() + b.end.size();
+        if (!ensure_buf(s.buf, s.cap, need)) return false;
+        std::vector<uint8_t> h(need, 0);
+        if (!b.start.empty()) memcpy(h.data() + 16, b.start.data(), b.start.size());
+        if (!b.end.empty()) memcpy(h.data() + 16 + b.start.size(), b.end.data(), b.end.size());
+        if (!x.copy_in(s.buf, h.data(), need)) return xfail();
+        s.kb.start = s.buf + 16;
+        s.kb.end = s.buf + 16 + b.start.size();
+        s.kb.start_len = (uint32_t)b.start.size();
+        s.kb.end_len = (uint32_t)b.end.size();
+        s.kb.flags = b.flags & 3u;
+        return true;
+    }
     // host mirror of the directory (placement only; live counters stay on the exec side) and of the tenant names
     std::vector<TenantSlot> dir_h;
     std::vector<uint8_t> names_h;

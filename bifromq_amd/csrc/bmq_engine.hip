@@ -18,6 +18,7 @@
 #include <string>
 #include <string_view>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/bmq.h"
@@ -229,6 +230,7 @@ struct bmq_engine {
         std::unique_ptr<DistIndex<HostExec>> next_h; // or (host-only engine) in host memory, like the serving one
         uint32_t cursor = 0, n_ids = 0; // ids of the serving generation handed over so far / to hand over
         uint64_t carried = 0;           // live keys handed over
+        Boundary bound;                 // bmq_compact_begin_in: the next generation keeps the keys inside it (flags 0: all of them)
         std::vector<uint8_t> log_keys;  // what was mutated meanwhile: replayed into `next` before the swap
         std::vector<uint32_t> log_off{0};
         std::vector<uint8_t> log_op;
@@ -242,6 +244,9 @@ struct bmq_engine {
     std::mutex cmp_mu;                // one compaction call at a time (taken BEFORE mu)
     hipStream_t s_build = nullptr;    // the stream the next generation is built on: lowest priority, beside the match batches
     hipEvent_t ev_serving = nullptr;  // "what the serving generation was told so far": the build stream waits for it before a snapshot
+    bool lending = false;    // bmq_routes_import reads this engine's key pool (src): its index keeps the blocks it outgrows (defer_release has one
+                             // owner), bmq_rebuild / bmq_compact / bmq_compact_begin[_in] and a second import from it are refused meanwhile
+    hipEvent_t ev_lend = nullptr; // ... "what this engine was told so far": the importing engine's stream waits for it before the snapshot
     bool apply_open = false; // bmq_routes_apply_async: the batch's outcome has not been fetched yet (complete_apply)
     // the persistent matcher of the batching front (bmq_poll_kernel.h, bmq_poller.inc)
     struct Poller {
@@ -911,6 +916,7 @@ void bmq_engine_destroy(bmq_engine* e) {
         e->cmp = bmq_engine::Compaction{}; // (a generation left half-built)
         if (e->s_build) (void)hipStreamDestroy(e->s_build);
         if (e->ev_serving) (void)hipEventDestroy(e->ev_serving);
+        if (e->ev_lend) (void)hipEventDestroy(e->ev_lend);
         if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
         if (e->ev_join) (void)hipEventDestroy(e->ev_join);
         e->dfo.reset();
@@ -934,6 +940,7 @@ int bmq_rebuild(bmq_engine* e, const uint8_t* keys, const uint32_t* key_off, uin
     std::lock_guard<std::mutex> g(e->mu);
     if (int rc_open = complete_apply(e)) return rc_open; // (a batch handed over with bmq_routes_apply_async first)
     if (e->cmp.active) return set_err(e, BMQ_E_STATE, "a compaction is running: bmq_compact_swap or bmq_compact_abort first");
+    if (e->lending) return set_err(e, BMQ_E_STATE, "a bmq_routes_import reads this engine's keys: wait for it to return");
     if (e->cur->pending) return set_err(e, BMQ_E_STATE, "a batch is in flight: call bmq_match_finish first");
     if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
     poller_stop_locked(e); // (the persistent matcher reads the index: it leaves before the index changes)
@@ -958,6 +965,7 @@ int bmq_compact(bmq_engine* e) {
     std::lock_guard<std::mutex> g(e->mu);
     if (int rc_open = complete_apply(e)) return rc_open; // (a batch handed over with bmq_routes_apply_async first)
     if (e->cmp.active) return set_err(e, BMQ_E_STATE, "a compaction is running: bmq_compact_swap or bmq_compact_abort first");
+    if (e->lending) return set_err(e, BMQ_E_STATE, "a bmq_routes_import reads this engine's keys: wait for it to return");
     for (auto& sl : e->slots)
         if (sl.pending) return set_err(e, BMQ_E_STATE, "a batch is in flight: finish / wait for it first");
     if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
@@ -1042,15 +1050,29 @@ static int replay_log(bmq_engine* e, size_t from) {
     }
     return BMQ_OK;
 }
-int bmq_compact_begin(bmq_engine* e) {
+// flags / start / end of the boundary arguments -> b; false: a present key without bytes behind it, unknown flag bits, or start >= end
+static bool parse_boundary(uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len, Boundary& b) {
+    if ((flags & ~3u) || ((flags & 1u) && start_len && !start) || ((flags & 2u) && end_len && !end)) return false;
+    b = Boundary{};
+    b.flags = flags;
+    if ((flags & 1u) && start_len) b.start.assign((const char*)start, start_len);
+    if ((flags & 2u) && end_len) b.end.assign((const char*)end, end_len);
+    return b.valid();
+}
+int bmq_compact_begin(bmq_engine* e) { return bmq_compact_begin_in(e, 0, nullptr, 0, nullptr, 0); }
+int bmq_compact_begin_in(bmq_engine* e, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len) {
     if (!e) return BMQ_E_INVAL;
     std::lock_guard<std::recursive_mutex> api_lock(e->api);
     std::lock_guard<std::mutex> gc(e->cmp_mu);
     std::lock_guard<std::mutex> g(e->mu);
+    Boundary bound;
+    if (!parse_boundary(flags, start, start_len, end, end_len, bound)) return set_err(e, BMQ_E_INVAL, "malformed boundary (start >= end, or a present key without bytes)");
     if (int rc = complete_apply(e)) return rc;
     if (e->cmp.active) return set_err(e, BMQ_E_STATE, "a compaction is running: bmq_compact_swap or bmq_compact_abort first");
+    if (e->lending) return set_err(e, BMQ_E_STATE, "a bmq_routes_import reads this engine's keys: wait for it to return");
     if (!e->built) return set_err(e, BMQ_E_STATE, "no index");
     e->cmp = bmq_engine::Compaction{};
+    e->cmp.bound = bound;
     if (e->dix) {
         HIPCHK(e, hipSetDevice(e->device));
         if (!e->s_build) {
@@ -1077,7 +1099,7 @@ int bmq_compact_begin(bmq_engine* e) {
     std::string msg;
     if (!with_generations(e, [&](auto& cur, auto& next) {
             e->cmp.n_ids = cur.id_bound();
-            const bool r = next.reserve_like(cur) && next.reserve_import(65536, 65536ull * 192); // regions, pools and tables at their final size, the chunk buffers too: the carry-over allocates nothing (chunks of up to 65536 ids)
+            const bool r = next.reserve_like(cur, &e->cmp.bound) && next.set_import_boundary(e->cmp.bound) && next.reserve_import(65536, 65536ull * 192); // regions, pools and tables at their final size, the chunk buffers too: the carry-over allocates nothing (chunks of up to 65536 ids)
             if (!r) msg = next.error;
             cur.defer_release = r; // what the serving generation outgrows meanwhile stays readable for the builder
             return r;
@@ -1144,6 +1166,20 @@ int bmq_compact_swap(bmq_engine* e, uint64_t* out_carried, uint64_t* out_replaye
         if (sl.pending) return set_err(e, BMQ_E_STATE, "a batch is in flight: finish / wait for it first");
     if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
     poller_stop_locked(e); // (the generations change places below)
+    if (c.bound.bounded()) { // ops on keys outside the boundary are dropped: the range does not own them any more (a host compare per logged key)
+        size_t w = 0;
+        uint32_t wb = 0;
+        for (size_t i = 0; i < c.log_op.size(); i++) {
+            const uint32_t lo = c.log_off[i], len = c.log_off[i + 1] - lo;
+            if (!c.bound.contains(std::string_view((const char*)c.log_keys.data() + lo, len))) continue;
+            if (wb != lo) memmove(c.log_keys.data() + wb, c.log_keys.data() + lo, len);
+            c.log_op[w] = c.log_op[i];
+            c.log_off[w] = wb;
+            wb += len, w++;
+        }
+        c.log_off[w] = wb;
+        c.log_off.resize(w + 1), c.log_op.resize(w), c.log_keys.resize(wb);
+    }
     if (int rc = replay_log(e, 0)) return rc; // what the serving generation was told since bmq_compact_begin, in order
     {
         std::string msg; // the tail records of the new generation (bulk loads form them in rebuild; the carry-over came through the apply path)
@@ -1164,6 +1200,7 @@ int bmq_compact_swap(bmq_engine* e, uint64_t* out_carried, uint64_t* out_replaye
     if (out_replayed) *out_replayed = c.log_op.size();
     with_generations(e, [&](auto& cur, auto& next) {
         next.generation = cur.generation + 1; // route ids of the two generations are unrelated
+        (void)next.set_import_boundary(Boundary{}); // (a serving generation: nothing is carried into it any more)
         return true;
     });
     e->dfo.reset(); // (the fan-out grouping state belongs to the index it was built over)
@@ -1192,6 +1229,159 @@ int bmq_compact_abort(bmq_engine* e) {
     }
     e->cmp = bmq_engine::Compaction{};
     return BMQ_OK;
+}
+
+int bmq_routes_count_in(const bmq_engine* ce, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len,
+                        uint64_t* out_routes, uint64_t* out_key_bytes) {
+    bmq_engine* e = const_cast<bmq_engine*>(ce);
+    if (!e) return BMQ_E_INVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    Boundary bound;
+    if (!parse_boundary(flags, start, start_len, end, end_len, bound)) return set_err(e, BMQ_E_INVAL, "malformed boundary (start >= end, or a present key without bytes)");
+    if (int rc_open = complete_apply(e)) return rc_open; // (a batch handed over with bmq_routes_apply_async first)
+    if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
+    uint64_t routes = 0, bytes = 0;
+    const bool ok = with_index(e, [&](auto& ix) {
+        const bool r = ix.count_in(bound, routes, bytes);
+        if (!r) e->err = ix.error;
+        return r;
+    });
+    if (!ok) return index_error(e, e->err, false);
+    if (out_routes) *out_routes = routes;
+    if (out_key_bytes) *out_key_bytes = bytes;
+    return BMQ_OK;
+}
+
+// ---- bmq_routes_import: the live keys of `src` inside a boundary into `dst`, without a KV scan ---------------------------------------
+// Locks: dst->api for the whole call (every mutator of dst takes it first), then ONE engine lock at a time -- dst->mu to check, src->mu for
+// the snapshot, dst->mu per chunk, src->mu to give the blocks back.  No thread ever waits for one engine's lock holding the other's, so two
+// imports in opposite directions cannot deadlock.  (The source of an import is refused as a destination; two that pass that check at the
+// same moment both run -- each engine lends and imports at once, which defer_release makes safe: an engine that lends frees nothing.)
+extern "C++" {
+template <class X> static std::unique_ptr<DistIndex<X>>& index_of(bmq_engine* e) {
+    if constexpr (std::is_same<X, DevExec>::value) return e->dix;
+    else return e->hix;
+}
+template <class X> static int routes_import_run(bmq_engine* dst, bmq_engine* src, const Boundary& bound, uint64_t* out_imported, uint64_t* out_dups) {
+    constexpr bool dev = std::is_same<X, DevExec>::value;
+    constexpr uint32_t CHUNK = 65536;
+    {
+        std::lock_guard<std::mutex> g(dst->mu);
+        if (int rc = complete_apply(dst)) return rc;
+        if (dst->cmp.active) return set_err(dst, BMQ_E_STATE, "a compaction is running: bmq_compact_swap or bmq_compact_abort first");
+        if (dst->lending) return set_err(dst, BMQ_E_STATE, "a bmq_routes_import reads this engine's keys: wait for it to return");
+        if (dst->cur->pending) return set_err(dst, BMQ_E_STATE, "a batch is in flight: call bmq_match_finish first");
+    }
+    X& dx = index_of<X>(dst)->x; // (dst's serving generation cannot change under dst->api)
+    unsigned long long* snap = nullptr;
+    uint32_t n_ids = 0;
+    const uint8_t* src_kpool = nullptr;
+    int src_rc = BMQ_OK; // (dst's error string is written under dst's lock, below)
+    std::string src_msg;
+    {
+        // src is held for this block only: its key references kref[0, next_id) are copied (enqueued on dst's stream, behind what src was told
+        // so far) and its index starts keeping the blocks it outgrows.  It matches and mutates meanwhile; a key mutated during the call is
+        // imported as it was at the snapshot.
+        std::lock_guard<std::mutex> g(src->mu);
+        auto hip_ok = [&](hipError_t err, const char* what) {
+            if (err != hipSuccess) src_rc = BMQ_E_HIP, src_msg = std::string(what) + ": " + hipGetErrorString(err);
+            return err == hipSuccess;
+        };
+        if ((src_rc = complete_apply(src)) != BMQ_OK) src_msg = "source engine: " + src->err;
+        else if (src->cmp.active || src->lending) src_rc = BMQ_E_STATE, src_msg = "source engine: a compaction or another import holds its key pool";
+        auto& s = *index_of<X>(src);
+        n_ids = src_rc == BMQ_OK && s.built ? s.id_bound() : 0;
+        bool ok = n_ids != 0;
+        if constexpr (dev) {
+            ok = ok && hip_ok(hipSetDevice(dst->device), "hipSetDevice") &&
+                 (src->ev_lend || hip_ok(hipEventCreateWithFlags(&src->ev_lend, hipEventDisableTiming), "hipEventCreateWithFlags")) &&
+                 hip_ok(hipEventRecord(src->ev_lend, src->stream), "hipEventRecord") &&
+                 hip_ok(hipStreamWaitEvent(dst->stream, src->ev_lend, 0), "hipStreamWaitEvent");
+        }
+        if (ok) {
+            snap = (unsigned long long*)dx.alloc(sizeof(unsigned long long) * (size_t)n_ids);
+            if (!snap) src_rc = BMQ_E_NOMEM, src_msg = "out of memory (import snapshot)";
+            else if (!dx.copy(snap, s.kref, sizeof(unsigned long long) * (size_t)n_ids)) {
+                src_rc = BMQ_E_HIP, src_msg = dx.err;
+                (void)dx.sync();
+                dx.release(snap);
+                snap = nullptr;
+            } else {
+                src_kpool = s.kpool;
+                s.defer_release = true;
+                src->lending = true;
+            }
+        }
+    }
+    if (src_rc != BMQ_OK) {
+        std::lock_guard<std::mutex> g(dst->mu);
+        return set_err(dst, src_rc, src_msg);
+    }
+    if (out_imported) *out_imported = 0;
+    if (out_dups) *out_dups = 0;
+    if (n_ids == 0) return BMQ_OK;
+    int rc = BMQ_OK;
+    uint64_t imported = 0, dups = 0;
+    for (uint32_t lo = 0; lo < n_ids && rc == BMQ_OK; lo += std::min(CHUNK, n_ids - lo)) {
+        const uint32_t n = std::min(CHUNK, n_ids - lo);
+        std::lock_guard<std::mutex> g(dst->mu); // (released between the chunks: dst's matchers get their turn)
+        if (dst->cur->pending) {
+            rc = set_err(dst, BMQ_E_STATE, "a batch is in flight: call bmq_match_finish first");
+            break;
+        }
+        if constexpr (dev) {
+            if (hipSetDevice(dst->device) != hipSuccess) {
+                rc = set_err(dst, BMQ_E_HIP, "hipSetDevice failed");
+                break;
+            }
+        }
+        poller_stop_locked(dst); // (a mutation: the persistent matcher leaves before the builder kernels are enqueued)
+        auto& d = *index_of<X>(dst);
+        ApplyResult res;
+        if ((lo == 0 && !d.set_import_boundary(bound)) || !d.import_refs(snap + lo, n, src_kpool, res)) rc = index_error(dst, d.error, false);
+        imported += res.added;
+        dups += res.dups;
+        if (rc == BMQ_OK) {
+            dst->epoch++;
+            dst->built = true;
+        }
+    }
+    // src gets its blocks back on every path: nothing of dst's reads them any more once dst's stream is idle
+    {
+        std::lock_guard<std::mutex> g(dst->mu);
+        (void)dx.sync();
+        dx.release(snap);
+        (void)index_of<X>(dst)->set_import_boundary(Boundary{});
+    }
+    {
+        std::lock_guard<std::mutex> g(src->mu);
+        if constexpr (dev) {
+            (void)hipSetDevice(src->device);
+            (void)hipStreamSynchronize(src->stream);
+        }
+        auto& s = *index_of<X>(src);
+        s.defer_release = false;
+        s.release_deferred();
+        src->lending = false;
+    }
+    if (out_imported) *out_imported = imported;
+    if (out_dups) *out_dups = dups;
+    return rc;
+}
+} // extern "C++"
+int bmq_routes_import(bmq_engine* dst, bmq_engine* src, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end,
+                      uint32_t end_len, uint64_t* out_imported, uint64_t* out_dups) {
+    if (!dst || !src) return BMQ_E_INVAL;
+    std::lock_guard<std::recursive_mutex> api_lock(dst->api);
+    Boundary bound;
+    std::unique_lock<std::mutex> g(dst->mu); // (for the error string; released before the import takes its locks one by one)
+    if (dst == src) return set_err(dst, BMQ_E_INVAL, "bmq_routes_import: source and destination are the same engine");
+    if (!parse_boundary(flags, start, start_len, end, end_len, bound)) return set_err(dst, BMQ_E_INVAL, "malformed boundary (start >= end, or a present key without bytes)");
+    if ((dst->device >= 0) != (src->device >= 0)) return set_err(dst, BMQ_E_INVAL, "bmq_routes_import: a host-executor engine and a device engine");
+    if (dst->device != src->device) return set_err(dst, BMQ_E_INVAL, "bmq_routes_import: the engines live on different devices");
+    g.unlock();
+    return dst->device >= 0 ? routes_import_run<DevExec>(dst, src, bound, out_imported, out_dups)
+                            : routes_import_run<HostExec>(dst, src, bound, out_imported, out_dups);
 }
 
 int bmq_index_info_get(const bmq_engine* ce, bmq_index_info* out) {

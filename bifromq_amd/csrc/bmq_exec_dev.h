@@ -98,6 +98,43 @@ __global__ __launch_bounds__(BK) void k_b_gather_bytes(DistIndexMut ix, const un
     if (i < n) gather_bytes_one(ix, refs, offs, i, out);
 }
 
+// The boundary predicate over a chunk of key references (key_in_boundary, bmq_build_core.h): one lane per reference.  References outside
+// lose their length bits in place; the chunk's inside keys and their bytes are added to ctr[0] / ctr[1].
+//   - The boundary is uniform for the launch: the first BND_LDS bytes of each present key are staged in LDS once per workgroup, so a
+//     lane's compare reads the boundary from LDS (every active lane of a wave is at the same step: a broadcast), never from global memory.
+//     A longer boundary key is read where it lies (a uniform address too; no route key of the reference's schema needs it).
+//   - Ids are handed out in append order of the key pool, so the 64 keys of a wave are neighbours there: their first words share lines.
+//   - Counters: ballot + popcount for the keys, a cross-lane sum for the bytes, then ONE atomic per wave and counter -- and at most
+//     4 * BND_BLOCKS waves per launch, so a 10 M-id pass adds 16 k times to the two words, not 313 k times (one hot word serialises in
+//     the L2 atomic unit: bmq_build_core.h, N_CTR_LANES).
+constexpr uint32_t BND_LDS = 256;
+constexpr uint32_t BND_BLOCKS = 2048; // 256 CUs x 8 workgroups of 256 lanes
+__global__ __launch_bounds__(256) void k_b_boundary(unsigned long long* refs, uint32_t n, const uint8_t* kpool, KeyBoundary b, unsigned long long* ctr) {
+    __shared__ uint8_t s_key[2][BND_LDS];
+    if ((b.flags & 1u) && b.start_len <= BND_LDS) {
+        for (uint32_t p = threadIdx.x; p < b.start_len; p += 256) s_key[0][p] = b.start[p];
+    }
+    if ((b.flags & 2u) && b.end_len <= BND_LDS) {
+        for (uint32_t p = threadIdx.x; p < b.end_len; p += 256) s_key[1][p] = b.end[p];
+    }
+    __syncthreads();
+    if ((b.flags & 1u) && b.start_len <= BND_LDS) b.start = s_key[0];
+    if ((b.flags & 2u) && b.end_len <= BND_LDS) b.end = s_key[1];
+    // a bounded grid that strides over the chunk (BND_BLOCKS workgroups at most): a wave keeps its sums in registers and adds them once
+    unsigned long long keys = 0, bytes = 0; // keys: the wave's (the same in every lane); bytes: this lane's until the cross-lane sum
+    for (unsigned long long base = (unsigned long long)blockIdx.x * 256; base < n; base += (unsigned long long)gridDim.x * 256) {
+        const unsigned long long i = base + threadIdx.x;
+        const unsigned long long len = i < n ? boundary_filter_one(kpool, refs, (uint32_t)i, b) : 0ull;
+        keys += (unsigned long long)__popcll(__ballot(len != 0));
+        bytes += len;
+    }
+    for (int d = 32; d > 0; d >>= 1) bytes += __shfl_xor(bytes, d, 64);
+    if ((threadIdx.x & 63u) == 0 && keys != 0) {
+        atomicAdd(ctr, keys);
+        atomicAdd(ctr + 1, bytes);
+    }
+}
+
 // fan-out grouping (bmq_fanout_core.h): one lane per (topic, route) pair
 __global__ __launch_bounds__(256) void k_fo_fill(DistIndexMut ix, FanoutState st, FanoutBatch b) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -371,6 +408,12 @@ struct DevExec {
     }
     bool gather_bytes(const DistIndexMut& ix, const unsigned long long* refs, const uint64_t* offs, uint32_t n, uint8_t* out) {
         hipLaunchKernelGGL(k_b_gather_bytes, grid(n, BK), dim3(BK), 0, stream, ix, refs, offs, n, out);
+        return launched();
+    }
+    // refs[0, n): references outside `b` lose their length bits; ctr[0] += keys inside, ctr[1] += their bytes (b's keys: exec memory)
+    bool boundary_filter(unsigned long long* refs, uint32_t n, const uint8_t* kpool, const KeyBoundary& b, unsigned long long* ctr) {
+        if (n == 0) return true;
+        hipLaunchKernelGGL(k_b_boundary, dim3(std::min((n + 255u) / 256u, BND_BLOCKS)), dim3(256), 0, stream, refs, n, kpool, b, ctr);
         return launched();
     }
     // ---- fan-out grouping, fast path (bmq_fanout_kernels.h): counting sort that carries its payload ----

@@ -177,6 +177,19 @@ struct HostExec {
         par(n, [&](size_t i) { gather_bytes_one(ix, refs, offs, (uint32_t)i, out); });
         return true;
     }
+    // refs[0, n): references outside `b` lose their length bits; ctr[0] += keys inside, ctr[1] += their bytes (k_b_boundary on the device)
+    bool boundary_filter(unsigned long long* refs, uint32_t n, const uint8_t* kpool, const KeyBoundary& b, unsigned long long* ctr) {
+        std::atomic<unsigned long long> keys{0}, bytes{0};
+        par(n, [&](size_t i) {
+            if (const unsigned long long len = boundary_filter_one(kpool, refs, (uint32_t)i, b)) {
+                keys.fetch_add(1, std::memory_order_relaxed);
+                bytes.fetch_add(len, std::memory_order_relaxed);
+            }
+        });
+        ctr[0] += keys.load();
+        ctr[1] += bytes.load();
+        return true;
+    }
     // ---- receivers of shared subscriptions (bmq_share.h) ----
     void mark(int) {} // (HIP-event marks of the device executor)
     float mark_ms(int, int) { return 0; }

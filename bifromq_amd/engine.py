@@ -290,10 +290,33 @@ class Engine:
         self._check(_lib.lib().bmq_compact(self.h))
         return self
 
-    def compact_begin(self):
-        """bmq_compact_begin: the next generation of the route index starts being built beside the serving one"""
-        self._check(_lib.lib().bmq_compact_begin(self.h))
+    @staticmethod
+    def _boundary(start, end):
+        """(flags, start, len, end, len) of a KV boundary: None = the side is absent, b"" = present and empty"""
+        flags = (1 if start is not None else 0) | (2 if end is not None else 0)
+        s, e = (b"" if start is None else bytes(start)), (b"" if end is None else bytes(end))
+        return flags, s, len(s), e, len(e)
+
+    def compact_begin(self, start=None, end=None):
+        """bmq_compact_begin[_in]: the next generation of the route index starts being built beside the serving one; with a boundary it
+        takes the keys with start <= key < end only (the range that shrinks in a split)"""
+        if start is None and end is None:
+            self._check(_lib.lib().bmq_compact_begin(self.h))
+        else:
+            self._check(_lib.lib().bmq_compact_begin_in(self.h, *self._boundary(start, end)))
         return self
+
+    def count_in(self, start=None, end=None) -> Tuple[int, int]:
+        """bmq_routes_count_in: (live routes inside the boundary, the sum of their key lengths); the index is not changed"""
+        routes, key_bytes = C.c_uint64(), C.c_uint64()
+        self._check(_lib.lib().bmq_routes_count_in(self.h, *self._boundary(start, end), C.byref(routes), C.byref(key_bytes)))
+        return int(routes.value), int(key_bytes.value)
+
+    def import_routes(self, src: "Engine", start=None, end=None) -> Tuple[int, int]:
+        """bmq_routes_import: every live key of src inside the boundary is put into this engine, without a KV scan -> (imported, dups)"""
+        imported, dups = C.c_uint64(), C.c_uint64()
+        self._check(_lib.lib().bmq_routes_import(self.h, src.h, *self._boundary(start, end), C.byref(imported), C.byref(dups)))
+        return int(imported.value), int(dups.value)
 
     def compact_poll(self, max_ids: int = 8192) -> int:
         """bmq_compact_poll: hands the next max_ids route ids' live keys to the builder -> progress in permille (1000: ready to swap)"""

@@ -186,6 +186,45 @@ int bmq_compact_poll(bmq_engine* e, uint32_t max_ids, uint32_t* out_done_permill
 int bmq_compact_swap(bmq_engine* e, uint64_t* out_carried /* may be NULL */, uint64_t* out_replayed /* may be NULL */);
 int bmq_compact_abort(bmq_engine* e);
 
+/* ---- split and merge by KV boundary, without a KV scan ---------------------------------------------------------------------------------
+ * IKVRangeCoProc.reset(Boundary) fires when a dist-worker range is split or merged (DW/DistWorkerCoProc.java:283-291); the reference's
+ * matcher then scans tenantBoundary ^ rangeBoundary only (DW/cache/TenantRouteMatcher.java:81-86).  bmq_rebuild answers it with a full KV
+ * scan; the three calls below answer it from the keys the engine already holds in device memory.
+ *
+ * Boundary arguments, as bmq_router_lookup_boundary takes them: flags bit 0 = a start key is present, bit 1 = an end key is present; a
+ * present key may be empty.  A key is inside iff (no start or key >= start) and (no end or key < end), unsigned lexicographic, a proper
+ * prefix first: BoundaryUtil.inRange (base-kv/.../utils/BoundaryUtil.java:241-252).  Both present with start >= end: BMQ_E_INVAL.  No
+ * start with an empty end (NULL_BOUNDARY) is valid and holds nothing.  BoundaryUtil.split (:509-533) cuts [start, end) at a key s into
+ * [start, s) and [s, end): the two halves of the recipes below.
+ *
+ *   bmq_routes_count_in    live routes inside the boundary and the sum of their key lengths: the native reader.size(boundary)
+ *                          (DW/hinter/FanoutSplitHinter.java:175-178).  One pass of the boundary kernel over a scratch copy of the key
+ *                          references; the index is not changed.  An open bmq_routes_apply_async batch is completed first.
+ *   bmq_compact_begin_in   bmq_compact_begin for a range that SHRINKS: the next generation takes the keys inside the boundary only
+ *                          (bmq_compact_begin is this call with flags = 0).  bmq_compact_poll / _swap / _abort are used as before; tenants
+ *                          that lie wholly outside get no region in the next generation, logged mutations of keys outside are not replayed.
+ *                          *out_carried of the swap counts the keys inside that were carried over, *out_replayed the ops replayed.  The
+ *                          serving generation matches and mutates over ALL its keys until the swap.  After the swap the engine does NOT
+ *                          police later mutations against the boundary: base-kv routes a mutation to the range that owns its key.
+ *   bmq_routes_import      puts every live key of src inside the boundary into dst, device memory to device memory, through dst's ordinary
+ *                          apply path (unknown tenants are created, regions grow).  Blocking; chunks of at most 65536 route ids.  Empty
+ *                          dst + [s, end) is the new sibling of a split; non-empty dst + the full boundary (flags = 0) is a merge.  It is a
+ *                          mutation of dst: ids dst handed out stay valid, its generation is unchanged, its epoch advances.  Keys dst
+ *                          already holds are counted in *out_dups and stored once; *out_imported counts the keys added.  src is locked
+ *                          only while its key references are copied; it matches and mutates meanwhile (a key mutated during the call is
+ *                          imported as the snapshot saw it).  BMQ_E_INVAL: dst == src, a host-only engine paired with a device engine, two
+ *                          devices.  BMQ_E_STATE: a compaction runs on either engine, src already lends its keys to another import, dst
+ *                          has a batch in flight.  Until the call returns bmq_rebuild / bmq_compact / bmq_compact_begin[_in] on src are
+ *                          refused with BMQ_E_STATE, and src must not be destroyed.
+ * A split of range A at key s:  bmq_routes_import(B, A, start = s)  then  bmq_compact_begin_in(A, end = s) ... bmq_compact_swap(A).
+ * A merge of B into A:          bmq_routes_import(A, B, flags = 0).
+ * Route ids cached outside the engine (bmq_route_cache) belong to a generation: bmq_route_cache_reset after a bounded swap or an import. */
+int bmq_routes_count_in(const bmq_engine* e, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len,
+                        uint64_t* out_routes /* may be NULL */, uint64_t* out_key_bytes /* may be NULL */);
+int bmq_compact_begin_in(bmq_engine* e, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len);
+int bmq_routes_import(bmq_engine* dst, bmq_engine* src, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end,
+                      uint32_t end_len, uint64_t* out_imported /* may be NULL */, uint64_t* out_dups /* may be NULL */);
+
 int bmq_index_info_get(const bmq_engine* e, bmq_index_info* out);
 /* id -> key (so the Java adapter can materialise Matching objects, SCHEMA/KVSchemaUtil.java:73-89).  BMQ_E_INVAL: no such
  * route (the id was never handed out, or its route has been deleted). */
@@ -395,7 +434,7 @@ int bmq_batcher_stats_get(bmq_batcher* b, bmq_batcher_stats* out);
  * cache miss from the matchExecutor pool (DW/cache/TenantRouteCache.java:180-193, DW/DistWorkerCoProcFactory.java:74-88) -- pays a
  * PCIe round trip per generation instead of a kernel launch and an event.  It needs no call of its own: bmq_batcher_match_all /
  * bmq_route_cache_get use it whenever it is enabled (the default on a device engine).
- *   - the index never changes under it: bmq_rebuild, bmq_routes_apply[_async], bmq_compact, bmq_compact_swap and bmq_engine_destroy stop it
+ *   - the index never changes under it: bmq_rebuild, bmq_routes_apply[_async], bmq_routes_import, bmq_compact, bmq_compact_swap and bmq_engine_destroy stop it
  *     first (it finishes the generation in hand, a few microseconds); the next generation starts it again.  The FIRST generation after a
  *     start pays the launch (~15 us); a generation whose doorbell it never saw is launched the old way by its leader;
  *   - it leaves the GPU by itself after 20 ms without a doorbell and after 2 s whatever happens;

@@ -8,8 +8,12 @@
 //     topics and compared with a brute-force application of the matching rule of SURVEY.md 8a-0 to every key of the model;
 //   * tiny initial capacities (BMQ_FUZZ_SMALL, default on) force region growth, dictionary growth, id-list pool growth,
 //     directory growth and key-store growth all the time.
+//   * every third round a random KV boundary: count_in against the model, a bounded generation change (reserve_like with the boundary,
+//     the boundary predicate on every chunk) and an import into a second index (import_refs: unknown tenants, duplicates) against the
+//     model's key set restricted to the boundary.
 // Build + run: make -C bifromq_amd/csrc fuzz   (tests/test_host.py runs short rounds)
 #include <cstdio>
+#include <algorithm>
 #include <cstdlib>
 #include <map>
 #include <random>
@@ -216,7 +220,7 @@ int main(int argc, char** argv) {
     hx.threads = threads;
     DistIndex<HostExec> h(hx);
     h.tiny = getenv("BMQ_FUZZ_BIG") == nullptr;
-    uint64_t checks = 0, n_apply = 0, n_rebuild = 0, fo_pairs = 0, n_generations = 0, plus_stat[2] = {0, 0};
+    uint64_t checks = 0, n_apply = 0, n_rebuild = 0, fo_pairs = 0, n_generations = 0, n_bounded = 0, n_imports = 0, plus_stat[2] = {0, 0};
     Fanout<HostExec> fo(hx, h); // fan-out grouping (bmq_fanout.h) over the same index, kept across rebuilds and applies
     fo.initial_table = 4;       // 36 deliverer keys: the group table grows twice
     for (int round = 0; round < rounds; round++) {
@@ -419,6 +423,125 @@ int main(int argc, char** argv) {
             }
             n_generations++;
         }
+        // ---- split and merge by KV boundary (bmq_routes_count_in, bmq_compact_begin_in, bmq_routes_import: Boundary, DistIndex::count_in,
+        // reserve_like(old, boundary), set_import_boundary, import_refs and the boundary predicate of bmq_build_core.h that k_b_boundary
+        // runs on the device).  The boundary's keys are keys of the model, prefixes of them, a tenant prefix, or absent.
+        if (h.built && rnd(3) == 0) {
+            auto rand_bound = [&]() {
+                if (model.empty() || rnd(6) == 0) return std::string(rnd(2) ? "" : "\xff\xff");
+                auto it = model.begin();
+                std::advance(it, rnd(model.size()));
+                const std::string& k = it->first;
+                switch (rnd(4)) {
+                case 0: return k;
+                case 1: return k.substr(0, rnd(k.size() + 1));
+                case 2: return k.substr(0, 3 + (((size_t)(uint8_t)k[1] << 8) | (uint8_t)k[2])); // 00 | u16be(len) | tenant
+                default: return k + std::string(1, (char)rnd(256));
+                }
+            };
+            Boundary bd;
+            bd.flags = (uint8_t)rnd(4);
+            bd.start = (bd.flags & 1) ? rand_bound() : std::string();
+            bd.end = (bd.flags & 2) ? rand_bound() : std::string();
+            if (!bd.valid()) std::swap(bd.start, bd.end);
+            if (!bd.valid()) bd.flags = 1; // (start == end)
+            std::set<std::string> inside;
+            uint64_t inside_bytes = 0;
+            for (auto& e : model)
+                if ((!(bd.flags & 1) || e.first >= bd.start) && (!(bd.flags & 2) || e.first < bd.end)) inside.insert(e.first), inside_bytes += e.first.size();
+            uint64_t cr = 0, cb = 0;
+            if (!h.count_in(bd, cr, cb) || cr != inside.size() || cb != inside_bytes) {
+                fprintf(stderr, "round %d: count_in gives %llu keys / %llu bytes, the model %zu / %llu (%s)\n", round, (unsigned long long)cr,
+                        (unsigned long long)cb, inside.size(), (unsigned long long)inside_bytes, h.error.c_str());
+                return 1;
+            }
+            auto key_set = [&](DistIndex<HostExec>& ix, std::set<std::string>& got) {
+                DistIndexStats is;
+                ix.stats(is);
+                std::vector<uint32_t> ids(is.next_id);
+                for (uint32_t i = 0; i < is.next_id; i++) ids[i] = i;
+                std::vector<uint8_t> kb;
+                std::vector<uint64_t> ko;
+                if (!ix.route_keys(ids.data(), is.next_id, kb, ko)) return false;
+                size_t live = 0;
+                for (uint32_t i = 0; i < is.next_id; i++)
+                    if (ko[i + 1] > ko[i]) got.insert(std::string((const char*)kb.data() + ko[i], ko[i + 1] - ko[i])), live++;
+                return live == got.size() && is.n_routes == live; // (no key stored twice)
+            };
+            { // the range that shrinks: a bounded generation change, chunks of random size
+                DistIndex<HostExec> g(hx);
+                g.tiny = h.tiny;
+                if (!g.reserve_like(h, &bd) || !g.set_import_boundary(bd)) {
+                    fprintf(stderr, "round %d: bounded reserve_like failed: %s\n", round, g.error.c_str());
+                    return 1;
+                }
+                h.defer_release = true;
+                const uint32_t n_ids = h.id_bound();
+                uint64_t carried = 0;
+                for (uint32_t cursor = 0; cursor < n_ids;) {
+                    const uint32_t hi = (uint32_t)std::min<uint64_t>(n_ids, (uint64_t)cursor + 1 + rnd(rnd(3) == 0 ? 2000 : 150));
+                    uint32_t n_live = 0;
+                    if (!g.import_snapshot(h, cursor, hi) || !g.import_apply(n_live)) {
+                        fprintf(stderr, "round %d: bounded generation change failed at id %u: %s\n", round, cursor, g.error.c_str());
+                        return 1;
+                    }
+                    carried += n_live;
+                    cursor = hi;
+                }
+                h.defer_release = false;
+                h.release_deferred();
+                std::set<std::string> got;
+                if (!key_set(g, got) || got != inside || carried != inside.size()) {
+                    fprintf(stderr, "round %d: the bounded generation holds %zu keys (%llu carried), the model has %zu inside\n", round, got.size(),
+                            (unsigned long long)carried, inside.size());
+                    return 1;
+                }
+                n_bounded++;
+            }
+            { // the sibling of a split / a merge: into an index that already holds some of the keys and some others
+                DistIndex<HostExec> d(hx);
+                d.tiny = h.tiny;
+                std::set<std::string> want = inside;
+                uint64_t want_dups = 0;
+                if (rnd(2)) {
+                    std::vector<std::string> pre;
+                    for (auto& e : model)
+                        if (rnd(5) == 0) pre.push_back(e.first);
+                    for (int i = 0; i < 5; i++) pre.push_back(rand_key());
+                    std::sort(pre.begin(), pre.end());
+                    pre.erase(std::unique(pre.begin(), pre.end()), pre.end());
+                    std::vector<uint8_t> pb;
+                    std::vector<uint32_t> po{0};
+                    for (auto& k : pre) {
+                        pb.insert(pb.end(), k.begin(), k.end());
+                        po.push_back((uint32_t)pb.size());
+                        want_dups += inside.count(k);
+                        want.insert(k);
+                    }
+                    pb.resize(pb.size() + 16, 0);
+                    if (!d.rebuild(pb.data(), po.data(), (uint32_t)pre.size())) return 3;
+                }
+                const uint32_t n_ids = h.id_bound();
+                std::vector<unsigned long long> snap(h.kref, h.kref + n_ids); // (the engine: a copy in exec memory, src held meanwhile)
+                h.defer_release = true;
+                ApplyResult res;
+                bool ok = d.set_import_boundary(bd);
+                for (uint32_t lo = 0; ok && lo < n_ids;) {
+                    const uint32_t n = (uint32_t)std::min<uint64_t>(n_ids - lo, 1 + rnd(rnd(3) == 0 ? 3000 : 200));
+                    ok = d.import_refs(snap.data() + lo, n, h.kpool, res);
+                    lo += n;
+                }
+                h.defer_release = false;
+                h.release_deferred();
+                std::set<std::string> got;
+                if (!ok || !key_set(d, got) || got != want || res.added != inside.size() - want_dups || res.dups != want_dups) {
+                    fprintf(stderr, "round %d: import: %s; %zu keys (want %zu), %u added %u dups (want %llu dups)\n", round, d.error.c_str(), got.size(),
+                            want.size(), res.added, res.dups, (unsigned long long)want_dups);
+                    return 1;
+                }
+                n_imports++;
+            }
+        }
         // decoded form of the model, for the brute force
         struct Dec {
             std::string tenant;
@@ -536,9 +659,9 @@ int main(int argc, char** argv) {
     DistIndexStats st;
     h.stats(st);
     printf("layout v3: %llu of the %llu nodes the checks discovered through a '+' edge below a non-root node lay beside their parent\n", (unsigned long long)plus_stat[0], (unsigned long long)plus_stat[1]);
-    printf("host_fuzz ok: seed %llu, %d rounds (%llu rebuilds, %llu applies, %llu generation changes), %llu topic checks, final %zu routes, %llu nodes, %llu tokens, "
+    printf("host_fuzz ok: seed %llu, %d rounds (%llu rebuilds, %llu applies, %llu generation changes, %llu bounded ones, %llu imports), %llu topic checks, final %zu routes, %llu nodes, %llu tokens, "
            "%llu trie slots (%llu garbage), %llu id-list words (%llu garbage), %llu fan-out pairs grouped\n",
-           (unsigned long long)seed, rounds, (unsigned long long)n_rebuild, (unsigned long long)n_apply, (unsigned long long)n_generations, (unsigned long long)checks, model.size(),
+           (unsigned long long)seed, rounds, (unsigned long long)n_rebuild, (unsigned long long)n_apply, (unsigned long long)n_generations, (unsigned long long)n_bounded, (unsigned long long)n_imports, (unsigned long long)checks, model.size(),
            (unsigned long long)st.n_nodes, (unsigned long long)st.n_tokens, (unsigned long long)st.trie_slots, (unsigned long long)st.trie_garbage_slots,
            (unsigned long long)st.id_list_words, (unsigned long long)st.id_list_garbage, (unsigned long long)fo_pairs);
     return 0;
