@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "bmq_batcher_match_all", "bmq_batcher_submit", "bmq_batcher_stats_get", "bmq_poller_stats_get", "bmq_poller_control",
     "bmq_route_cache_create", "bmq_route_cache_destroy", "bmq_route_cache_get", "bmq_route_cache_get_async", "bmq_route_cache_get_batch", "bmq_batcher_match_batch", "bmq_route_cache_is_cached", "bmq_route_cache_apply",
     "bmq_route_cache_rebuild", "bmq_route_cache_reset", "bmq_route_cache_expire", "bmq_route_cache_stats_get", "bmq_route_cache_tenant_stats_get",
-    "bmq_route_cache_set_caps", "bmq_route_cache_set_event_sink", "bmq_routes_cap", "bmq_fanout_group", "bmq_fanout_group_dev", "bmq_share_members_apply", "bmq_share_resolve", "bmq_share_resolve_dev", "bmq_share_member", "bmq_share_info_get", "bmq_router_find_by_key", "bmq_router_find_by_boundary", "bmq_retain_range_lookup", "bmq_router_create", "bmq_router_destroy", "bmq_router_lookup_key", "bmq_router_lookup_boundary", "bmq_router_retain_lookup",
+    "bmq_route_cache_set_caps", "bmq_route_cache_set_event_sink", "bmq_routes_cap", "bmq_fanout_group", "bmq_fanout_group_dev", "bmq_fanout_info_get", "bmq_share_members_apply", "bmq_share_resolve", "bmq_share_resolve_dev", "bmq_share_member", "bmq_share_info_get", "bmq_router_find_by_key", "bmq_router_find_by_boundary", "bmq_retain_range_lookup", "bmq_router_create", "bmq_router_destroy", "bmq_router_lookup_key", "bmq_router_lookup_boundary", "bmq_router_retain_lookup",
 ]
 
 
@@ -99,6 +99,11 @@ class ShareInfo(C.Structure):
     _fields_ = [("n_tables", C.c_uint64), ("n_members", C.c_uint64), ("n_deliverers", C.c_uint64), ("device_bytes", C.c_uint64),
                 ("generation", C.c_uint64), ("ms_count", C.c_float), ("ms_rows", C.c_float), ("ms_resolve", C.c_float), ("ms_sort", C.c_float),
                 ("ms_group", C.c_float), ("reserved0", C.c_uint32)]
+
+
+class FanoutInfo(C.Structure):
+    _fields_ = [("n_fast_calls", C.c_uint64), ("n_generic_calls", C.c_uint64), ("n_refill_calls", C.c_uint64), ("n_table_grows", C.c_uint64),
+                ("n_table_reseeds", C.c_uint64), ("n_keys", C.c_uint64), ("table_slots", C.c_uint64), ("generation", C.c_uint64)]
 
 
 class RangesInfo(C.Structure):
@@ -220,6 +225,7 @@ def lib() -> C.CDLL:
             "bmq_routes_cap": (C.c_int, [vp, vp, vp, u32, i32, i32, vp, vp, vp, vp, u32, P(u32)]),
             "bmq_fanout_group": (C.c_int, [vp, vp, vp, u32, vp, vp, u64, vp, vp, u32, P(u32), P(u32)]),
             "bmq_fanout_group_dev": (C.c_int, [vp, vp, vp, u32, u64, vp, vp, vp, vp, u32, P(u32), P(u32)]),
+            "bmq_fanout_info_get": (C.c_int, [vp, P(FanoutInfo)]),
             "bmq_share_members_apply": (C.c_int, [vp, vp, u32, vp, vp, vp]),
             "bmq_share_resolve": (C.c_int, [vp, vp, vp, u32, vp, vp, u32, u64, vp, vp, vp, u32, vp, u32, P(u32), P(u32), P(u32)]),
             "bmq_share_resolve_dev": (C.c_int, [vp, vp, vp, u32, vp, vp, u32, u32, u64, vp, vp, vp, u32, vp, u32, P(u32), P(u32), P(u32)]),

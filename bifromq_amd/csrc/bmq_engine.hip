@@ -927,6 +927,7 @@ void bmq_engine_destroy(bmq_engine* e) {
         e->dx.tmp = nullptr;
         if (e->stream) (void)hipStreamDestroy(e->stream);
     }
+    e->hfo.reset(); // (before the index it refers to)
     delete e;
 }
 
@@ -1203,7 +1204,8 @@ int bmq_compact_swap(bmq_engine* e, uint64_t* out_carried, uint64_t* out_replaye
         (void)next.set_import_boundary(Boundary{}); // (a serving generation: nothing is carried into it any more)
         return true;
     });
-    e->dfo.reset(); // (the fan-out grouping state belongs to the index it was built over)
+    e->dfo.reset(); // (the fan-out grouping state belongs to the index it was built over: it holds a reference to it)
+    e->hfo.reset();
     if (e->dix) e->dix.swap(c.next_d);
     else e->hix.swap(c.next_h);
     e->cmp = bmq_engine::Compaction{}; // frees the old generation (and the blocks it outgrew meanwhile)

@@ -17,6 +17,16 @@ struct FanoutResult {
     bool group_overflow = false;
 };
 
+// What bmq_fanout_info_get reports: plain host-side counts of the control below (no kernel knows of them).  They belong to the grouping
+// state and start again at 0 whenever that state is rebuilt for another generation of the index.
+struct FanoutCounters {
+    uint64_t n_fast = 0;     // calls answered by the counting-sort fast path (bmq_fanout_kernels.h)
+    uint64_t n_generic = 0;  // calls answered by the generic radix-sort passes
+    uint64_t n_refill = 0;   // calls of the fast path that found route ids without a group slot and ran the mapping passes first
+    uint64_t n_grow = 0;     // group-table resets into a larger table
+    uint64_t n_reseed = 0;   // group-table resets after a 64-bit hash collision (same size, new seed)
+};
+
 template <class Exec> class Fanout {
 public:
     Fanout(Exec& exec, DistIndex<Exec>& index) : x(exec), ix(index) {}
@@ -26,6 +36,10 @@ public:
 
     std::string error;
     uint32_t initial_table = 1024; // tests shrink it to force growth
+    FanoutCounters ctr;
+    uint32_t keys_mapped() const { return used_slots; }
+    uint32_t table_slots() const { return st.gt_cap; }
+    uint64_t state_generation() const { return generation; } // ~0: no state yet
 
     // All pointers are exec memory.  row_ptr[n_topics + 1] with row_ptr[n_topics] == total; out_topic / out_route [total];
     // group_off [group_cap + 1], group_rep [group_cap].
@@ -41,6 +55,7 @@ public:
         if (!ensure_state() || !ensure_scratch(total)) return false;
         if (grow_next) {
             grow_next = false;
+            ctr.n_grow++;
             if (!reset_table(st.gt_cap * 4)) return false;
         }
         if constexpr (Exec::has_fanout_fast) {
@@ -80,11 +95,13 @@ public:
             used_slots = fl[1];
             if (fl[0] & FO_ERR_COLLISION) { // two deliverer keys with one 64-bit hash: new seed, every route is mapped afresh
                 seed++;
+                ctr.n_reseed++;
                 if (!reset_table(st.gt_cap)) return false;
                 continue;
             }
             if (fl[0] & FO_ERR_FULL) {
                 if (st.gt_cap >= (1u << 29)) return fail("deliverer table too large");
+                ctr.n_grow++;
                 if (!reset_table(st.gt_cap * 4)) return false;
                 continue;
             }
@@ -92,6 +109,7 @@ public:
             res.n_groups = fl[2];
             res.group_overflow = fl[2] > group_cap;
             if (!res.group_overflow && !read_special(b, res)) return false;
+            ctr.n_generic++;
             return true;
         }
         return fail("fan-out grouping did not settle");
@@ -149,6 +167,7 @@ private:
         else {
             if (st.gt_cap > 0xFFF0u) return -1;
             if (!f_ctr && !fresh(f_ctr, 4)) return 0;
+            bool refilled = false;
             for (int attempt = 0; attempt < 12; attempt++) {
                 if (f_dense_cap < st.gt_cap) {
                     if (!x.sync()) return xfail() ? 1 : 0;
@@ -205,8 +224,11 @@ private:
                     res.n_groups = fl[2];
                     res.group_overflow = fl[2] > group_cap;
                     res.special = fl[3];
+                    ctr.n_fast++;
                     return 1;
                 }
+                if (!refilled) ctr.n_refill++;
+                refilled = true;
                 // route ids without a group slot (the first batch of a generation, routes added since): map them -- the passes of
                 // bmq_fanout_core.h over all pairs, cached ids fall through at once -- and run the split again
                 FanoutBatch b{};
@@ -221,11 +243,13 @@ private:
                 dense_stale = true;
                 if (fl[0] & FO_ERR_COLLISION) { // two deliverer keys with one 64-bit hash: new seed, every route is mapped afresh
                     seed++;
+                    ctr.n_reseed++;
                     if (!reset_table(st.gt_cap)) return 0;
                     continue;
                 }
                 if ((fl[0] & FO_ERR_FULL) || (uint64_t)used_slots * 2 > st.gt_cap) { // keep the table at most half full
                     if (st.gt_cap >= (1u << 29)) return fail("deliverer table too large") ? 1 : 0;
+                    ctr.n_grow++;
                     if (!reset_table(st.gt_cap * 4)) return 0;
                     if (st.gt_cap > 0xFFF0u) return -1;
                     continue;
@@ -280,6 +304,7 @@ private:
         ix.fo_dgroup = st.dgroup;
         ix.fo_cap = st.id_cap;
         generation = ix.generation;
+        if (regen) ctr = FanoutCounters{}; // (the counts belong to the state of one generation)
         // a grown id space keeps the table (hash -> slot stays valid); the per-id cache simply refills
         if (regen || !st.gt_hash) return reset_table(st.gt_hash && !regen ? st.gt_cap : initial_table);
         return x.fill_bytes(st.dgroup, 0xFF, sizeof(uint32_t) * (size_t)st.id_cap) ? true : xfail();

@@ -1,4 +1,4 @@
-// bmq_fanout_engine.inc -- bmq_fanout_group / bmq_fanout_group_dev: the segmented sort of a match CSR by DelivererKey (SURVEY.md 8f-4;
+// bmq_fanout_engine.inc -- bmq_fanout_group / bmq_fanout_group_dev / bmq_fanout_info_get: the segmented sort of a match CSR by DelivererKey (SURVEY.md 8f-4;
 // bmq_fanout_core.h says what it replaces in the reference).  Included at the end of bmq_engine.hip.
 namespace {
 int fanout_result(bmq_engine* e, const FanoutResult& r, uint32_t* out_n_groups, uint32_t* out_special) {
@@ -78,4 +78,26 @@ extern "C" int bmq_fanout_group(bmq_engine* e, const uint32_t* row_ptr, const ui
     }
     HIPCHK(e, hipStreamSynchronize(s));
     return fanout_result(e, r, out_n_groups, out_special);
+}
+
+extern "C" int bmq_fanout_info_get(const bmq_engine* ce, bmq_fanout_info* out) {
+    bmq_engine* e = const_cast<bmq_engine*>(ce);
+    if (!e || !out) return BMQ_E_INVAL;
+    std::unique_lock<std::recursive_mutex> api_lock(e->api);
+    std::lock_guard<std::mutex> g(e->mu);
+    memset(out, 0, sizeof(*out));
+    auto fill = [&](const auto& fo) {
+        if (fo.state_generation() == ~0ull) return; // created, never grouped
+        out->n_fast_calls = fo.ctr.n_fast;
+        out->n_generic_calls = fo.ctr.n_generic;
+        out->n_refill_calls = fo.ctr.n_refill;
+        out->n_table_grows = fo.ctr.n_grow;
+        out->n_table_reseeds = fo.ctr.n_reseed;
+        out->n_keys = fo.keys_mapped();
+        out->table_slots = fo.table_slots();
+        out->generation = fo.state_generation();
+    };
+    if (e->dfo) fill(*e->dfo);
+    else if (e->hfo) fill(*e->hfo);
+    return BMQ_OK;
 }

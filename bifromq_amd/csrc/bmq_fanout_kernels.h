@@ -18,7 +18,9 @@
 // Ids that have no group slot yet (first batch after a rebuild, routes added since) are counted by k_fo_hist; the control then
 // runs the mapping passes of bmq_fanout_core.h (fo_fill / fo_verify) once and starts over.
 #pragma once
+#ifndef BMQ_WAVE_EMU // (tools/emu/fanout_emu.cpp compiles this file with g++ against the wave64 emulator)
 #include <hip/hip_runtime.h>
+#endif
 
 #include "bmq_dist_kernels.h" // rank_below, wave_sync
 #include "bmq_fanout_core.h"
@@ -87,7 +89,9 @@ __host__ __device__ inline uint32_t fo_scatter_bins(uint32_t n_bins) { return (n
 __host__ __device__ inline uint32_t fo_scatter_lds(uint32_t n_bins, uint32_t tile) { return fo_scatter_bins(n_bins) * 8u + tile * 10u; }
 
 __global__ __launch_bounds__(FO_SC_WAVES * 64) void k_fo_scatter(FanoutFast f) {
+#ifndef BMQ_WAVE_EMU // (under the emulator the harness supplies the buffer)
     extern __shared__ __align__(16) unsigned char fo_lds[];
+#endif
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t tile = blockIdx.x * FO_SC_WAVES + wave;
     if (tile >= f.n_tiles) return;

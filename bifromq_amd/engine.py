@@ -558,6 +558,12 @@ class Engine:
             raise err
         return ng.value, sp.value
 
+    def fanout_info(self) -> _lib.FanoutInfo:
+        """bmq_fanout_info_get: which path answered the groupings of this generation, and the state of the group table"""
+        out = _lib.FanoutInfo()
+        self._check(_lib.lib().bmq_fanout_info_get(self.h, C.byref(out)))
+        return out
+
     # ---- receivers of shared subscriptions (DeliverExecutorGroup.send(GroupMatching, ...)) --------------------------------------------
     def share_members_apply(self, tables):
         """bmq_share_members_apply.  tables: {route id: [receiverUrl, ...]} (or a sequence of such pairs); the list order is the

@@ -604,6 +604,24 @@ int bmq_fanout_group(bmq_engine* e, const uint32_t* row_ptr, const uint32_t* rou
 int bmq_fanout_group_dev(bmq_engine* e, const uint32_t* d_row_ptr, const uint32_t* d_route_ids, uint32_t n_topics, uint64_t total,
                          uint32_t* d_out_topic, uint32_t* d_out_route, uint32_t* d_out_group_off, uint32_t* d_out_group_rep,
                          uint32_t group_cap, uint32_t* out_n_groups, uint32_t* out_special);
+/* Which way the grouping answered.  On the device a call takes a counting sort written for up to 1024 deliverer keys (the fast path,
+ * bifromq_amd/csrc/bmq_fanout_kernels.h) and, with more keys than that, generic radix-sort passes; a host-only engine has only the
+ * generic passes and reports n_fast_calls == 0.  Both give the same groups.  The counts are kept by the host-side control (no kernel
+ * takes part) and belong to the grouping state, which is tied to ONE generation of the route index: they restart at 0 when that state is
+ * dropped or built anew -- the first grouping after bmq_rebuild / bmq_compact, and bmq_compact_swap.  All fields are 0 before the first
+ * grouping of a batch that is not empty. */
+typedef struct bmq_fanout_info {
+    uint64_t n_fast_calls;    /* calls answered by the fast path */
+    uint64_t n_generic_calls; /* calls answered by the generic passes */
+    uint64_t n_refill_calls;  /* calls of the fast path that met route ids without a group (the first batch of a generation, routes added
+                                 since), mapped them and ran again -- whichever path answered in the end */
+    uint64_t n_table_grows;   /* times the group table was emptied to continue four times as large (kept at most half full) */
+    uint64_t n_table_reseeds; /* times it was emptied because two deliverer keys shared a 64-bit hash */
+    uint64_t n_keys;          /* distinct deliverer keys mapped so far (used slots of the table) */
+    uint64_t table_slots;     /* capacity of the group table */
+    uint64_t generation;      /* generation of the route index the state belongs to (bmq_index_info.generation) */
+} bmq_fanout_info;
+int bmq_fanout_info_get(const bmq_engine* e, bmq_fanout_info* out);
 
 /* ---- receivers of shared subscriptions: the step behind the fan-out grouping ------------------------------------------------------ */
 /* DeliverExecutorGroup.send(GroupMatching, ...) (bifromq-dist/bifromq-dist-worker/src/main/java/org/apache/bifromq/dist/worker/

@@ -47,6 +47,14 @@ int main(void) {
     uint32_t row[2];
     uint64_t need = 0;
     CHECK(bmq_match_batch(e, (const uint8_t*)"tenantA", toff, 1, tt, (const uint8_t*)"a/b/c", poff, 1, row, ids, 4, &need) == BMQ_E_NODEVICE);
+    /* fan-out grouping of a hand-written CSR (one row, the one route), and which path answered: a host-only engine has no fast path */
+    const uint32_t frow[2] = {0, 1}, fids[1] = {0};
+    uint32_t ftopic[1], froute[1], goff[2], grep[1], ng = 0, special = 9;
+    CHECK(bmq_fanout_group(e, frow, fids, 1, ftopic, froute, 1, goff, grep, 1, &ng, &special) == BMQ_OK && ng == 1 && special == 0);
+    CHECK(ftopic[0] == 0 && froute[0] == 0 && goff[0] == 0 && goff[1] == 1 && grep[0] == 0);
+    bmq_fanout_info fi;
+    CHECK(bmq_fanout_info_get(e, &fi) == BMQ_OK && fi.n_fast_calls == 0 && fi.n_generic_calls == 1 && fi.n_keys == 1 && fi.table_slots == 1024);
+    CHECK(fi.generation == info.generation);
     bmq_batcher* b = NULL;
     CHECK(bmq_batcher_create(e, NULL, &b) == BMQ_E_NODEVICE && b == NULL);
     bmq_engine_destroy(e);

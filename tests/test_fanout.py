@@ -12,9 +12,10 @@ import pytest
 
 import bifromq_amd as B
 from oracle import oracle as O
+from tests import fanout_cases as FC
 from tests import util as U
 
-SHARED, DEAD = 0xFFFFFFFE, 0xFFFFFFFF
+SHARED, DEAD = U.FANOUT_SHARED, U.FANOUT_DEAD
 
 
 def _workload(seed, n_filters=400, n_topics=300, brokers=(0, 1, 2), dkeys=9, shared=0.12):
@@ -38,41 +39,7 @@ def _workload(seed, n_filters=400, n_topics=300, brokers=(0, 1, 2), dkeys=9, sha
     return tenants, keys, topics, tt
 
 
-def _csr(rows):
-    row = np.zeros(len(rows) + 1, dtype=np.uint32)
-    row[1:] = np.cumsum([len(r) for r in rows])
-    ids = np.array([x for r in rows for x in r], dtype=np.uint32)
-    return row, ids
-
-
-def _check(eng, rows, key_of, result):
-    """result of Engine.fanout_group vs the oracle: the same groups, each with the same pairs in (topic, route) order"""
-    ot, orr, goff, grep, special = result
-    exp, exp_shared, exp_dead = O.fanout_groups(key_of, rows)
-    n_groups = len(goff) - 1
-    assert goff[0] == 0 and goff[-1] == sum(len(r) for r in rows) and (np.diff(goff.astype(np.int64)) > 0).all()
-    got = {}
-    kinds = []
-    for g in range(n_groups):
-        pairs = list(zip(ot[goff[g]:goff[g + 1]].tolist(), orr[goff[g]:goff[g + 1]].tolist()))
-        assert pairs == sorted(pairs)  # (topic, route id) order inside a group
-        rep = int(grep[g])
-        kinds.append(rep)
-        if rep == SHARED:
-            assert pairs == exp_shared
-        elif rep == DEAD:
-            assert pairs == exp_dead
-        else:
-            assert (any(p[1] == rep for p in pairs))  # the group is named by one of its own routes
-            dk = O.deliverer_key_of(eng.route_key(rep))
-            assert dk not in got
-            got[dk] = pairs
-    assert got == exp
-    assert special == (1 if exp_shared else 0) | (2 if exp_dead else 0)
-    # the special groups come last: shared, then dead
-    tail = [k for k in kinds if k >= SHARED]
-    assert kinds[len(kinds) - len(tail):] == tail == sorted(tail)
-    return len(exp)
+_csr, _check = U.csr_of_rows, U.fanout_check  # (shared with the shape-directed cases of tests/fanout_cases.py)
 
 
 def test_host_engine_groups_equal_oracle():
@@ -171,6 +138,29 @@ def test_argument_checks():
     ot, orr, goff, grep, sp = eng.fanout_group(np.array([0, 1, 3], dtype=np.uint32), np.array([0, 0, 9], dtype=np.uint32))
     assert sp == 2 and grep.tolist() == [0, DEAD] and ot.tolist() == [0, 1, 1] and orr.tolist() == [0, 0, 9]  # id 9 was never handed out
     eng.close()
+
+
+def test_host_engine_groups_after_compact_swap():
+    """bmq_compact_swap replaces (and frees) the index the grouping state of a host-only engine refers to: the state must go with it"""
+    FC.swap_sequence(-1)
+
+
+def test_fanout_info_mirror_has_the_layout_of_the_header(tmp_path):
+    """_lib.FanoutInfo restates bmq_fanout_info: same size, every field at the same offset"""
+    import ctypes as C
+    import os
+    import subprocess
+    from bifromq_amd import _lib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "bmq.h"', 'int main(void) {', 'printf("size %zu\\n", sizeof(bmq_fanout_info));']
+    lines += ['printf("%s %%zu\\n", offsetof(bmq_fanout_info, %s));' % (f, f) for f, _ in _lib.FanoutInfo._fields_]
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines + ['return 0;', '}']))
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(root, "include"), str(src), "-o", str(exe)], check=True, capture_output=True)
+    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    assert int(got["size"]) == C.sizeof(_lib.FanoutInfo)
+    for f, _ in _lib.FanoutInfo._fields_:
+        assert int(got[f]) == getattr(_lib.FanoutInfo, f).offset, f
 
 
 # ---- on the device --------------------------------------------------------------------------------------------------------------

@@ -425,3 +425,44 @@ def churn_case(eng, match_fn, n_tenants, per_tenant, n_ops, n_topics, sample_ten
     assert_rows_equal_modulo_quirk_ii(keys_sorted, tn[:S], stt.tolist(), [sorted(r) for r in res.per_topic()], got)
     assert any(keys_sorted[r] in added for g in got for r in g)  # routes subscribed by the batch are matched
     return n_new
+
+
+# ---- fan-out grouping: bmq_fanout_group against oracle.fanout_groups (tests/test_fanout.py, tests/fanout_cases.py) ----
+FANOUT_SHARED, FANOUT_DEAD = 0xFFFFFFFE, 0xFFFFFFFF
+
+
+def csr_of_rows(rows):
+    row = np.zeros(len(rows) + 1, dtype=np.uint32)
+    row[1:] = np.cumsum([len(r) for r in rows])
+    ids = np.array([x for r in rows for x in r], dtype=np.uint32)
+    return row, ids
+
+
+def fanout_check(eng, rows, key_of, result):
+    """result of Engine.fanout_group vs the oracle: the same groups, each with the same pairs in (topic, route) order"""
+    ot, orr, goff, grep, special = result
+    exp, exp_shared, exp_dead = O.fanout_groups(key_of, rows)
+    n_groups = len(goff) - 1
+    assert goff[0] == 0 and goff[-1] == sum(len(r) for r in rows) and (np.diff(goff.astype(np.int64)) > 0).all()
+    got = {}
+    kinds = []
+    for g in range(n_groups):
+        pairs = list(zip(ot[goff[g]:goff[g + 1]].tolist(), orr[goff[g]:goff[g + 1]].tolist()))
+        assert pairs == sorted(pairs)  # (topic, route id) order inside a group
+        rep = int(grep[g])
+        kinds.append(rep)
+        if rep == FANOUT_SHARED:
+            assert pairs == exp_shared
+        elif rep == FANOUT_DEAD:
+            assert pairs == exp_dead
+        else:
+            assert (any(p[1] == rep for p in pairs))  # the group is named by one of its own routes
+            dk = O.deliverer_key_of(eng.route_key(rep))
+            assert dk not in got
+            got[dk] = pairs
+    assert got == exp
+    assert special == (1 if exp_shared else 0) | (2 if exp_dead else 0)
+    # the special groups come last: shared, then dead
+    tail = [k for k in kinds if k >= FANOUT_SHARED]
+    assert kinds[len(kinds) - len(tail):] == tail == sorted(tail)
+    return len(exp)

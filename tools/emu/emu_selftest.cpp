@@ -1,7 +1,7 @@
 // emu_selftest.cpp -- the emulator's own cross-lane operations against their definitions (tests/test_expand_emu.py runs it):
 // ballot with lanes that have returned, readlane / readfirstlane, the DPP row shifts and broadcasts as the inclusive scan of
 // bmq_expand_kernel.h uses them (against a serial prefix sum, for random inputs and with a tail of lanes gone), LDS hand-over through
-// wave_sync, and -- in a forked child -- that a divergent cross-lane operation aborts instead of pairing up lanes that are not at the same place.
+// wave_sync, a wave that is not the first of its workgroup (threadIdx.x = wave * 64 + lane, the lane helpers mask it), __any, and -- in a forked child -- that a divergent cross-lane operation aborts instead of pairing up lanes that are not at the same place.
 #define BMQ_WAVE_EMU 1
 #include "wave_emu.h"
 
@@ -62,6 +62,27 @@ int main() {
             CHECK(rl[l] == in[alive - 1]);
             CHECK(handed[l] == in[(l + 1) % alive] * 3u);
         }
+    }
+    // wave 3 of a workgroup: threadIdx.x counts on, the helpers that want a lane number still get one
+    {
+        uint32_t tid[64], lane[64], rank[64], bit[64], any1[64], any0[64];
+        const unsigned long long mask = 0xF0F0F0F0A5A5A5A5ull;
+        wemu::run_wave(5, [&] {
+            const uint32_t l = threadIdx.x & 63u;
+            tid[l] = threadIdx.x;
+            lane[l] = lane_here();
+            rank[l] = rank_below(mask);
+            bit[l] = lane_bit(mask);
+            any1[l] = __any(l == 37) ? 1u : 0u;
+            any0[l] = __any(l == 64) ? 1u : 0u;
+            CHECK(blockIdx.x == 5);
+        }, 3);
+        for (uint32_t l = 0; l < 64; l++) {
+            CHECK(tid[l] == 3 * 64 + l && lane[l] == l);
+            CHECK(rank[l] == (uint32_t)__builtin_popcountll(mask & ((1ull << l) - 1ull)) && bit[l] == ((mask >> l) & 1u));
+            CHECK(any1[l] == 1 && any0[l] == 0);
+        }
+        wemu::run_wave(0, [&] { CHECK(threadIdx.x < 64); }); // (the default stays wave 0)
     }
     // divergence: half of the lanes ask for a ballot, the other half for a wave_sync -> abort()
     const pid_t pid = fork();

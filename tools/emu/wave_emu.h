@@ -7,6 +7,9 @@
 // divergence and aborts.  Between two rendezvous a lane runs ahead of the others on its own, so code that relies on lockstep execution
 // without a wave_sync() between an LDS write and another lane's read of it fails here (on purpose).  `__shared__` variables are function
 // statics: one workgroup at a time, contents survive from one workgroup to the next like stale LDS does.
+//
+// A workgroup of several INDEPENDENT waves (each owns its slice of LDS, no __syncthreads) is run one wave after the other: run_wave takes
+// the wave's index in the workgroup and threadIdx.x reads wave * 64 + lane.  The single-wave harnesses keep wave 0.
 #pragma once
 #include <ucontext.h>
 
@@ -29,6 +32,7 @@ inline uint2 make_uint2(uint32_t x, uint32_t y) { return uint2{x, y}; }
 
 #define __global__
 #define __device__
+#define __host__
 #define __forceinline__ inline
 #define __shared__ static
 #define __launch_bounds__(...)
@@ -54,6 +58,7 @@ struct State {
     uint64_t val[64], res[64];
     int cur = -1;
     uint32_t block = 0;
+    uint32_t wave = 0; // index of the wave in its workgroup
     std::function<void()> body;
     unsigned long long rendezvous = 0;
 };
@@ -61,7 +66,7 @@ inline State& st() {
     static State s;
     return s;
 }
-inline Dim3 tid() { return Dim3{(uint32_t)st().cur, 0, 0}; }
+inline Dim3 tid() { return Dim3{st().wave * 64u + (uint32_t)st().cur, 0, 0}; }
 inline Dim3 bid() { return Dim3{st().block, 0, 0}; }
 inline uint32_t& grid_size() { // what gridDim.x reads (persistent kernels stride by it); set by the harness
     static uint32_t g = 1;
@@ -163,12 +168,13 @@ inline void resolve() {
     for (int l = 0; l < 64; l++) s.parked[l] = false;
 }
 
-// runs `body` as workgroup `block` (one wave of 64 lanes)
-inline void run_wave(uint32_t block, std::function<void()> body) {
+// runs `body` as wave `wave` (64 lanes) of workgroup `block`
+inline void run_wave(uint32_t block, std::function<void()> body, uint32_t wave = 0) {
     State& s = st();
     const size_t STK = 256 * 1024;
     if (!s.stacks) s.stacks = (char*)malloc(64 * STK);
     s.block = block;
+    s.wave = wave;
     s.body = std::move(body);
     for (int l = 0; l < 64; l++) {
         s.done[l] = s.parked[l] = false;
@@ -206,18 +212,19 @@ inline unsigned long long ballot64(bool p) { return wemu::collective(wemu::K_BAL
 inline uint32_t sgpr(uint32_t v) { return (uint32_t)wemu::collective(wemu::K_FIRST, 0, v); }
 inline uint32_t read_lane(uint32_t v, uint32_t l) { return (uint32_t)wemu::collective(wemu::K_READLANE, l, v); }
 template <int CTRL, int ROWS> inline uint32_t dpp_take(uint32_t v) { return (uint32_t)wemu::collective(wemu::K_DPP, (uint64_t)CTRL | ((uint64_t)ROWS << 16), v); }
-inline uint32_t rank_below(unsigned long long mask) { return (uint32_t)__builtin_popcountll(mask & ((1ull << threadIdx.x) - 1ull)); }
-inline uint32_t lane_bit(unsigned long long m) { return (uint32_t)(m >> threadIdx.x) & 1u; }
+inline uint32_t rank_below(unsigned long long mask) { return (uint32_t)__builtin_popcountll(mask & ((1ull << (threadIdx.x & 63u)) - 1ull)); }
+inline uint32_t lane_bit(unsigned long long m) { return (uint32_t)(m >> (threadIdx.x & 63u)) & 1u; }
 inline uint32_t first_bit(unsigned long long m) { return (uint32_t)__builtin_ffsll((long long)m) - 1u; }
 inline uint32_t count_bits(unsigned long long m) { return (uint32_t)__builtin_popcountll(m); }
 inline uint32_t uniform_word(const uint32_t* p) { return *p; }
 inline uint32_t copy_here(uint32_t v) { return v; }
-inline uint32_t lane_here() { return threadIdx.x; }
+inline uint32_t lane_here() { return threadIdx.x & 63u; }
 } // namespace bmq
 
 // HIP spellings the older kernels use
 inline unsigned long long __ballot(bool p) { return wemu::collective(wemu::K_BALLOT, 0, p ? 1 : 0); }
 inline bool __all(bool p) { return wemu::collective(wemu::K_BALLOT, 1, p ? 0 : 1) == 0; }
+inline bool __any(bool p) { return wemu::collective(wemu::K_BALLOT, 2, p ? 1 : 0) != 0; }
 inline uint32_t __shfl(uint32_t v, uint32_t l) { return (uint32_t)wemu::collective(wemu::K_SHFL, l, v); }
 inline uint32_t __shfl(uint32_t v, int l) { return (uint32_t)wemu::collective(wemu::K_SHFL, (uint32_t)l, v); }
 inline uint32_t __shfl_up(uint32_t v, int d) { return (uint32_t)wemu::collective(wemu::K_SHFL_UP, (uint64_t)d, v); }
