@@ -16,13 +16,13 @@ CSRC = os.path.join(_HERE, "csrc")
 
 # every symbol include/bmq.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
-    "bmq_engine_create", "bmq_engine_destroy", "bmq_last_error", "bmq_version", "bmq_rebuild", "bmq_compact", "bmq_compact_begin", "bmq_compact_poll", "bmq_compact_swap", "bmq_compact_abort", "bmq_routes_count_in", "bmq_compact_begin_in", "bmq_routes_import", "bmq_routes_apply", "bmq_routes_apply_async", "bmq_routes_apply_wait",
+    "bmq_engine_create", "bmq_engine_destroy", "bmq_last_error", "bmq_version", "bmq_rebuild", "bmq_compact", "bmq_compact_begin", "bmq_compact_poll", "bmq_compact_swap", "bmq_compact_abort", "bmq_routes_count_in", "bmq_routes_tenant_stats", "bmq_compact_begin_in", "bmq_routes_import", "bmq_routes_apply", "bmq_routes_apply_async", "bmq_routes_apply_wait",
     "bmq_index_info_get", "bmq_route_key", "bmq_route_keys", "bmq_index_find", "bmq_match_batch", "bmq_match_batch_dev",
     "bmq_match_finish", "bmq_set_kernel_timing", "bmq_match_submit", "bmq_match_wait", "bmq_match_submit_fmt", "bmq_match_submit_dev", "bmq_match_wait_dev", "bmq_match_wait_counts", "bmq_match_wait_ranges", "bmq_match_wait_grouped", "bmq_host_alloc", "bmq_host_free", "bmq_sync", "bmq_stats_get", "bmq_stream", "bmq_match_all", "bmq_route_key_encode",
     "bmq_route_key_decode", "bmq_java_string_hash", "bmq_range_lookup", "bmq_comm_unique_id", "bmq_comm_init", "bmq_comm_destroy", "bmq_exchange_fanout",
     "bmq_exchange_csr", "bmq_exchange_wait", "bmq_partition_batch_dev", "bmq_retain_message_key", "bmq_retain_filter_route", "bmq_retain_rebuild", "bmq_retain_rebuild_ex", "bmq_retain_apply", "bmq_retain_apply_ex", "bmq_retain_topic",
     "bmq_retain_topic_info", "bmq_retain_find_all", "bmq_retain_expired", "bmq_retain_apply_batch", "bmq_retain_compact", "bmq_retain_compact_begin", "bmq_retain_compact_build", "bmq_retain_compact_swap", "bmq_retain_compact_abort", "bmq_retain_info_get",
-    "bmq_retain_live_ids", "bmq_retain_topics",
+    "bmq_retain_live_ids", "bmq_retain_topics", "bmq_retain_tenant_counts", "bmq_retain_message_keys", "bmq_retain_remove_ids",
     "bmq_retain_match_batch", "bmq_retain_match_batch_dev", "bmq_retain_match_limited", "bmq_batcher_create", "bmq_batcher_destroy",
     "bmq_batcher_match_all", "bmq_batcher_submit", "bmq_batcher_stats_get", "bmq_poller_stats_get", "bmq_poller_control",
     "bmq_route_cache_create", "bmq_route_cache_destroy", "bmq_route_cache_get", "bmq_route_cache_get_async", "bmq_route_cache_get_batch", "bmq_batcher_match_batch", "bmq_route_cache_is_cached", "bmq_route_cache_apply",
@@ -141,6 +141,10 @@ def lib() -> C.CDLL:
             "bmq_compact_begin": (C.c_int, [vp]),
             "bmq_compact_begin_in": (C.c_int, [vp, C.c_uint8, C.c_char_p, u32, C.c_char_p, u32]),
             "bmq_routes_count_in": (C.c_int, [vp, C.c_uint8, C.c_char_p, u32, C.c_char_p, u32, P(u64), P(u64)]),
+            "bmq_routes_tenant_stats": (C.c_int, [vp, C.c_uint8, C.c_char_p, u32, C.c_char_p, u32, vp, u64, vp, vp, u32, P(u32), P(u64)]),
+            "bmq_retain_tenant_counts": (C.c_int, [vp, vp, u64, vp, vp, u32, P(u32), P(u64)]),
+            "bmq_retain_message_keys": (C.c_int, [vp, vp, u32, vp, u64, vp]),
+            "bmq_retain_remove_ids": (C.c_int, [vp, vp, u32, u64, P(u64)]),
             "bmq_routes_import": (C.c_int, [vp, vp, C.c_uint8, C.c_char_p, u32, C.c_char_p, u32, P(u64), P(u64)]),
             "bmq_compact_poll": (C.c_int, [vp, u32, P(u32)]),
             "bmq_compact_swap": (C.c_int, [vp, P(u64), P(u64)]),

@@ -1269,5 +1269,18 @@ BMQ_HD unsigned long long boundary_filter_one(const uint8_t* kpool, unsigned lon
     refs[i] = r & KREF_OFF_MASK;
     return 0;
 }
+// one key reference of the per-tenant census (TenantsStats.doReset, DW/TenantsStats.java:229-246): the directory slot of the key's tenant
+// if the key is live and inside the boundary, NONE otherwise; flag = 1 normal, 2 unordered share, 3 ordered share; len = the key's length.
+// Reads only.
+BMQ_HD uint32_t census_key_one(const DistIndexMut& ix, uint32_t id, const KeyBoundary& b, uint32_t& flag, uint32_t& len) {
+    const unsigned long long r = ix.kref[id];
+    len = (uint32_t)(r >> KREF_LEN_SHIFT);
+    if (len == 0 || !key_in_boundary(ix.kpool, r, b)) return NONE;
+    KeyView k;
+    const unsigned long long off = r & KREF_OFF_MASK;
+    if (!key_parse(ix.kpool, off, off + len, k)) return NONE;
+    flag = k.flag;
+    return tenant_find(ix.tenants, ix.tenant_mask, ix.tenant_names, ix.kpool, k.tenant, k.tenant_end);
+}
 
 } // namespace bmq

@@ -543,6 +543,37 @@ public:
         bytes = c[1];
         return true;
     }
+    // The per-tenant census of the live keys inside `b` (TenantsStats.doReset, DW/TenantsStats.java:229-246: normal and shared routes per
+    // tenant from the key's flag; :140-162: the tenant's space): one READ-ONLY pass over kref[0, next_id) (on the device: k_b_census,
+    // bmq_census_kernels.h) into a table of four 64-bit counters per directory slot, zeroed per call.  Tenants with nothing inside are
+    // left out; the result is in byte order of the tenant ids.
+    struct TenantStat {
+        std::string tenant;
+        uint64_t n_normal = 0, n_unordered_share = 0, n_ordered_share = 0, key_bytes = 0;
+    };
+    bool tenant_stats(const Boundary& b, std::vector<TenantStat>& out) {
+        error.clear();
+        out.clear();
+        if (!built || next_id == 0 || dir_slots == 0) return true;
+        if (dir_dirty && !flush_directory()) return false;
+        const size_t words = 4 * (size_t)dir_slots;
+        if (!ensure_buf(g_census, g_census_cap, words) || !stage_boundary(q_bnd, b)) return false;
+        std::vector<unsigned long long> t(words);
+        if (!x.zero(g_census, sizeof(unsigned long long) * words) || !x.census(mut(), next_id, q_bnd.kb, g_census) ||
+            !x.copy_out(t.data(), g_census, sizeof(unsigned long long) * words))
+            return xfail();
+        for (const auto& [name, d] : tenant_slot) {
+            const unsigned long long* c = t.data() + 4 * (size_t)d;
+            if ((c[0] | c[1] | c[2]) == 0) continue;
+            out.push_back(TenantStat{name, c[0], c[1], c[2], c[3]});
+        }
+        std::sort(out.begin(), out.end(), [](const TenantStat& a, const TenantStat& c) { // unsigned byte order, a proper prefix first
+            const size_t m = std::min(a.tenant.size(), c.tenant.size());
+            const int r = m ? memcmp(a.tenant.data(), c.tenant.data(), m) : 0;
+            return r ? r < 0 : a.tenant.size() < c.tenant.size();
+        });
+        return true;
+    }
     // The buffers a chunk of `n` ids / `bytes` key bytes of a generation change goes through, taken NOW: the first bmq_compact_poll used to
     // allocate them -- a dozen device allocations beside a saturated matcher, the one batch of a compaction that took 10 ms instead of 0.35.
     bool reserve_import(uint32_t n, uint64_t bytes) {
@@ -661,11 +692,11 @@ public:
         rel(trie); rel(dir); rel(names); rel(dict); rel(dpool); rel(route_pos); rel(kref); rel(khash); rel(kpool); rel(bc);
         rel(s_key_off); rel(s_op); rel(s_put_rank); rel(s_dir_slot); rel(s_nn); rel(s_flag); rel(s_target); rel(s_order);
         rel(s_sorted_target); rel(s_group_done); rel(s_unknown); rel(s_grow); rel(s_bt_first); rel(s_bt_nodes); rel(s_bt_keys); rel(s_bt_dir);
-        rel(g_ids); rel(g_refs); rel(g_offs); rel(g_bytes); rel(q_bnd.buf); rel(imp_bnd.buf);
+        rel(g_ids); rel(g_refs); rel(g_offs); rel(g_bytes); rel(g_census); rel(q_bnd.buf); rel(imp_bnd.buf);
         q_bnd = imp_bnd = StagedBoundary{};
         imp_bounded = false;
         trie_cap = trie_used = 0; dir_slots = 0; names_cap = names_used = 0; dict_slots = 0; dpool_cap = 0; rp_cap = 0; id_cap = next_id = 0;
-        kpool_cap = kpool_used = 0; s_cap = 0; s_bt_cap = 0; s_grow_cap = 0; g_ids_cap = g_refs_cap = g_offs_cap = g_bytes_cap = 0;
+        kpool_cap = kpool_used = 0; s_cap = 0; s_bt_cap = 0; s_grow_cap = 0; g_ids_cap = g_refs_cap = g_offs_cap = g_bytes_cap = g_census_cap = 0;
         tenant_slot.clear(); free_regions.clear(); dir_h.clear(); names_h.clear(); trie_garbage = 0;
         built = false;
     }
@@ -682,6 +713,8 @@ private:
     uint64_t* g_offs = nullptr;
     uint8_t* g_bytes = nullptr;
     size_t g_ids_cap = 0, g_refs_cap = 0, g_offs_cap = 0, g_bytes_cap = 0;
+    unsigned long long* g_census = nullptr; // tenant_stats: four counters per directory slot
+    size_t g_census_cap = 0;
     // a boundary in exec memory: [inside keys, their bytes: two 64-bit counters][start key][end key]
     struct StagedBoundary {
         uint8_t* buf = nullptr;

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -1252,6 +1253,52 @@ int bmq_routes_count_in(const bmq_engine* ce, uint8_t flags, const uint8_t* star
     if (out_routes) *out_routes = routes;
     if (out_key_bytes) *out_key_bytes = bytes;
     return BMQ_OK;
+}
+
+// caps in, needed sizes out (bmq_route_keys, bmq_retain_topics): names packed with offsets, `width` 64-bit words of numbers per name
+static int pack_names(bmq_engine* e, const std::vector<std::pair<std::string, std::array<uint64_t, 4>>>& rows, uint32_t width, uint8_t* out_names, uint64_t names_cap,
+                      uint64_t* out_off, uint64_t* out_numbers, uint32_t cap, uint32_t* out_n, uint64_t* out_name_bytes) {
+    uint64_t bytes = 0;
+    for (const auto& r : rows) bytes += r.first.size();
+    if (out_n) *out_n = (uint32_t)rows.size();
+    if (out_name_bytes) *out_name_bytes = bytes;
+    if (rows.size() > cap || (!rows.empty() && (!out_off || !out_numbers))) return set_err(e, BMQ_E_NOSPACE, "output arrays too small: see the needed sizes");
+    uint64_t at = 0;
+    for (size_t i = 0; i < rows.size(); i++) {
+        out_off[i] = at;
+        at += rows[i].first.size();
+        for (uint32_t k = 0; k < width; k++) out_numbers[(size_t)width * i + k] = rows[i].second[k];
+    }
+    if (out_off) out_off[rows.size()] = at;
+    if (bytes > names_cap || (bytes && !out_names)) return set_err(e, BMQ_E_NOSPACE, "name buffer too small: see the needed sizes");
+    at = 0;
+    for (const auto& r : rows) {
+        if (!r.first.empty()) memcpy(out_names + at, r.first.data(), r.first.size());
+        at += r.first.size();
+    }
+    return BMQ_OK;
+}
+
+int bmq_routes_tenant_stats(const bmq_engine* ce, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len,
+                            uint8_t* out_tenants, uint64_t tenants_cap, uint64_t* out_tenant_off, uint64_t* out_stats, uint32_t cap,
+                            uint32_t* out_n_tenants, uint64_t* out_tenant_bytes) {
+    bmq_engine* e = const_cast<bmq_engine*>(ce);
+    if (!e) return BMQ_E_INVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    Boundary bound;
+    if (!parse_boundary(flags, start, start_len, end, end_len, bound)) return set_err(e, BMQ_E_INVAL, "malformed boundary (start >= end, or a present key without bytes)");
+    if (int rc_open = complete_apply(e)) return rc_open; // (a batch handed over with bmq_routes_apply_async first)
+    if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
+    std::vector<std::pair<std::string, std::array<uint64_t, 4>>> rows;
+    const bool ok = with_index(e, [&](auto& ix) { // (the serving generation, also while a compaction builds the next one)
+        std::vector<typename std::remove_reference_t<decltype(ix)>::TenantStat> st;
+        const bool r = ix.tenant_stats(bound, st);
+        if (!r) e->err = ix.error;
+        for (auto& t : st) rows.push_back({std::move(t.tenant), {t.n_normal, t.n_unordered_share, t.n_ordered_share, t.key_bytes}});
+        return r;
+    });
+    if (!ok) return index_error(e, e->err, false);
+    return pack_names(e, rows, 4, out_tenants, tenants_cap, out_tenant_off, out_stats, cap, out_n_tenants, out_tenant_bytes);
 }
 
 // ---- bmq_routes_import: the live keys of `src` inside a boundary into `dst`, without a KV scan ---------------------------------------

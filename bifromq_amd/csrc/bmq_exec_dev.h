@@ -13,6 +13,7 @@
 #include <string>
 
 #include "bmq_build_core.h"
+#include "bmq_census_kernels.h"
 #include "bmq_fanout_core.h"
 #include "bmq_fanout_kernels.h"
 #include "bmq_retain_core.h"
@@ -203,6 +204,26 @@ __global__ __launch_bounds__(BK) void k_r_topic_write(RetainMut m, const uint32_
 __global__ __launch_bounds__(256) void k_r_gc_flags(RetainMut m, GcQuery q, uint8_t* flags) {
     const uint32_t id = blockIdx.x * 256 + threadIdx.x;
     if (id < q.n_ids) flags[id] = (uint8_t)gc_flag_one(m, q, id);
+}
+__global__ __launch_bounds__(256) void k_r_remove_ids(RetainMut m, const uint32_t* ids, uint32_t n, uint32_t n_ids) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) remove_id_one(m, ids, i, n_ids);
+}
+__global__ __launch_bounds__(BK) void k_r_census_bulk(RetainMut m, const uint32_t* ranges, uint32_t n_tenants, uint32_t* out) {
+    const uint32_t t = blockIdx.x * BK + threadIdx.x;
+    if (t < n_tenants) census_bulk_one(m, ranges, t, out);
+}
+__global__ __launch_bounds__(256) void k_r_census_pick(const unsigned long long* table, uint32_t n, unsigned long long* list, uint32_t* count) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) census_pick_one(table, i, list, count);
+}
+__global__ __launch_bounds__(BK) void k_r_node_len(RetainMut m, const uint32_t* nodes, uint32_t n, uint32_t* lens) {
+    const uint32_t i = blockIdx.x * BK + threadIdx.x;
+    if (i < n) ov_node_len_one(m, nodes, i, lens);
+}
+__global__ __launch_bounds__(BK) void k_r_node_write(RetainMut m, const uint32_t* nodes, uint32_t n, const unsigned long long* offs, uint8_t* out) {
+    const uint32_t i = blockIdx.x * BK + threadIdx.x;
+    if (i < n) ov_node_write_one(m, nodes, i, offs, out);
 }
 __global__ __launch_bounds__(64) void k_r_find_tenant(RetainMut m, const uint8_t* name, uint32_t len, uint32_t* out) {
     if (threadIdx.x || blockIdx.x) return;
@@ -416,6 +437,12 @@ struct DevExec {
         hipLaunchKernelGGL(k_b_boundary, dim3(std::min((n + 255u) / 256u, BND_BLOCKS)), dim3(256), 0, stream, refs, n, kpool, b, ctr);
         return launched();
     }
+    // table[4 * directory slot ..] += live keys of kref[0, n) inside `b` per flag, and their bytes (k_b_census, bmq_census_kernels.h; b's keys: exec memory)
+    bool census(const DistIndexMut& ix, uint32_t n, const KeyBoundary& b, unsigned long long* table) {
+        if (n == 0) return true;
+        hipLaunchKernelGGL(k_b_census, dim3(census_grid(n)), dim3(CENSUS_WAVES * 64), 0, stream, ix, n, b, table);
+        return launched();
+    }
     // ---- fan-out grouping, fast path (bmq_fanout_kernels.h): counting sort that carries its payload ----
     static constexpr bool has_fanout_fast = true;
     bool fo_dense(const FanoutState& st, uint16_t* dense, uint32_t* n_used) {
@@ -531,6 +558,34 @@ struct DevExec {
         if (!BMQ_X(hipcub::DeviceSelect::Flagged(nullptr, bytes, iota, flags, out_ids, out_count, (int)q.n_ids, stream))) return false;
         if (!ensure_tmp(bytes)) return false;
         return BMQ_X(hipcub::DeviceSelect::Flagged(tmp, bytes, iota, flags, out_ids, out_count, (int)q.n_ids, stream));
+    }
+    bool r_remove_ids(const RetainMut& m, const uint32_t* ids, uint32_t n, uint32_t n_ids) {
+        hipLaunchKernelGGL(k_r_remove_ids, grid(n, 256), dim3(256), 0, stream, m, ids, n, n_ids);
+        return launched();
+    }
+    // out[t] = live topics of the bulk-loaded rank range ranges[2 t .. 2 t + 1]
+    bool r_census_bulk(const RetainMut& m, const uint32_t* ranges, uint32_t n_tenants, uint32_t* out) {
+        if (n_tenants == 0) return true;
+        hipLaunchKernelGGL(k_r_census_bulk, grid(n_tenants, BK), dim3(BK), 0, stream, m, ranges, n_tenants, out);
+        return launched();
+    }
+    // table[tenant node] += retained topics among the ids [m.base_n, n_ids) (k_r_census, bmq_census_kernels.h)
+    bool r_census(const RetainMut& m, uint32_t n_ids, unsigned long long* table) {
+        if (n_ids <= m.base_n) return true;
+        hipLaunchKernelGGL(k_r_census, dim3(census_grid(n_ids - m.base_n)), dim3(CENSUS_WAVES * 64), 0, stream, m, n_ids, table);
+        return launched();
+    }
+    bool r_census_pick(const unsigned long long* table, uint32_t n, unsigned long long* list, uint32_t* count) {
+        hipLaunchKernelGGL(k_r_census_pick, grid(n, 256), dim3(256), 0, stream, table, n, list, count);
+        return launched();
+    }
+    bool r_node_lens(const RetainMut& m, const uint32_t* nodes, uint32_t n, uint32_t* lens) {
+        hipLaunchKernelGGL(k_r_node_len, grid(n, BK), dim3(BK), 0, stream, m, nodes, n, lens);
+        return launched();
+    }
+    bool r_node_write(const RetainMut& m, const uint32_t* nodes, uint32_t n, const unsigned long long* offs, uint8_t* out) {
+        hipLaunchKernelGGL(k_r_node_write, grid(n, BK), dim3(BK), 0, stream, m, nodes, n, offs, out);
+        return launched();
     }
     bool r_find_tenant(const RetainMut& m, const uint8_t* name, uint32_t len, uint32_t* out) {
         hipLaunchKernelGGL(k_r_find_tenant, dim3(1), dim3(64), 0, stream, m, name, len, out);

@@ -190,6 +190,17 @@ struct HostExec {
         ctr[1] += bytes.load();
         return true;
     }
+    // table[4 * directory slot ..] += live keys of kref[0, n) inside `b` per flag, and their bytes (k_b_census on the device)
+    bool census(const DistIndexMut& ix, uint32_t n, const KeyBoundary& b, unsigned long long* table) {
+        par(n, [&](size_t i) {
+            uint32_t flag = 0, len = 0;
+            const uint32_t d = census_key_one(ix, (uint32_t)i, b, flag, len);
+            if (d == NONE) return;
+            __atomic_fetch_add(table + 4 * (size_t)d + (flag - 1), 1ull, __ATOMIC_RELAXED);
+            __atomic_fetch_add(table + 4 * (size_t)d + 3, (unsigned long long)len, __ATOMIC_RELAXED);
+        });
+        return true;
+    }
     // ---- receivers of shared subscriptions (bmq_share.h) ----
     void mark(int) {} // (HIP-event marks of the device executor)
     float mark_ms(int, int) { return 0; }
@@ -257,6 +268,34 @@ struct HostExec {
         for (uint32_t id = 0; id < q.n_ids; id++)
             if (gc_flag_one(m, q, id)) out_ids[n++] = id;
         *out_count = n;
+        return true;
+    }
+    bool r_remove_ids(const RetainMut& m, const uint32_t* ids, uint32_t n, uint32_t n_ids) {
+        par(n, [&](size_t i) { remove_id_one(m, ids, (uint32_t)i, n_ids); });
+        return true;
+    }
+    bool r_census_bulk(const RetainMut& m, const uint32_t* ranges, uint32_t n_tenants, uint32_t* out) {
+        par(n_tenants, [&](size_t t) { census_bulk_one(m, ranges, (uint32_t)t, out); });
+        return true;
+    }
+    bool r_census(const RetainMut& m, uint32_t n_ids, unsigned long long* table) { // (k_r_census on the device)
+        if (n_ids <= m.base_n) return true;
+        par(n_ids - m.base_n, [&](size_t i) {
+            const uint32_t tn = census_topic_one(m, m.base_n + (uint32_t)i);
+            if (tn != NONE) __atomic_fetch_add(table + tn, 1ull, __ATOMIC_RELAXED);
+        });
+        return true;
+    }
+    bool r_census_pick(const unsigned long long* table, uint32_t n, unsigned long long* list, uint32_t* count) {
+        par(n, [&](size_t i) { census_pick_one(table, (uint32_t)i, list, count); });
+        return true;
+    }
+    bool r_node_lens(const RetainMut& m, const uint32_t* nodes, uint32_t n, uint32_t* lens) {
+        par(n, [&](size_t i) { ov_node_len_one(m, nodes, (uint32_t)i, lens); });
+        return true;
+    }
+    bool r_node_write(const RetainMut& m, const uint32_t* nodes, uint32_t n, const unsigned long long* offs, uint8_t* out) {
+        par(n, [&](size_t i) { ov_node_write_one(m, nodes, (uint32_t)i, offs, out); });
         return true;
     }
     bool r_find_tenant(const RetainMut& m, const uint8_t* name, uint32_t len, uint32_t* out) {

@@ -378,10 +378,58 @@ BMQ_HD void rcommit_one(const RetainMut& m, const RetainOps& ob, uint32_t i) {
     ob.out_ids[i] = id;
 }
 
+// Removal BY ID: the post-commit half of RetainStoreCoProc.gc (RS/RetainStoreCoProc.java:270-275), for ids the engine itself handed out
+// (bmq_retain_expired / bmq_retain_live_ids / a match) -- the id names its slot, nothing is looked up.  A live id goes dead exactly as a
+// remove op leaves it in rcommit_one.  64 ids of one word may arrive in 64 lanes and an id may be listed twice: the lane whose OR flipped
+// the bit is the one that counts.  ids[i] < n_ids (the host checked every id before anything was launched).
+BMQ_HD void remove_id_one(const RetainMut& m, const uint32_t* ids, uint32_t i, uint32_t n_ids) {
+    const uint32_t id = ids[i];
+    if (id >= n_ids || id >= m.id_cap) return;
+    const unsigned long long bit = 1ull << (id & 63u);
+    if (atom_or(&m.dead_bits[id >> 6], bit) & bit) return; // dead already, or listed twice: another lane took it
+    m.expire_at[id] = 0ull;
+    const uint32_t c = i & (N_CTR_LANES - 1);
+    atom_add(&m.ctr->went_dead[c], 1u);
+    if (id < m.base_n) atom_add(&m.ctr->base_went_dead[c], 1u);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// retained topics per tenant (RetainStoreCoProc.load(), RS/RetainStoreCoProc.java:279-296: tenantsStats.increaseTopicCount per key)
+// ------------------------------------------------------------------------------------------------------------
+// a bulk-loaded tenant owns the rank range [lo, hi): its live topics are the range minus the dead ids inside -- no pass over the ids
+BMQ_HD void census_bulk_one(const RetainMut& m, const uint32_t* ranges, uint32_t t, uint32_t* out) {
+    const uint32_t lo = ranges[2 * t], hi = ranges[2 * t + 1];
+    out[t] = (hi - lo) - (dead_before(m.dead_bits, m.dead_rank, hi) - dead_before(m.dead_bits, m.dead_rank, lo));
+}
+// an id handed out since the bulk load: the overlay node of its tenant if the topic is retained now, NONE otherwise ('$' topics count)
+BMQ_HD uint32_t census_topic_one(const RetainMut& m, uint32_t id) {
+    if (id >= m.id_cap || id_dead(m.dead_bits, id)) return NONE;
+    const uint32_t tn = m.id_tnode[id];
+    return tn == NONE ? NONE : (tn & ~ID_SYS);
+}
+// the census table holds a word per overlay node and only the tenant nodes can have a count: the non-zero entries go into a list
+// ((node << 32) | count, any order) on the executor's side, so that the host reads the list and never the table
+BMQ_HD void census_pick_one(const unsigned long long* table, uint32_t i, unsigned long long* list, uint32_t* count) {
+    const unsigned long long c = table[i];
+    if (c) list[atom_add(count, 1u)] = ((unsigned long long)i << 32) | c;
+}
+// labels of overlay nodes (the tenant ids of tenant nodes): lengths, then bytes at offs[i]
+BMQ_HD void ov_node_len_one(const RetainMut& m, const uint32_t* nodes, uint32_t i, uint32_t* lens) { lens[i] = m.onodes[nodes[i]].str_len & ~ON_SYS; }
+BMQ_HD void ov_node_write_one(const RetainMut& m, const uint32_t* nodes, uint32_t i, const unsigned long long* offs, uint8_t* out) {
+    const ONode& n = m.onodes[nodes[i]];
+    const uint32_t l = n.str_len & ~ON_SYS;
+    for (uint32_t k = 0; k < l; k++) out[offs[i] + k] = m.opool[n.str_off + k];
+}
+
 // re-insert overlay node i into a larger edge table (all nodes in parallel, after the table was cleared)
 BMQ_HD void ov_rehash_one(const RetainMut& m, uint32_t i) {
     if (i == 0) return;
     const ONode& n = m.onodes[i];
+    // A node that lost the race for its table slot (ov_child: "built for nothing") was never published: it hangs in no child list, no
+    // topic ends at it and nothing hangs below it.  It must not enter the new table -- it carries the same (parent, label) as the node
+    // that won, and a lookup that meets it first finds neither the topic nor the children.  (A batch of 50 k adds below one first level
+    // leaves thousands of them on the device; a published node always has a topic or a child.)
+    if (n.first_child == NONE && n.topic_id == NONE) return;
     uint32_t s = ov_slot(n.parent, n.h1, n.h2, m.oedge_mask);
     for (uint32_t probes = 0; probes <= m.oedge_mask; probes++) {
         if (atom_cas(&m.oedges[s], 0u, i) == 0u) return;

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "bmq_retain_core.h"
@@ -166,6 +167,92 @@ public:
         info.overlay_ids = hc.next_id - base_n;
         info.overlay_nodes = hc.ov_nodes - 1;
         info.batches++;
+        return true;
+    }
+
+    // ---- removal by id (remove_id_one): the ids are the engine's own, every one below info.id_bound (the caller checked).  One kernel over
+    // the ids and the rank directory, on the executor's stream behind whatever is in flight; removed = the topics that stopped being retained
+    bool remove_ids(const uint32_t* ids, uint32_t n, uint64_t& removed) {
+        error.clear();
+        removed = 0;
+        if (!ready) return fail("the retained-topic index has not been built");
+        if (n == 0) return true;
+        if (!ensure(q_buf, q_cap, 4 * (size_t)n)) return false;
+        if (!x.copy_in_async(q_buf, ids, 4 * (size_t)n)) return xfail();
+        if (!x.zero((uint8_t*)d_ctr + offsetof(RetainCounters, went_live), sizeof(RetainCounters) - offsetof(RetainCounters, went_live))) return xfail();
+        const RetainMut m = mut();
+        if (!x.r_remove_ids(m, (const uint32_t*)q_buf, n, (uint32_t)info.id_bound) || !x.r_rank(m, n_words())) return xfail();
+        if (!x.copy_out(&hc, d_ctr, sizeof(hc))) return xfail(); // waits for the kernels
+        uint64_t dead = 0, bdead = 0;
+        for (uint32_t k = 0; k < N_CTR_LANES; k++) dead += hc.went_dead[k], bdead += hc.base_went_dead[k];
+        info.n_live -= dead;
+        info.base_dead += bdead;
+        info.batches++;
+        removed = dead;
+        return true;
+    }
+
+    // the dead bitmap over the ids handed out: bit id set = not retained now
+    bool dead_words(std::vector<unsigned long long>& w) {
+        w.assign((size_t)(info.id_bound + 63) / 64 + 1, ~0ull);
+        if (!ready) return fail("the retained-topic index has not been built");
+        const size_t n = (size_t)(info.id_bound + 63) / 64;
+        return (n == 0 || x.copy_out(w.data(), d_dead, 8 * n)) ? true : xfail();
+    }
+
+    // ---- retained topics per tenant.  bulk: the (id_base, id_base + topics) rank range of every bulk-loaded tenant, in the order of
+    // bulk_live's entries; ov: (tenant id, live topics) of every tenant node of the overlay that has some
+    bool tenant_counts(const std::vector<uint32_t>& bulk_ranges, std::vector<uint32_t>& bulk_live, std::vector<std::pair<std::string, uint64_t>>& ov) {
+        error.clear();
+        const uint32_t nt = (uint32_t)(bulk_ranges.size() / 2);
+        bulk_live.assign(nt, 0);
+        ov.clear();
+        if (!ready) return fail("the retained-topic index has not been built");
+        const RetainMut m = mut();
+        if (nt) {
+            const size_t off_out = align16(8 * (size_t)nt);
+            if (!ensure(q_buf, q_cap, off_out + 4 * (size_t)nt)) return false;
+            if (!x.copy_in_async(q_buf, bulk_ranges.data(), 8 * (size_t)nt) || !x.r_census_bulk(m, (const uint32_t*)q_buf, nt, (uint32_t*)(q_buf + off_out)) ||
+                !x.copy_out(bulk_live.data(), q_buf + off_out, 4 * (size_t)nt))
+                return xfail();
+        }
+        if (info.overlay_ids == 0) return true;
+        // a counter per overlay node (zeroed and filled on the executor's side), then the non-zero entries as a list: the host reads the
+        // list -- one entry per tenant -- and never the table, however many nodes the overlay has
+        const uint32_t n_nodes = hc.ov_nodes;
+        const size_t off_list = 8 * (size_t)n_nodes, off_cnt = 2 * off_list;
+        if (!ensure(q_buf, q_cap, off_cnt + 16)) return false;
+        unsigned long long* d_table = (unsigned long long*)q_buf;
+        unsigned long long* d_list = (unsigned long long*)(q_buf + off_list);
+        uint32_t* d_cnt = (uint32_t*)(q_buf + off_cnt);
+        uint32_t n = 0;
+        if (!x.zero(d_table, off_list) || !x.zero(d_cnt, 16) || !x.r_census(m, (uint32_t)info.id_bound, d_table) || !x.r_census_pick(d_table, n_nodes, d_list, d_cnt) ||
+            !x.copy_out(&n, d_cnt, 4))
+            return xfail();
+        if (n == 0) return true;
+        std::vector<unsigned long long> picked(n);
+        if (!x.copy_out(picked.data(), d_list, 8 * (size_t)n)) return xfail();
+        std::sort(picked.begin(), picked.end());
+        std::vector<uint32_t> nodes(n);
+        std::vector<unsigned long long> table_of(n);
+        for (uint32_t i = 0; i < n; i++) nodes[i] = (uint32_t)(picked[i] >> 32), table_of[i] = picked[i] & 0xFFFFFFFFull;
+        // the tenant ids: labels of the tenant nodes, from the overlay string pool
+        const size_t off_len = align16(4 * (size_t)n), off_off = align16(off_len + 4 * (size_t)n);
+        if (!ensure(q_buf, q_cap, off_off + 8 * ((size_t)n + 1))) return false;
+        std::vector<uint32_t> lens(n);
+        if (!x.copy_in_async(q_buf, nodes.data(), 4 * (size_t)n) || !x.r_node_lens(m, (const uint32_t*)q_buf, n, (uint32_t*)(q_buf + off_len)) ||
+            !x.copy_out(lens.data(), q_buf + off_len, 4 * (size_t)n))
+            return xfail();
+        std::vector<unsigned long long> offs((size_t)n + 1, 0);
+        for (uint32_t i = 0; i < n; i++) offs[i + 1] = offs[i] + lens[i];
+        std::vector<uint8_t> bytes(offs[n] + 1);
+        if (offs[n]) {
+            if (!ensure(o_buf, o_cap, offs[n] + 16)) return false;
+            if (!x.copy_in_async(q_buf + off_off, offs.data(), 8 * ((size_t)n + 1)) ||
+                !x.r_node_write(m, (const uint32_t*)q_buf, n, (const unsigned long long*)(q_buf + off_off), o_buf) || !x.copy_out(bytes.data(), o_buf, offs[n]))
+                return xfail();
+        }
+        for (uint32_t i = 0; i < n; i++) ov.emplace_back(std::string((const char*)bytes.data() + offs[i], lens[i]), table_of[i]);
         return true;
     }
 

@@ -591,6 +591,148 @@ int bmq_retain_topic(const bmq_engine* ce, uint32_t topic_id, uint8_t* out, uint
     return BMQ_OK;
 }
 
+// liveness of ids: the dead bitmap over the ids handed out (a bit per id: 128 KB per million ids), one copy
+static int retain_dead_words_locked(bmq_engine* e, std::vector<unsigned long long>& words) {
+    const bool ok = with_retain(e, [&](auto& rt) {
+        const bool r = rt.dead_words(words);
+        if (!r) e->err = rt.error;
+        return r;
+    });
+    return ok ? BMQ_OK : set_err(e, BMQ_E_HIP, e->err);
+}
+
+int bmq_retain_message_keys(const bmq_engine* ce, const uint32_t* topic_ids, uint32_t n, uint8_t* out, uint64_t cap, uint64_t* out_off) {
+    bmq_engine* e = const_cast<bmq_engine*>(ce);
+    std::unique_lock<std::recursive_mutex> api_lock;
+    if (e) api_lock = std::unique_lock<std::recursive_mutex>(e->api);
+    if (!e || !out_off || (n && !topic_ids)) return BMQ_E_INVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    std::vector<uint64_t> koff((size_t)n + 1, 0);
+    std::vector<uint8_t> keys;
+    if (e->rbuilt && n) {
+        std::vector<unsigned long long> dead;
+        if (int rc = retain_dead_words_locked(e, dead)) return rc;
+        const uint64_t bound = e->drt ? e->drt->info.id_bound : e->hrt->info.id_bound;
+        std::vector<uint32_t> live; // (positions keep their order: the keys are composed id for id below)
+        for (uint32_t i = 0; i < n; i++)
+            if (topic_ids[i] < bound && !((dead[topic_ids[i] >> 6] >> (topic_ids[i] & 63u)) & 1ull)) live.push_back(topic_ids[i]);
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> off;
+        std::vector<uint32_t> tlen;
+        if (int rc = retain_topics_locked(e, live.data(), (uint32_t)live.size(), bytes, off, tlen)) return rc;
+        size_t k = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            if (k < live.size() && topic_ids[i] < bound && !((dead[topic_ids[i] >> 6] >> (topic_ids[i] & 63u)) & 1ull)) {
+                const std::string_view tn((const char*)bytes.data() + off[k], tlen[k]), tp((const char*)bytes.data() + off[k] + tlen[k], (size_t)(off[k + 1] - off[k]) - tlen[k]);
+                if (off[k + 1] != off[k]) {
+                    const std::string key = retain_message_key(tn, tp);
+                    keys.insert(keys.end(), key.begin(), key.end());
+                }
+                k++;
+            }
+            koff[i + 1] = keys.size();
+        }
+    }
+    memcpy(out_off, koff.data(), sizeof(uint64_t) * ((size_t)n + 1));
+    if (koff[n] > cap || (koff[n] && !out)) return set_err(e, BMQ_E_NOSPACE, "output buffer too small");
+    if (koff[n]) memcpy(out, keys.data(), koff[n]);
+    return BMQ_OK;
+}
+
+int bmq_retain_remove_ids(bmq_engine* e, const uint32_t* topic_ids, uint32_t n, uint64_t generation, uint64_t* out_removed) {
+    std::unique_lock<std::recursive_mutex> api_lock;
+    if (e) api_lock = std::unique_lock<std::recursive_mutex>(e->api);
+    if (!e || (n && !topic_ids)) return BMQ_E_INVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (out_removed) *out_removed = 0;
+    if (!e->rbuilt || generation != e->rgeneration) return set_err(e, BMQ_E_STATE, "the topic ids belong to another generation of the retained-topic index");
+    const uint64_t bound = e->drt ? e->drt->info.id_bound : e->hrt->info.id_bound;
+    for (uint32_t i = 0; i < n; i++) // nothing is changed by a call that holds an id nobody handed out
+        if (topic_ids[i] >= bound) return set_err(e, BMQ_E_INVAL, "topic id out of range (>= bmq_retain_info.id_bound)");
+    if (n == 0) return BMQ_OK;
+    if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
+    // a generation is being built beside this one: it gets the removals as remove ops of the topics.  The ops are made ready here (the ids
+    // that are live now, once each, with their strings) and enter the log only after the removal has succeeded, as in retain_apply_common
+    std::vector<bmq_engine::RetainCompaction::Op> log_ops;
+    uint64_t log_ops_bytes = 0;
+    if (e->rcmp.active && !e->rcmp.log_overflow) {
+        std::vector<unsigned long long> dead;
+        if (int rc = retain_dead_words_locked(e, dead)) return rc;
+        std::vector<uint32_t> live;
+        for (uint32_t i = 0; i < n; i++) {
+            const uint32_t id = topic_ids[i];
+            if ((dead[id >> 6] >> (id & 63u)) & 1ull) continue;
+            dead[id >> 6] |= 1ull << (id & 63u); // (a repeat inside the call is logged once)
+            live.push_back(id);
+        }
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> off;
+        std::vector<uint32_t> tlen;
+        if (int rc = retain_topics_locked(e, live.data(), (uint32_t)live.size(), bytes, off, tlen)) return rc;
+        for (size_t i = 0; i < live.size(); i++) {
+            bmq_engine::RetainCompaction::Op o;
+            o.tenant.assign((const char*)bytes.data() + off[i], tlen[i]);
+            o.topic.assign((const char*)bytes.data() + off[i] + tlen[i], (size_t)(off[i + 1] - off[i]) - tlen[i]);
+            o.op = 1;
+            o.has_ts = false;
+            o.ts = 0ull;
+            o.expiry = 0xFFFFFFFFu;
+            log_ops_bytes += o.tenant.size() + o.topic.size() + 48;
+            log_ops.push_back(std::move(o));
+        }
+    }
+    uint64_t removed = 0;
+    const bool ok = with_retain(e, [&](auto& rt) {
+        const bool r = rt.remove_ids(topic_ids, n, removed);
+        if (!r) e->err = rt.error;
+        return r;
+    });
+    if (!ok) return set_err(e, e->err.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : BMQ_E_HIP, e->err);
+    if (e->rcmp.active && !e->rcmp.log_overflow) {
+        bmq_engine::RetainCompaction& c = e->rcmp;
+        c.log_bytes += log_ops_bytes;
+        for (auto& o : log_ops) c.log.push_back(std::move(o));
+        if (c.log_bytes > (1ull << 30)) { // (what gives way is the compaction, never the mutation)
+            c.log_overflow = true;
+            c.log.clear(), c.log.shrink_to_fit();
+        }
+    }
+    if (out_removed) *out_removed = removed;
+    e->repoch++;
+    return BMQ_OK;
+}
+
+int bmq_retain_tenant_counts(const bmq_engine* ce, uint8_t* out_tenants, uint64_t tenants_cap, uint64_t* out_tenant_off, uint64_t* out_counts, uint32_t cap,
+                             uint32_t* out_n_tenants, uint64_t* out_tenant_bytes) {
+    bmq_engine* e = const_cast<bmq_engine*>(ce);
+    std::unique_lock<std::recursive_mutex> api_lock;
+    if (e) api_lock = std::unique_lock<std::recursive_mutex>(e->api);
+    if (!e) return BMQ_E_INVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    std::map<std::string, uint64_t> merged; // byte order of the tenant ids; a tenant with both parts comes out once
+    if (e->rbuilt) {
+        if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
+        std::vector<uint32_t> ranges, bulk_live;
+        for (const RTenantState* t : e->rhost.order) {
+            ranges.push_back(t->id_base);
+            ranges.push_back(t->id_base + (uint32_t)t->topics.size());
+        }
+        std::vector<std::pair<std::string, uint64_t>> ov;
+        const bool ok = with_retain(e, [&](auto& rt) {
+            const bool r = rt.tenant_counts(ranges, bulk_live, ov);
+            if (!r) e->err = rt.error;
+            return r;
+        });
+        if (!ok) return set_err(e, BMQ_E_HIP, e->err);
+        for (size_t i = 0; i < e->rhost.order.size(); i++)
+            if (bulk_live[i]) merged[e->rhost.order[i]->name] += bulk_live[i];
+        for (auto& o : ov) merged[o.first] += o.second;
+    }
+    std::vector<std::pair<std::string, std::array<uint64_t, 4>>> rows;
+    for (auto& m : merged) rows.push_back({m.first, {m.second, 0, 0, 0}});
+    return pack_names(e, rows, 1, out_tenants, tenants_cap, out_tenant_off, out_counts, cap, out_n_tenants, out_tenant_bytes);
+}
+
 // Maintenance: merge what bmq_retain_apply* changed into a fresh bulk load -- removed topics and their ids go, overlay topics become
 // ranks again (every subtree one id range: the fast path of '+' and '#').  A new generation of ids.
 // the live retained topics with their stamps, as bmq_retain_rebuild_ex takes them (under e->mu)

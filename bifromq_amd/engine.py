@@ -312,6 +312,25 @@ class Engine:
         self._check(_lib.lib().bmq_routes_count_in(self.h, *self._boundary(start, end), C.byref(routes), C.byref(key_bytes)))
         return int(routes.value), int(key_bytes.value)
 
+    def _named_numbers(self, call, width: int, tenants_cap: int = 4096, cap: int = 256):
+        """the buffer protocol of bmq_routes_tenant_stats / bmq_retain_tenant_counts: caps in, needed sizes out, -3 when a cap is too small"""
+        n, nb = C.c_uint32(), C.c_uint64()
+        while True:
+            names, off, nums = np.zeros(max(tenants_cap, 1), dtype=np.uint8), np.zeros(cap + 1, dtype=np.uint64), np.zeros(max(width * cap, 1), dtype=np.uint64)
+            rc = call(_ptr(names), tenants_cap, _ptr(off), _ptr(nums), cap, C.byref(n), C.byref(nb))
+            if rc == -3:
+                cap, tenants_cap = max(cap, int(n.value)), max(tenants_cap, int(nb.value))
+                continue
+            self._check(rc)
+            raw = names.tobytes()
+            return [(raw[int(off[i]):int(off[i + 1])],) + tuple(int(v) for v in nums[width * i:width * (i + 1)]) for i in range(n.value)]
+
+    def routes_tenant_stats(self, start=None, end=None, tenants_cap: int = 4096, cap: int = 256) -> List[Tuple[bytes, int, int, int, int]]:
+        """bmq_routes_tenant_stats: [(tenant id bytes, normal, unordered share, ordered share, key_bytes)] of every tenant with a live route
+        inside the boundary, in byte order of the ids; the index is not changed"""
+        b = self._boundary(start, end)
+        return self._named_numbers(lambda *a: _lib.lib().bmq_routes_tenant_stats(self.h, *b, *a), 4, tenants_cap, cap)
+
     def import_routes(self, src: "Engine", start=None, end=None) -> Tuple[int, int]:
         """bmq_routes_import: every live key of src inside the boundary is put into this engine, without a KV scan -> (imported, dups)"""
         imported, dups = C.c_uint64(), C.c_uint64()
@@ -749,6 +768,33 @@ class Engine:
             self._check(rc)
             raw = out.tobytes()
             return [(raw[int(off[i]):int(off[i]) + int(tl[i])].decode(), raw[int(off[i]) + int(tl[i]):int(off[i + 1])].decode()) for i in range(n)]
+
+    def retain_tenant_counts(self, tenants_cap: int = 4096, cap: int = 256) -> List[Tuple[bytes, int]]:
+        """bmq_retain_tenant_counts: [(tenant id bytes, retained topics now)] in byte order of the ids ('$' topics included)"""
+        return self._named_numbers(lambda *a: _lib.lib().bmq_retain_tenant_counts(self.h, *a), 1, tenants_cap, cap)
+
+    def retain_remove_ids(self, topic_ids, generation: int) -> int:
+        """bmq_retain_remove_ids: the post-commit half of the GC, by id -> topics removed (dead ids and repeats are no-ops)"""
+        ids = np.ascontiguousarray(topic_ids, dtype=np.uint32)
+        removed = C.c_uint64()
+        self._check(_lib.lib().bmq_retain_remove_ids(self.h, _ptr(ids) if len(ids) else None, len(ids), generation, C.byref(removed)))
+        return int(removed.value)
+
+    def retain_message_keys(self, topic_ids) -> List[bytes]:
+        """bmq_retain_message_keys: retainMessageKey(tenant, topic) per id (b"" for an id that is unknown or not retained now)"""
+        ids = np.ascontiguousarray(topic_ids, dtype=np.uint32)
+        n = len(ids)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        cap = max(4096, 96 * n)
+        while True:
+            out = np.zeros(cap, dtype=np.uint8)
+            rc = _lib.lib().bmq_retain_message_keys(self.h, _ptr(ids) if n else None, n, _ptr(out), cap, _ptr(off))
+            if rc == -3:
+                cap = int(off[n]) + 16
+                continue
+            self._check(rc)
+            raw = out.tobytes()
+            return [raw[int(off[i]):int(off[i + 1])] for i in range(n)]
 
     def retain_topic_info(self, topic_id: int) -> Tuple[int, int, int]:
         """-> (timestamp_hlc, expiry_seconds, expire_at_ms)"""

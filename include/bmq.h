@@ -225,6 +225,30 @@ int bmq_compact_begin_in(bmq_engine* e, uint8_t flags, const uint8_t* start, uin
 int bmq_routes_import(bmq_engine* dst, bmq_engine* src, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end,
                       uint32_t end_len, uint64_t* out_imported /* may be NULL */, uint64_t* out_dups /* may be NULL */);
 
+/* ---- per-tenant statistics of the route index, without a KV scan ---------------------------------------------------------------------
+ * TenantsStats.doReset walks every key of the range on every reset and counts, per tenant, normal routes and shared routes from the key's
+ * flag (bifromq-dist/bifromq-dist-worker/.../TenantsStats.java:229-246); the tenant's space gauge asks reader.size(tenantSection)
+ * (:140-162).  bmq_routes_tenant_stats answers both from the keys the engine holds: ONE read-only pass of the census kernel over the key
+ * references (no scratch copy; a wave reduces its lanes per tenant before it adds), whatever the number of tenants.
+ *
+ * Boundary arguments as for bmq_routes_count_in (flags = 0: everything).  For every tenant with at least one live route inside the
+ * boundary, in unsigned byte order of the tenant ids (a proper prefix first): its id bytes, packed into out_tenants with out_tenant_off
+ * [n + 1], and four numbers in out_stats[4 i ..]: live keys with flag 1 (normal), 2 (unordered share), 3 (ordered share), and key_bytes,
+ * the sum of their key lengths.  A tenant with nothing inside is left out (TenantsStats destroys an entry at isNoRoutes).  A shared-
+ * subscription key counts ONCE (doReset: doAddSharedRoutes(tenantId, 1) per key); member counts live in the KV value, which the engine
+ * does not hold.  key_bytes against reader.size: KEYS ONLY -- the caller adds the 8-byte value of every normal route.
+ * Over the full boundary a tenant's three counts sum to its live routes and all tenants to bmq_index_info.n_routes; over any boundary the
+ * sums equal bmq_routes_count_in's routes and bytes.
+ *
+ * Buffers: `cap` = tenants out_tenant_off (cap + 1 entries) and out_stats (4 * cap entries) have room for, tenants_cap = bytes of
+ * out_tenants.  *out_n_tenants and *out_tenant_bytes (either may be NULL) always receive the needed sizes; BMQ_E_NOSPACE when a cap is too
+ * small (offsets and numbers are still written when `cap` suffices).
+ * Locks and state as bmq_routes_count_in: an open bmq_routes_apply_async batch is completed first; while a compaction runs the SERVING
+ * generation is read, after the swap the new one; nothing is changed and the persistent matcher keeps running. */
+int bmq_routes_tenant_stats(const bmq_engine* e, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len,
+                            uint8_t* out_tenants, uint64_t tenants_cap, uint64_t* out_tenant_off, uint64_t* out_stats, uint32_t cap,
+                            uint32_t* out_n_tenants /* may be NULL */, uint64_t* out_tenant_bytes /* may be NULL */);
+
 int bmq_index_info_get(const bmq_engine* e, bmq_index_info* out);
 /* id -> key (so the Java adapter can materialise Matching objects, SCHEMA/KVSchemaUtil.java:73-89).  BMQ_E_INVAL: no such
  * route (the id was never handed out, or its route has been deleted). */
@@ -859,6 +883,31 @@ int bmq_retain_topic_info(const bmq_engine* e, uint32_t topic_id, uint64_t* out_
  * ones too) or, tenant == NULL, of all.  Writes up to cap ids, *out_n = total; BMQ_E_NOSPACE if cap was too small. */
 int bmq_retain_find_all(const bmq_engine* e, uint64_t* out_n_topics, uint64_t* out_epoch);
 int bmq_retain_live_ids(const bmq_engine* e, const uint8_t* tenant, uint32_t tenant_len, uint32_t* out_ids, uint32_t cap, uint32_t* out_n);
+/* Retained topics per tenant, without a KV scan: RetainStoreCoProc.load() counts them while it scans (RS/RetainStoreCoProc.java:279-296,
+ * tenantsStats.increaseTopicCount per key -- '$' topics included).  Every tenant with at least one retained topic NOW, in unsigned byte
+ * order of the ids, with its count in out_counts[i]; the counts sum to bmq_retain_info.n_topics.  Bulk-loaded tenants: size of the
+ * tenant's rank range minus the dead ids inside (the rank directory: no pass over the ids); ids handed out since the load: one pass of
+ * the census kernel; a tenant with both parts comes out once, with the sum.  Buffer protocol of bmq_routes_tenant_stats (one number per
+ * tenant). */
+int bmq_retain_tenant_counts(const bmq_engine* e, uint8_t* out_tenants, uint64_t tenants_cap, uint64_t* out_tenant_off, uint64_t* out_counts,
+                             uint32_t cap, uint32_t* out_n_tenants /* may be NULL */, uint64_t* out_tenant_bytes /* may be NULL */);
+/* The two native halves of RetainStoreCoProc.gc around the KV commit (RS/RetainStoreCoProc.java:258-277), for ids the engine handed out
+ * (bmq_retain_expired, bmq_retain_live_ids, a match):
+ *   bmq_retain_message_keys  out_off[n + 1] / out: retainMessageKey(tenant, topic) of every id (the keys gc deletes and match gets with
+ *                            reader.get), equal to bmq_retain_message_key of bmq_retain_topics id for id; EMPTY for an id that is unknown
+ *                            or not retained now.  Host code under one engine lock.  BMQ_E_NOSPACE if cap < out_off[n] (offsets are
+ *                            still written).
+ *   bmq_retain_remove_ids    the post-commit index removal (:270-275) BY ID: every live id goes dead exactly as a remove op of
+ *                            bmq_retain_apply_batch leaves it (dead bit, expire_at = 0, the counts behind bmq_retain_info), then the
+ *                            rank directory is rebuilt -- one kernel over the ids, nothing is looked up level by level -- on the engine
+ *                            stream behind batches in flight.  Ids that are dead already and repeats inside the call are no-ops;
+ *                            *out_removed (may be NULL) = topics removed.  `generation` = bmq_retain_info.generation the ids belong to:
+ *                            BMQ_E_STATE if it has changed; BMQ_E_INVAL if any id is >= id_bound (checked before anything changes).
+ *                            The epoch advances as after bmq_retain_apply_batch; a later add of the same topic gets the same id back.
+ *                            Between bmq_retain_compact_begin and _swap the removals enter the compaction log as remove ops of the
+ *                            topics' strings, so the swap replays them (the log cap applies). */
+int bmq_retain_message_keys(const bmq_engine* e, const uint32_t* topic_ids, uint32_t n, uint8_t* out, uint64_t cap, uint64_t* out_off);
+int bmq_retain_remove_ids(bmq_engine* e, const uint32_t* topic_ids, uint32_t n, uint64_t generation, uint64_t* out_removed /* may be NULL */);
 /* The scan of RetainStoreCoProc's GC (RS/RetainStoreCoProc.java:257-277): ids (ascending) of the retained topics whose message has
  * expired at now_ms (expireTime <= now) -- of every tenant (tenant == NULL: the reference's findAll() branch), or of `tenant`: there the
  * reference scans index.match(tenantId, "#"), which does not reach topics whose first level starts with '$'

@@ -1,5 +1,6 @@
 /* bmq_jni.c -- the JNI binding a bifromq maintainer adds to put libbmq.so behind the dist worker's match path
- * (INTEGRATION.md).  Java side: integration/java/org/apache/bifromq/dist/worker/gpu/NativeMatcher.java.
+ * (INTEGRATION.md).  Java side: integration/java/org/apache/bifromq/dist/worker/gpu/NativeMatcher.java and, for the per-tenant
+ * statistics and the retain GC by id, integration/java/org/apache/bifromq/retain/store/gpu/NativeStore.java (the same engine handle).
  *
  * Conventions: every buffer is a DIRECT ByteBuffer / IntBuffer in native byte order (zero copy, GetDirectBufferAddress);
  * tenant ids travel as byte[] (short, copied).  A method returning "long" gives the number of ids written, or -(needed) when
@@ -23,6 +24,8 @@
 /* GetDirectBufferCapacity counts ELEMENTS of the buffer's type: bytes for a ByteBuffer, ints for an IntBuffer */
 #define CAP(o) ((o) ? (uint64_t)(*env)->GetDirectBufferCapacity(env, (o)) : 0u)
 #define NM(name) Java_org_apache_bifromq_dist_worker_gpu_NativeMatcher_##name
+/* the statistics and the GC by id of both co-processors: integration/java/org/apache/bifromq/retain/store/gpu/NativeStore.java */
+#define NS(name) Java_org_apache_bifromq_retain_store_gpu_NativeStore_##name
 
 static void throw_state(JNIEnv* env, bmq_engine* e, const char* what, int rc) {
     char msg[512];
@@ -480,6 +483,92 @@ JNIEXPORT jlong JNICALL NM(retainLiveIds)(JNIEnv* env, jclass c, jlong h, jbyteA
     const int rc = bmq_retain_live_ids(ENGINE(h), (const uint8_t*)tn, (uint32_t)tl, (uint32_t*)ADDR(outIds), (uint32_t)CAP(outIds), &n);
     if (tenant) (*env)->ReleaseByteArrayElements(env, tenant, tn, JNI_ABORT);
     return result_of(env, ENGINE(h), "bmq_retain_live_ids", rc, n);
+}
+/* long retainExpired(long engine, byte[] tenant (null: all tenants), long nowMs, long overrideExpirySeconds (< 0: none), IntBuffer outIds)
+ * the scan of RetainStoreCoProc.gc on the device -> number of expired topics, or -(needed) */
+JNIEXPORT jlong JNICALL NS(retainExpired)(JNIEnv* env, jclass c, jlong h, jbyteArray tenant, jlong nowMs, jlong overrideExpirySeconds, jobject outIds) {
+    (void)c;
+    jsize tl = tenant ? (*env)->GetArrayLength(env, tenant) : 0;
+    jbyte* tn = tenant ? (*env)->GetByteArrayElements(env, tenant, NULL) : NULL;
+    uint32_t n = 0;
+    const int rc = bmq_retain_expired(ENGINE(h), (const uint8_t*)tn, (uint32_t)tl, (uint64_t)nowMs, (int64_t)overrideExpirySeconds, (uint32_t*)ADDR(outIds),
+                                      (uint32_t)CAP(outIds), &n);
+    if (tenant) (*env)->ReleaseByteArrayElements(env, tenant, tn, JNI_ABORT);
+    return result_of(env, ENGINE(h), "bmq_retain_expired", rc, n);
+}
+/* long retainGeneration(long engine)     bmq_retain_info.generation: the generation topic ids belong to (read it BEFORE the scan whose ids go to retainRemoveIds) */
+JNIEXPORT jlong JNICALL NS(retainGeneration)(JNIEnv* env, jclass c, jlong h) {
+    (void)c;
+    bmq_retain_info info;
+    const int rc = bmq_retain_info_get(ENGINE(h), &info);
+    if (rc != BMQ_OK) {
+        throw_state(env, ENGINE(h), "bmq_retain_info_get", rc);
+        return 0;
+    }
+    return (jlong)info.generation;
+}
+/* long retainMessageKeys(long engine, IntBuffer ids, int n, ByteBuffer out, LongBuffer outOff)    retainMessageKey(tenant, topic) of every id:
+ * the keys gc deletes and match gets; outOff[n + 1] byte offsets into out, an id that is unknown or not retained now gives an empty key;
+ * -> bytes, or -(needed) */
+JNIEXPORT jlong JNICALL NS(retainMessageKeys)(JNIEnv* env, jclass c, jlong h, jobject ids, jint n, jobject out, jobject outOff) {
+    (void)c;
+    uint64_t* off = (uint64_t*)ADDR(outOff);
+    const int rc = bmq_retain_message_keys(ENGINE(h), (const uint32_t*)ADDR(ids), (uint32_t)n, (uint8_t*)ADDR(out), CAP(out), off);
+    return result_of(env, ENGINE(h), "bmq_retain_message_keys", rc, off ? off[n] : 0);
+}
+/* long retainRemoveIds(long engine, IntBuffer ids, int n, long generation)     the post-commit half of gc, by id -> topics removed; throws if the
+ * generation has changed (the ids belong to the one before) or an id was never handed out */
+JNIEXPORT jlong JNICALL NS(retainRemoveIds)(JNIEnv* env, jclass c, jlong h, jobject ids, jint n, jlong generation) {
+    (void)c;
+    uint64_t removed = 0;
+    const int rc = bmq_retain_remove_ids(ENGINE(h), (const uint32_t*)ADDR(ids), (uint32_t)n, (uint64_t)generation, &removed);
+    if (rc != BMQ_OK) {
+        throw_state(env, ENGINE(h), "bmq_retain_remove_ids", rc);
+        return 0;
+    }
+    return (jlong)removed;
+}
+/* out[0] = tenants, out[1] = bytes of their ids: what the census calls need (also when they return -1: a buffer was too small) */
+static jlong census_result(JNIEnv* env, bmq_engine* e, const char* what, int rc, uint32_t n, uint64_t bytes, jlongArray needed) {
+    const jlong v[2] = {(jlong)n, (jlong)bytes};
+    if (needed) (*env)->SetLongArrayRegion(env, needed, 0, 2, v);
+    if (rc == BMQ_E_NOSPACE) return -1;
+    if (rc != BMQ_OK) {
+        throw_state(env, e, what, rc);
+        return 0;
+    }
+    return (jlong)n;
+}
+/* long routesTenantStats(long engine, byte[] start (null: none), byte[] end (null: none), ByteBuffer outTenants, LongBuffer outTenantOff,
+ *                        LongBuffer outStats, long[] needed)
+ * the census TenantsStats.doReset takes by walking the range: per tenant with a live route inside the boundary, in byte order of the ids,
+ * outStats[4 i ..] = {normal, unordered share, ordered share, key bytes}; -> tenants, or -1 with needed = {tenants, id bytes} */
+JNIEXPORT jlong JNICALL NS(routesTenantStats)(JNIEnv* env, jclass c, jlong h, jbyteArray start, jbyteArray end, jobject outTenants, jobject outTenantOff,
+                                              jobject outStats, jlongArray needed) {
+    (void)c;
+    jsize sl = start ? (*env)->GetArrayLength(env, start) : 0, el = end ? (*env)->GetArrayLength(env, end) : 0;
+    jbyte* sb = start ? (*env)->GetByteArrayElements(env, start, NULL) : NULL;
+    jbyte* eb = end ? (*env)->GetByteArrayElements(env, end, NULL) : NULL;
+    uint64_t cap = CAP(outStats) / 4, bytes = 0;
+    if (CAP(outTenantOff) < cap + 1) cap = CAP(outTenantOff) ? CAP(outTenantOff) - 1 : 0;
+    uint32_t n = 0;
+    const int rc = bmq_routes_tenant_stats(ENGINE(h), (uint8_t)((start ? 1 : 0) | (end ? 2 : 0)), (const uint8_t*)sb, (uint32_t)sl, (const uint8_t*)eb, (uint32_t)el,
+                                           (uint8_t*)ADDR(outTenants), CAP(outTenants), (uint64_t*)ADDR(outTenantOff), (uint64_t*)ADDR(outStats), (uint32_t)cap, &n,
+                                           &bytes);
+    if (start) (*env)->ReleaseByteArrayElements(env, start, sb, JNI_ABORT);
+    if (end) (*env)->ReleaseByteArrayElements(env, end, eb, JNI_ABORT);
+    return census_result(env, ENGINE(h), "bmq_routes_tenant_stats", rc, n, bytes, needed);
+}
+/* long retainTenantCounts(long engine, ByteBuffer outTenants, LongBuffer outTenantOff, LongBuffer outCounts, long[] needed)
+ * retained topics per tenant, in byte order of the ids; -> tenants, or -1 with needed = {tenants, id bytes} */
+JNIEXPORT jlong JNICALL NS(retainTenantCounts)(JNIEnv* env, jclass c, jlong h, jobject outTenants, jobject outTenantOff, jobject outCounts, jlongArray needed) {
+    (void)c;
+    uint64_t cap = CAP(outCounts), bytes = 0;
+    if (CAP(outTenantOff) < cap + 1) cap = CAP(outTenantOff) ? CAP(outTenantOff) - 1 : 0;
+    uint32_t n = 0;
+    const int rc = bmq_retain_tenant_counts(ENGINE(h), (uint8_t*)ADDR(outTenants), CAP(outTenants), (uint64_t*)ADDR(outTenantOff), (uint64_t*)ADDR(outCounts),
+                                            (uint32_t)cap, &n, &bytes);
+    return census_result(env, ENGINE(h), "bmq_retain_tenant_counts", rc, n, bytes, needed);
 }
 /* void retainTopicInfo(long engine, int topicId, long[] out)     out = {timestampHlc, expirySeconds, expireAtMs} */
 JNIEXPORT void JNICALL NM(retainTopicInfo)(JNIEnv* env, jclass c, jlong h, jint id, jlongArray out) {

@@ -8,12 +8,13 @@
 //     topics and compared with a brute-force application of the matching rule of SURVEY.md 8a-0 to every key of the model;
 //   * tiny initial capacities (BMQ_FUZZ_SMALL, default on) force region growth, dictionary growth, id-list pool growth,
 //     directory growth and key-store growth all the time.
-//   * every third round a random KV boundary: count_in against the model, a bounded generation change (reserve_like with the boundary,
+//   * every third round a random KV boundary: count_in and the per-tenant census (tenant_stats) against the model, a bounded generation change (reserve_like with the boundary,
 //     the boundary predicate on every chunk) and an import into a second index (import_refs: unknown tenants, duplicates) against the
 //     model's key set restricted to the boundary.
 // Build + run: make -C bifromq_amd/csrc fuzz   (tests/test_host.py runs short rounds)
 #include <cstdio>
 #include <algorithm>
+#include <array>
 #include <cstdlib>
 #include <map>
 #include <random>
@@ -220,7 +221,7 @@ int main(int argc, char** argv) {
     hx.threads = threads;
     DistIndex<HostExec> h(hx);
     h.tiny = getenv("BMQ_FUZZ_BIG") == nullptr;
-    uint64_t checks = 0, n_apply = 0, n_rebuild = 0, fo_pairs = 0, n_generations = 0, n_bounded = 0, n_imports = 0, plus_stat[2] = {0, 0};
+    uint64_t checks = 0, n_apply = 0, n_rebuild = 0, fo_pairs = 0, n_generations = 0, n_census = 0, n_bounded = 0, n_imports = 0, plus_stat[2] = {0, 0};
     Fanout<HostExec> fo(hx, h); // fan-out grouping (bmq_fanout.h) over the same index, kept across rebuilds and applies
     fo.initial_table = 4;       // 36 deliverer keys: the group table grows twice
     for (int round = 0; round < rounds; round++) {
@@ -455,6 +456,28 @@ int main(int argc, char** argv) {
                         (unsigned long long)cb, inside.size(), (unsigned long long)inside_bytes, h.error.c_str());
                 return 1;
             }
+            // the per-tenant census over the same boundary (bmq_routes_tenant_stats: DistIndex::tenant_stats, census_key_one -- what
+            // k_b_census runs per lane on the device) against the model's keys taken apart here: tenant from the front, flag from the back
+            {
+                std::map<std::string, std::array<uint64_t, 4>> want;
+                for (const std::string& k : inside) {
+                    const size_t tl = ((size_t)(uint8_t)k[1] << 8) | (uint8_t)k[2], rl = ((size_t)(uint8_t)k[k.size() - 2] << 8) | (uint8_t)k[k.size() - 1];
+                    auto& w = want[k.substr(3, tl)];
+                    w[(uint8_t)k[k.size() - 3 - rl] - 1]++;
+                    w[3] += k.size();
+                }
+                std::vector<DistIndex<HostExec>::TenantStat> got;
+                bool same = h.tenant_stats(bd, got) && got.size() == want.size();
+                auto it = want.begin();
+                for (size_t i = 0; same && i < got.size(); i++, ++it)
+                    same = got[i].tenant == it->first && got[i].n_normal == it->second[0] && got[i].n_unordered_share == it->second[1] &&
+                           got[i].n_ordered_share == it->second[2] && got[i].key_bytes == it->second[3];
+                if (!same) {
+                    fprintf(stderr, "round %d: the tenant census differs from the model (%zu tenants against %zu) (%s)\n", round, got.size(), want.size(), h.error.c_str());
+                    return 1;
+                }
+                n_census++;
+            }
             auto key_set = [&](DistIndex<HostExec>& ix, std::set<std::string>& got) {
                 DistIndexStats is;
                 ix.stats(is);
@@ -659,9 +682,9 @@ int main(int argc, char** argv) {
     DistIndexStats st;
     h.stats(st);
     printf("layout v3: %llu of the %llu nodes the checks discovered through a '+' edge below a non-root node lay beside their parent\n", (unsigned long long)plus_stat[0], (unsigned long long)plus_stat[1]);
-    printf("host_fuzz ok: seed %llu, %d rounds (%llu rebuilds, %llu applies, %llu generation changes, %llu bounded ones, %llu imports), %llu topic checks, final %zu routes, %llu nodes, %llu tokens, "
+    printf("host_fuzz ok: seed %llu, %d rounds (%llu rebuilds, %llu applies, %llu generation changes, %llu bounded ones, %llu imports, %llu tenant censuses), %llu topic checks, final %zu routes, %llu nodes, %llu tokens, "
            "%llu trie slots (%llu garbage), %llu id-list words (%llu garbage), %llu fan-out pairs grouped\n",
-           (unsigned long long)seed, rounds, (unsigned long long)n_rebuild, (unsigned long long)n_apply, (unsigned long long)n_generations, (unsigned long long)n_bounded, (unsigned long long)n_imports, (unsigned long long)checks, model.size(),
+           (unsigned long long)seed, rounds, (unsigned long long)n_rebuild, (unsigned long long)n_apply, (unsigned long long)n_generations, (unsigned long long)n_bounded, (unsigned long long)n_imports, (unsigned long long)n_census, (unsigned long long)checks, model.size(),
            (unsigned long long)st.n_nodes, (unsigned long long)st.n_tokens, (unsigned long long)st.trie_slots, (unsigned long long)st.trie_garbage_slots,
            (unsigned long long)st.id_list_words, (unsigned long long)st.id_list_garbage, (unsigned long long)fo_pairs);
     return 0;

@@ -7,7 +7,9 @@
 //     k_r_locate / k_r_commit / k_r_rank run, here on several host threads with minimal capacities (every growth path runs all the
 //     time).  After every batch: ids are stable (an untouched topic keeps its id, a re-added one gets its id back, a new one a fresh
 //     id), stamps are those of the last add, the image walk (dead ids dropped) + a walk over the overlay trie done the way the kernel
-//     does it equal the brute force, the GC scan and the live-id listing equal the model, overlay ids resolve to their strings.
+//     does it equal the brute force, the GC scan and the live-id listing equal the model, overlay ids resolve to their strings;
+//   * removal by id (remove_id_one: live ids, dead ones, repeats, the 64 ids of one word in one batch) interleaved with the batches and
+//     the compactions, and after every step the retained topics per tenant (census_bulk_one, census_topic_one) against the model.
 // Build + run: make -C bifromq_amd/csrc fuzz   (tests/test_host.py runs a short round of both builds)
 #include <algorithm>
 #include <cstdio>
@@ -216,7 +218,7 @@ int main(int argc, char** argv) {
     RetainDyn<HostExec> rt(hx);
     rt.tiny = true;
     RetainIndexView bview{};
-    uint64_t checks = 0, n_ops = 0, n_batches = 0;
+    uint64_t checks = 0, n_ops = 0, n_batches = 0, n_id_removals = 0;
     auto base_view = [&]() {
         RetainIndexView v{};
         v.nodes = h.nodes.data();
@@ -277,6 +279,26 @@ int main(int argc, char** argv) {
                 live[{std::string(tn), std::string(tp)}] = id;
                 ever[{std::string(tn), std::string(tp)}] = id;
             }
+        } else if (!ever.empty() && rnd(4) == 0) { // removal BY ID (bmq_retain_remove_ids: remove_id_one): live ids, dead ones, repeats
+            std::map<uint32_t, Key> by_id;
+            for (auto& kv : ever) by_id[kv.second] = kv.first;
+            std::vector<uint32_t> ids;
+            const size_t n = 1 + rnd(rnd(3) == 0 ? 700 : 70);
+            const uint32_t start = (uint32_t)rnd(rt.info.id_bound);
+            for (size_t i = 0; i < n; i++) {
+                const size_t how = rnd(8);
+                if (how < 4) ids.push_back((uint32_t)((start + i) % rt.info.id_bound)); // neighbours: the ids of one 64-id word in one batch
+                else if (how < 7 || ids.empty()) ids.push_back((uint32_t)rnd(rt.info.id_bound));
+                else ids.push_back(ids[rnd(ids.size())]);
+            }
+            uint64_t want = 0, removed = 0;
+            for (uint32_t id : ids) {
+                auto f = by_id.find(id);
+                if (f != by_id.end()) want += live.erase(f->second);
+            }
+            if (!rt.remove_ids(ids.data(), (uint32_t)ids.size(), removed)) FAIL("round %d: remove_ids failed: %s\n", round, rt.error.c_str());
+            if (removed != want) FAIL("round %d: remove_ids reports %llu topics removed, the model %llu\n", round, (unsigned long long)removed, (unsigned long long)want);
+            n_id_removals += want;
         } else { // one batch of adds / removes over several tenants, duplicates inside the batch included
             std::vector<std::string> tn_list;
             std::string tbytes, pbytes;
@@ -365,6 +387,18 @@ int main(int argc, char** argv) {
         uint64_t base_dead = 0;
         for (auto& kv : ever) base_dead += kv.second < h.n_topics && !live.count(kv.first);
         if (rt.info.base_dead != base_dead) FAIL("round %d: base_dead %llu != %llu\n", round, (unsigned long long)rt.info.base_dead, (unsigned long long)base_dead);
+        { // retained topics per tenant (bmq_retain_tenant_counts: census_bulk_one over the rank ranges + census_topic_one over the overlay ids)
+            std::vector<uint32_t> ranges, bulk_live;
+            for (const RTenantState* t : h.order) ranges.push_back(t->id_base), ranges.push_back(t->id_base + (uint32_t)t->topics.size());
+            std::vector<std::pair<std::string, uint64_t>> ov;
+            if (!rt.tenant_counts(ranges, bulk_live, ov)) FAIL("round %d: tenant_counts failed: %s\n", round, rt.error.c_str());
+            std::map<std::string, uint64_t> got, want;
+            for (size_t i = 0; i < h.order.size(); i++)
+                if (bulk_live[i]) got[h.order[i]->name] += bulk_live[i];
+            for (auto& o : ov) got[o.first] += o.second;
+            for (auto& kv : live) want[kv.first.first]++;
+            if (got != want) FAIL("round %d: tenant counts differ from the model (%zu tenants against %zu)\n", round, got.size(), want.size());
+        }
         std::vector<uint32_t> ids, want_ids;
         GcQuery q{};
         q.live_only = 1;
@@ -464,7 +498,7 @@ int main(int argc, char** argv) {
             }
         }
     }
-    printf("retain_fuzz ok: seed %llu, %d rounds, %u threads, %llu ops in %llu batches, %llu filter checks\n", (unsigned long long)seed, rounds, threads,
-           (unsigned long long)n_ops, (unsigned long long)n_batches, (unsigned long long)checks);
+    printf("retain_fuzz ok: seed %llu, %d rounds, %u threads, %llu ops in %llu batches, %llu topics removed by id, %llu filter checks\n", (unsigned long long)seed, rounds,
+           threads, (unsigned long long)n_ops, (unsigned long long)n_batches, (unsigned long long)n_id_removals, (unsigned long long)checks);
     return 0;
 }
