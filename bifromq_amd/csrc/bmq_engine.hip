@@ -292,9 +292,10 @@ int set_err(bmq_engine* e, int code, const std::string& msg) {
     return code;
 }
 
-int upload(bmq_engine* e, DevBuf& b, const void* src, size_t bytes) {
+// (s: the engine stream unless given)
+int upload(bmq_engine* e, DevBuf& b, const void* src, size_t bytes, hipStream_t s = nullptr) {
     HIPCHK(e, b.ensure(bytes ? bytes : 16));
-    if (bytes) HIPCHK(e, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, e->stream));
+    if (bytes) HIPCHK(e, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s ? s : e->stream));
     return BMQ_OK;
 }
 
@@ -389,8 +390,8 @@ int enqueue_ranges(bmq_engine* e, bmq_engine::BatchSlot& S, const BatchArgs& a) 
     return BMQ_OK;
 }
 
-int launch_dist(bmq_engine* e, bmq_engine::BatchSlot& S, BatchArgs& a) {
-    if (int rc = complete_apply(e)) return rc; // (an apply batch still open: the launch needs the index as it leaves it)
+// ---- launch_dist in four steps: the slot's buffers into the arguments, the heavy-block list, the de-duplication mode, the kernels ----
+int bind_slot(bmq_engine* e, bmq_engine::BatchSlot& S, BatchArgs& a) {
     a.ix = e->dix->view();
     a.tpw_shift = tpw_shift_for(a.n_topics);
     a.n_blocks = (a.n_topics + (1u << a.tpw_shift) - 1) >> a.tpw_shift;
@@ -423,9 +424,12 @@ int launch_dist(bmq_engine* e, bmq_engine::BatchSlot& S, BatchArgs& a) {
     }
     a.qcap = e->cfg.wave_queue_cap;
     a.pcap = e->cfg.wave_pair_cap;
-    a.rep = nullptr, a.visit_cnt = nullptr, a.dd_table = nullptr, a.dd_mask = 0, a.dd_gen = 0;
-    // k_expand's heavy blocks (bmq_batch_args.h): listed by whoever writes the per-block sums, expanded by four waves each.  Large batches only:
-    // a small one has no tail to speak of, and its waves own fewer than 64 rows.
+    return BMQ_OK;
+}
+
+// k_expand's heavy blocks (bmq_batch_args.h): listed by whoever writes the per-block sums, expanded by four waves each.  Large batches only:
+// a small one has no tail to speak of, and its waves own fewer than 64 rows.
+int size_heavy_list(bmq_engine* e, bmq_engine::BatchSlot& S, BatchArgs& a) {
     a.heavy_list = nullptr, a.heavy_cap = 0, a.split_ranges = a.split_ids = 0xFFFFFFFFu;
     if (a.tpw_shift == 6 && a.n_blocks >= 1024) {
         a.heavy_cap = a.n_blocks / EXPAND_HEAVY_DIV;
@@ -435,11 +439,16 @@ int launch_dist(bmq_engine* e, bmq_engine::BatchSlot& S, BatchArgs& a) {
         HIPCHK(e, S.b_heavy.ensure(sizeof(uint32_t) * a.heavy_cap));
         a.heavy_list = S.b_heavy.as<uint32_t>();
     }
-    const bool adj = a.n_topics >= e->dedup_min && e->dedup_sorted; // an ordered batch: equal rows are neighbours (bmq_dedup_adj_kernels.h)
-    BatchArgs a2{};  // adj: the dense batch of run heads the walk kernels run on
-    AdjArgs g{};
-    AdjFill gf{};
-    if (adj) {
+    return BMQ_OK;
+}
+
+// Which in-batch de-duplication the batch gets, with its buffers and arguments: DD_TABLE fills a's rep / visit_cnt / dd_*; DD_ADJ also the
+// dense batch of run heads the walk kernels run on (a2) and the arguments of the kernels around it (g, gf).  < 0: a bmq_status.
+enum { DD_NONE = 0, DD_TABLE = 1, DD_ADJ = 2 };
+int prepare_dedup(bmq_engine* e, bmq_engine::BatchSlot& S, BatchArgs& a, BatchArgs& a2, AdjArgs& g, AdjFill& gf) {
+    a.rep = nullptr, a.visit_cnt = nullptr, a.dd_table = nullptr, a.dd_mask = 0, a.dd_gen = 0;
+    if (a.n_topics < e->dedup_min) return DD_NONE;
+    if (e->dedup_sorted) { // an ordered batch: equal rows are neighbours (bmq_dedup_adj_kernels.h)
         const size_t n = a.n_topics, nb = a.n_blocks, n_super = ((nb - 1) >> SUPER_SHIFT) + 1;
         if (S.adj_cap == 0) S.adj_cap = 48 * n + 4096; // (a first guess: the scatter kernel asks for more -- ST_NEED_ADJ -- and the batch runs again)
         HIPCHK(e, S.b_visit.ensure(4 * n));
@@ -467,7 +476,9 @@ int launch_dist(bmq_engine* e, bmq_engine::BatchSlot& S, BatchArgs& a) {
         a2.topics = g.c_topics, a2.topic_off = g.c_off, a2.topic_tenant = g.c_tenant, a2.rep = g.c_rep;
         a2.pair_off = S.b_c_pair_off.as<uint32_t>(), a2.pair_cnt = S.b_c_pair_cnt.as<uint32_t>(), a2.route_cnt = S.b_c_route_cnt.as<uint32_t>();
         gf.drow = g.drow, gf.c_pair_off = a2.pair_off, gf.c_pair_cnt = a2.pair_cnt, gf.c_route_cnt = a2.route_cnt, gf.c_visit = a2.visit_cnt;
-    } else if (a.n_topics >= e->dedup_min) { // identical (tenant, topic) rows are walked once
+        return DD_ADJ;
+    }
+    { // identical (tenant, topic) rows are walked once
         uint32_t cap = 1024;
         while (cap < 2 * a.n_topics && cap < (1u << 31)) cap <<= 1;
         if (e->dd_table.cap < sizeof(unsigned long long) * cap) e->dd_gen = 0; // (a new table: to be zeroed)
@@ -484,6 +495,11 @@ int launch_dist(bmq_engine* e, bmq_engine::BatchSlot& S, BatchArgs& a) {
         a.rep = S.b_rep.as<uint32_t>(), a.visit_cnt = S.b_visit.as<uint32_t>();
         a.dd_table = e->dd_table.as<unsigned long long>(), a.dd_mask = cap - 1, a.dd_gen = e->dd_gen;
     }
+    return DD_TABLE;
+}
+
+int enqueue_dist(bmq_engine* e, bmq_engine::BatchSlot& S, BatchArgs& a, bool adj, const BatchArgs& a2, const AdjArgs& g,
+                 const AdjFill& gf) {
     const BatchArgs& w = adj ? a2 : a; // what the walk kernels run on
     hipStream_t s = e->stream;
     S.timed = e->kernel_events;
@@ -505,7 +521,7 @@ int launch_dist(bmq_engine* e, bmq_engine::BatchSlot& S, BatchArgs& a) {
         // k_walk<token table entries, stack items, range entries, MIXED>: the LDS geometry is a compile-time property (bmq_walk_kernel.h)
         const dim3 grid((a.debug_flags & 32u) ? ((a.n_blocks + 7u) / 8u) * 8u : a.n_blocks), block(64);
         S.ran_mixed = e->mixed_on;
-        const int g = e->walk_geom;
+        const int geom = e->walk_geom;
 #define BMQ_WALK_LAUNCH(...) BMQ_WALK_LAUNCH3(__VA_ARGS__)
 #define BMQ_WALK_LAUNCH3(TC, QC, PC)                                                       \
     do {                                                                                   \
@@ -515,7 +531,7 @@ int launch_dist(bmq_engine* e, bmq_engine::BatchSlot& S, BatchArgs& a) {
 #if BMQ_EXPERIMENTS
         if (a.debug_flags & 16u) hipLaunchKernelGGL(k_occ_probe, grid, block, 0, s, a); // (experiments: its census replaces k_walk's)
 #endif
-        if (g == 2) BMQ_WALK_LAUNCH(BMQ_WALK_GEOM_SMALLEST); // smallest lists: every overflow path runs all the time (tests)
+        if (geom == 2) BMQ_WALK_LAUNCH(BMQ_WALK_GEOM_SMALLEST); // smallest lists: every overflow path runs all the time (tests)
         else BMQ_WALK_LAUNCH(BMQ_WALK_GEOM_DEFAULT);
 #undef BMQ_WALK_LAUNCH
 #undef BMQ_WALK_LAUNCH3
@@ -551,6 +567,29 @@ int launch_dist(bmq_engine* e, bmq_engine::BatchSlot& S, BatchArgs& a) {
     S.last = a;
     S.pending = true;
     S.pending_kind = 0;
+    return BMQ_OK;
+}
+
+int launch_dist(bmq_engine* e, bmq_engine::BatchSlot& S, BatchArgs& a) {
+    int rc = complete_apply(e); // (an apply batch still open: the launch needs the index as it leaves it)
+    if (rc || (rc = bind_slot(e, S, a)) || (rc = size_heavy_list(e, S, a))) return rc;
+    BatchArgs a2{};
+    AdjArgs g{};
+    AdjFill gf{};
+    const int dd = prepare_dedup(e, S, a, a2, g, gf);
+    return dd < 0 ? dd : enqueue_dist(e, S, a, dd == DD_ADJ, a2, g, gf);
+}
+
+// the growth steps a finished batch can ask for in either direction (ST_NEED_PAIRS, ST_NEED_SORTLIST)
+int grow_pairs(bmq_engine* e, bmq_engine::BatchSlot& S) {
+    S.pair_cap = S.pair_cap * 2; // slices fill unevenly: double until every sub-allocator fits
+    if (S.pair_cap >= 0xFFFFFFFFull) return set_err(e, BMQ_E_RANGE, "matched-range buffer exceeds 2^32 entries");
+    HIPCHK(e, S.b_pairs.ensure(sizeof(MatchRange) * S.pair_cap));
+    return BMQ_OK;
+}
+int grow_sort_list(bmq_engine* e, bmq_engine::BatchSlot& S, uint32_t sort_count) {
+    S.sort_cap = std::max<uint32_t>(S.sort_cap * 2, sort_count);
+    HIPCHK(e, S.b_sort_list.ensure(sizeof(uint32_t) * S.sort_cap));
     return BMQ_OK;
 }
 
@@ -637,17 +676,18 @@ static void print_wave_debug(bmq_engine* e, bmq_engine::BatchSlot& S) {
 }
 
 int finish_dist(bmq_engine* e, bmq_engine::BatchSlot& S, uint64_t* out_total) {
+    const auto rerun = [&] { // the same batch once more, with what this function has grown or switched on
+        BatchArgs a = S.last;
+        return launch_dist(e, S, a);
+    };
     for (int attempt = 0; attempt < 8; attempt++) {
         HIPCHK(e, hipEventSynchronize(S.ev_done)); // this batch only: a later batch may already be running behind it
         if (S.last.debug_flags & 30u) print_wave_debug(e, S);
         const Counters c = *S.h_ctr;
         const uint32_t grow = c.status & (ST_RERUN | ST_NEED_SORTLIST | ST_NEED_ADJ);
         if (grow) {
-            if (grow & ST_NEED_PAIRS) {
-                S.pair_cap = S.pair_cap * 2; // slices fill unevenly: double until every sub-allocator fits
-                if (S.pair_cap >= 0xFFFFFFFFull) return set_err(e, BMQ_E_RANGE, "matched-range buffer exceeds 2^32 entries");
-                HIPCHK(e, S.b_pairs.ensure(sizeof(MatchRange) * S.pair_cap));
-            }
+            int rc;
+            if ((grow & ST_NEED_PAIRS) && (rc = grow_pairs(e, S))) return rc;
             if (grow & ST_NEED_SPILL) {
                 S.spill_cap = S.spill_cap * 2;
                 if (S.spill_cap >= 0xFFFFFFFFull) return set_err(e, BMQ_E_RANGE, "range spill buffer exceeds 2^32 records");
@@ -665,30 +705,21 @@ int finish_dist(bmq_engine* e, bmq_engine::BatchSlot& S, uint64_t* out_total) {
                 S.adj_cap = (uint64_t)c.adj_bytes + c.adj_bytes / 8 + 4096;
                 HIPCHK(e, S.b_c_topics.ensure(S.adj_cap + 64));
             }
-            if (grow & ST_NEED_SORTLIST) {
-                S.sort_cap = std::max<uint32_t>(S.sort_cap * 2, c.sort_count);
-                HIPCHK(e, S.b_sort_list.ensure(sizeof(uint32_t) * S.sort_cap));
-            }
+            if ((grow & ST_NEED_SORTLIST) && (rc = grow_sort_list(e, S, c.sort_count))) return rc;
             if (c.sort_count) e->sort_on = true, e->sort_idle = 0;
             if (c.slow_count) e->slow_on = true, e->slow_idle = 0;
             if (c.status & ST_WANT_MIXED) e->mixed_on = true, e->mixed_idle = 0;
-            BatchArgs a = S.last;
-            int rc = launch_dist(e, S, a);
-            if (rc) return rc;
+            if ((rc = rerun())) return rc;
             continue;
         }
         if ((c.status & ST_WANT_MIXED) && !S.ran_mixed) { // waves held many tenants each: once more through the instantiation for that
             e->mixed_on = true, e->mixed_idle = 0;
-            BatchArgs a = S.last;
-            int rc = launch_dist(e, S, a);
-            if (rc) return rc;
+            if (int rc = rerun()) return rc;
             continue;
         }
         if (c.slow_count && !S.ran_slow) { // deep topics and k_walk_slow was not in the pipeline: the batch runs again with it
             e->slow_on = true, e->slow_idle = 0;
-            BatchArgs a = S.last;
-            int rc = launch_dist(e, S, a);
-            if (rc) return rc;
+            if (int rc = rerun()) return rc;
             continue;
         }
         if (c.sort_count && !S.ran_sort && !(c.status & (ST_RANGE | ST_NOSPACE))) { // rows to order: only that kernel
@@ -746,6 +777,160 @@ int check_dist_ready(bmq_engine* e) {
     if (e->device < 0) return set_err(e, BMQ_E_NODEVICE, "engine is host-only: matching requires a gfx950 device");
     if (!e->built || !e->dix || !e->dix->built) return set_err(e, BMQ_E_STATE, "bmq_rebuild has not been called");
     return BMQ_OK;
+}
+int check_retain_ready(bmq_engine* e) {
+    if (!e) return BMQ_E_INVAL;
+    if (e->device < 0) return set_err(e, BMQ_E_NODEVICE, "engine is host-only: matching requires a gfx950 device");
+    if (!e->rbuilt) return set_err(e, BMQ_E_STATE, "bmq_retain_rebuild has not been called");
+    return BMQ_OK;
+}
+
+// ---- what the match entry points share: submit, stage, wait ----------------------------------------------------------------------
+// One batch as every entry point takes it (host or device pointers): rows are topics in the dist direction, filters in the retain direction.
+struct BatchInput {
+    const uint8_t* tenants;
+    const uint32_t* tenant_off;
+    uint32_t n_tenants;
+    const uint32_t* row_tenant;
+    const uint8_t* rows;
+    const uint32_t* row_off;
+    uint32_t n_rows;
+};
+
+// Host batch `in` -> the slot's staging buffers, copied on stream `s`; `staged` = the same batch over them.  Also sizes the slot's own
+// outputs: row pointers, the total, and -- ids_per_row != 0 -- an id buffer of at least that many ids per row (S.dev_cap; a batch that
+// needs more says so: regrow_ids_and_relaunch).
+int stage_input(bmq_engine* e, bmq_engine::BatchSlot& S, const BatchInput& in, hipStream_t s, uint32_t ids_per_row,
+                BatchInput& staged) {
+    const size_t tb = in.n_tenants ? in.tenant_off[in.n_tenants] : 0, pb = in.row_off[in.n_rows];
+    int rc;
+    HIPCHK(e, S.s_tenants.ensure(tb + 16)); // (the kernels read whole 16-byte words)
+    HIPCHK(e, S.s_topics.ensure(pb + 16));
+    const size_t n_toff = in.n_tenants ? (size_t)in.n_tenants + 1 : 0;
+    if ((rc = upload(e, S.s_tenant_off, in.tenant_off, sizeof(uint32_t) * n_toff, s))) return rc;
+    if (tb) HIPCHK(e, hipMemcpyAsync(S.s_tenants.p, in.tenants, tb, hipMemcpyHostToDevice, s));
+    if ((rc = upload(e, S.s_topic_tenant, in.row_tenant, sizeof(uint32_t) * (size_t)in.n_rows, s))) return rc;
+    if (pb) HIPCHK(e, hipMemcpyAsync(S.s_topics.p, in.rows, pb, hipMemcpyHostToDevice, s));
+    if ((rc = upload(e, S.s_topic_off, in.row_off, sizeof(uint32_t) * ((size_t)in.n_rows + 1), s))) return rc;
+    HIPCHK(e, S.s_row_ptr.ensure(sizeof(uint32_t) * ((size_t)in.n_rows + 1)));
+    HIPCHK(e, S.b_total.ensure(sizeof(unsigned long long)));
+    if (ids_per_row) {
+        S.dev_cap = std::max<uint64_t>(S.s_ids.cap / 4, std::max<uint64_t>((uint64_t)in.n_rows * ids_per_row, 1024));
+        HIPCHK(e, S.s_ids.ensure(S.dev_cap * 4));
+    }
+    staged = BatchInput{S.s_tenants.as<uint8_t>(), S.s_tenant_off.as<uint32_t>(), in.n_tenants, S.s_topic_tenant.as<uint32_t>(),
+                        S.s_topics.as<uint8_t>(), S.s_topic_off.as<uint32_t>(), in.n_rows};
+    return BMQ_OK;
+}
+
+// where a batch's CSR goes (no id buffer: the kernels lay down the row pointers and the total, and report ST_NOSPACE)
+void bind_outputs(BatchArgs& a, uint32_t* out_row, uint32_t* out_ids, uint64_t cap, uint64_t* out_total) {
+    a.out_row_ptr = out_row;
+    a.out_ids = out_ids;
+    a.out_capacity = out_ids ? cap : 0;
+    a.out_total = (unsigned long long*)out_total;
+}
+BatchArgs dist_args(const BatchInput& in, uint32_t* out_row, uint32_t* out_ids, uint64_t cap, uint64_t* out_total) {
+    BatchArgs a{};
+    a.tenants = in.tenants;
+    a.tenant_off = in.tenant_off;
+    a.n_tenants = in.n_tenants;
+    a.topic_tenant = in.row_tenant;
+    a.topics = in.rows;
+    a.topic_off = in.row_off;
+    a.n_topics = in.n_rows;
+    bind_outputs(a, out_row, out_ids, cap, out_total);
+    return a;
+}
+
+// a free ticket slot of bmq_match_submit* (its index), or BMQ_E_STATE
+int take_ticket(bmq_engine* e) {
+    for (int i = 0; i < BMQ_MAX_TICKETS; i++)
+        if (!e->slots[1 + i].pending && !e->slots[1 + i].submitted) return i;
+    return set_err(e, BMQ_E_STATE, "every ticket is in flight: call bmq_match_wait first");
+}
+
+// The launch .. finish window of a *_dev launch belongs to ONE caller: the api lock is tried here and, once the launch is out (keep), given
+// back by bmq_match_finish (same thread), so a host-buffer call or a batcher launch of another thread cannot consume or overwrite the batch.
+struct ApiHold {
+    bmq_engine* e;
+    const bool owns;
+    bool kept = false;
+    explicit ApiHold(bmq_engine* e_) : e(e_), owns(e_->api.try_lock()) {}
+    ApiHold(const ApiHold&) = delete;
+    ~ApiHold() {
+        if (owns && !kept) e->api.unlock();
+    }
+    void keep() {
+        kept = true;
+        e->cur->api_held = true;
+    }
+};
+
+int launch_retain(bmq_engine* e, RetainArgs& r, BatchArgs& a); // (bmq_retain_engine.inc)
+
+// The batch of S ended in BMQ_E_NOSPACE because the slot's own id buffer was too small: it knows the size now.  Grows the buffer and
+// launches the batch again, as it was but for the buffer (dist or retain).  Called under e->mu.  No memory for the buffer: the waits
+// say BMQ_E_NOMEM; the blocking calls name the HIP call that failed (`hip_what`, BMQ_E_HIP), as they always have.
+constexpr const char* BLOCKING_REGROW = "e->cur->s_ids.ensure(dev_cap * 4)";
+int regrow_ids_and_relaunch(bmq_engine* e, bmq_engine::BatchSlot& S, uint64_t total, const char* hip_what = nullptr) {
+    S.dev_cap = total;
+    const hipError_t he = S.s_ids.ensure(S.dev_cap * 4);
+    if (he != hipSuccess && hip_what) return set_err(e, BMQ_E_HIP, std::string(hip_what) + ": " + hipGetErrorString(he));
+    if (he != hipSuccess) return set_err(e, BMQ_E_NOMEM, "out of device memory (result buffer)");
+    BatchArgs a = S.last;
+    a.out_ids = S.s_ids.as<uint32_t>();
+    a.out_capacity = S.dev_cap;
+    if (S.pending_kind == 0) return launch_dist(e, S, a);
+    RetainArgs r = S.rlast;
+    return launch_retain(e, r, a);
+}
+
+// Common front of the five waits: the ticket's batch is complete (run again where a buffer had to grow).  Returns WITHOUT the lock when the
+// wait is refused before anything was waited for -- the ticket stays in flight -- and with it otherwise.  `devptr`: a bmq_match_submit_dev
+// ticket (the caller's buffers: nothing of the slot's can grow).  COUNTS / RANGES batches end in ST_NOSPACE by design (no id buffer):
+// that is success here.
+int ticket_begin(bmq_engine* e, int ticket, int format, bool devptr, std::unique_lock<std::mutex>& g, uint64_t* total) {
+    bmq_engine::BatchSlot& S = e->slots[1 + ticket];
+    {
+        std::lock_guard<std::mutex> g0(e->mu);
+        if (devptr) {
+            if (!S.submitted || !S.devptr) return set_err(e, BMQ_E_STATE, "no such device-buffer ticket in flight");
+        } else {
+            if (!S.submitted) return set_err(e, BMQ_E_STATE, "no such ticket in flight");
+            if (S.format != format || S.devptr) return set_err(e, BMQ_E_STATE, "the ticket was submitted with another result format");
+        }
+        HIPCHK(e, hipSetDevice(e->device));
+    }
+    (void)hipEventSynchronize(S.ev_done); // outside the lock: other threads may submit / apply meanwhile
+    g.lock();
+    const bool own_ids = !devptr && (format == BMQ_FMT_IDS || format == BMQ_FMT_GROUPED);
+    int rc = BMQ_OK;
+    for (int attempt = 0; attempt < 3; attempt++) {
+        rc = finish_dist(e, S, total); // grows internal scratch and re-runs if a kernel asked for it
+        if (!own_ids) {
+            if (rc == BMQ_E_NOSPACE && !devptr) rc = BMQ_OK;
+            break;
+        }
+        if (rc != BMQ_E_NOSPACE || *total <= S.dev_cap) break;
+        if ((rc = regrow_ids_and_relaunch(e, S, *total))) break;
+    }
+    return rc;
+}
+// end of a wait's download on the copy-out stream (`he`: what enqueueing it returned): waited for without the engine lock -- the next
+// batch's kernels run meanwhile, the slot stays taken
+int download_end(bmq_engine* e, std::unique_lock<std::mutex>& g, hipError_t he) {
+    g.unlock();
+    if (he == hipSuccess) he = hipStreamSynchronize(e->s_out);
+    g.lock();
+    if (he != hipSuccess) return set_err(e, BMQ_E_HIP, std::string("result download: ") + hipGetErrorString(he));
+    return BMQ_OK;
+}
+void ticket_release(bmq_engine::BatchSlot& S) {
+    S.submitted = false;
+    S.pending = false;
+    S.devptr = false;
+    S.format = BMQ_FMT_IDS;
 }
 
 } // namespace
@@ -1536,37 +1721,16 @@ int bmq_match_batch_dev(bmq_engine* e, const uint8_t* d_tenants, const uint32_t*
     if (n_topics == 0 || !d_out_row_ptr || !d_topic_off || !d_topics || !d_topic_tenant || !d_out_total)
         return set_err(e, BMQ_E_INVAL, "null pointer or empty batch");
     if ((uintptr_t)d_topics & 15) return set_err(e, BMQ_E_INVAL, "the topic byte buffer must be 16-byte aligned");
-    // The launch .. finish window belongs to ONE caller: the api lock is taken here and given back by bmq_match_finish (same
-    // thread), so a host-buffer call or a batcher launch of another thread cannot consume or overwrite this batch.
-    if (!e->api.try_lock()) return set_err(e, BMQ_E_STATE, "the engine is busy with another thread's call");
-    struct Unlock {
-        bmq_engine* e;
-        bool keep = false;
-        ~Unlock() {
-            if (!keep) e->api.unlock();
-        }
-    } api_guard{e};
+    ApiHold api(e);
+    if (!api.owns) return set_err(e, BMQ_E_STATE, "the engine is busy with another thread's call");
     std::lock_guard<std::mutex> g(e->mu);
     if (e->cur->pending) return set_err(e, BMQ_E_STATE, "a batch is in flight: call bmq_match_finish first");
     HIPCHK(e, hipSetDevice(e->device));
     if ((rc = ensure_batch_scratch(e, *e->cur, n_tenants, n_topics))) return rc;
-    BatchArgs a{};
-    a.tenants = d_tenants;
-    a.tenant_off = d_tenant_off;
-    a.n_tenants = n_tenants;
-    a.topic_tenant = d_topic_tenant;
-    a.topics = d_topics;
-    a.topic_off = d_topic_off;
-    a.n_topics = n_topics;
-    a.out_row_ptr = d_out_row_ptr;
-    a.out_ids = d_out_route_ids;
-    a.out_capacity = d_out_route_ids ? out_capacity : 0;
-    a.out_total = (unsigned long long*)d_out_total;
+    BatchArgs a = dist_args({d_tenants, d_tenant_off, n_tenants, d_topic_tenant, d_topics, d_topic_off, n_topics}, d_out_row_ptr, d_out_route_ids,
+                            out_capacity, d_out_total);
     rc = launch_dist(e, *e->cur, a);
-    if (rc == BMQ_OK) {
-        api_guard.keep = true;
-        e->cur->api_held = true;
-    }
+    if (rc == BMQ_OK) api.keep();
     return rc;
 }
 
@@ -1623,47 +1787,32 @@ int bmq_match_batch(bmq_engine* e, const uint8_t* tenants, const uint32_t* tenan
     }
     if (!topics || !topic_off || !topic_tenant || (n_tenants && (!tenants || !tenant_off)))
         return set_err(e, BMQ_E_INVAL, "null input pointer");
-    uint64_t dev_cap;
+    bmq_engine::BatchSlot& S = *e->cur;
+    BatchInput d;
     {
         std::lock_guard<std::mutex> g(e->mu);
         HIPCHK(e, hipSetDevice(e->device));
-        const size_t tb = n_tenants ? tenant_off[n_tenants] : 0, pb = topic_off[n_topics];
-        HIPCHK(e, e->cur->s_tenants.ensure(tb + 16));
-        HIPCHK(e, e->cur->s_topics.ensure(pb + 16));
-        if ((rc = upload(e, e->cur->s_tenant_off, tenant_off, sizeof(uint32_t) * (n_tenants ? n_tenants + 1 : 0)))) return rc;
-        if (tb) HIPCHK(e, hipMemcpyAsync(e->cur->s_tenants.p, tenants, tb, hipMemcpyHostToDevice, e->stream));
-        if ((rc = upload(e, e->cur->s_topic_tenant, topic_tenant, sizeof(uint32_t) * n_topics))) return rc;
-        if (pb) HIPCHK(e, hipMemcpyAsync(e->cur->s_topics.p, topics, pb, hipMemcpyHostToDevice, e->stream));
-        if ((rc = upload(e, e->cur->s_topic_off, topic_off, sizeof(uint32_t) * (n_topics + 1)))) return rc;
-        HIPCHK(e, e->cur->s_row_ptr.ensure(sizeof(uint32_t) * (n_topics + 1)));
-        HIPCHK(e, e->cur->b_total.ensure(sizeof(unsigned long long)));
-        dev_cap = std::max<uint64_t>(e->cur->s_ids.cap / 4, std::max<uint64_t>((uint64_t)n_topics * 4, 1024));
-        HIPCHK(e, e->cur->s_ids.ensure(dev_cap * 4));
+        const BatchInput in{tenants, tenant_off, n_tenants, topic_tenant, topics, topic_off, n_topics};
+        if ((rc = stage_input(e, S, in, e->stream, 4, d))) return rc;
     }
-    for (int attempt = 0; attempt < 3; attempt++) {
-        rc = bmq_match_batch_dev(e, e->cur->s_tenants.as<uint8_t>(), e->cur->s_tenant_off.as<uint32_t>(), n_tenants,
-                                 e->cur->s_topic_tenant.as<uint32_t>(), e->cur->s_topics.as<uint8_t>(), e->cur->s_topic_off.as<uint32_t>(),
-                                 n_topics, e->cur->s_row_ptr.as<uint32_t>(), e->cur->s_ids.as<uint32_t>(), dev_cap,
-                                 e->cur->b_total.as<uint64_t>());
-        if (rc) return rc;
-        uint64_t total = 0;
+    rc = bmq_match_batch_dev(e, d.tenants, d.tenant_off, d.n_tenants, d.row_tenant, d.rows, d.row_off, d.n_rows, S.s_row_ptr.as<uint32_t>(),
+                             S.s_ids.as<uint32_t>(), S.dev_cap, S.b_total.as<uint64_t>());
+    uint64_t total = 0;
+    for (int attempt = 0; rc == BMQ_OK; attempt++) { // launched: finish; the slot's id buffer too small: once more with the size it told
         rc = bmq_match_finish(e, &total);
         *out_needed = total;
-        if (rc == BMQ_E_NOSPACE) {
-            if (total > out_capacity || !out_route_ids) return rc; // the caller's buffer is the problem
-            std::lock_guard<std::mutex> g(e->mu);
-            dev_cap = total;
-            HIPCHK(e, e->cur->s_ids.ensure(dev_cap * 4));
-            continue;
-        }
-        if (rc) return rc;
+        if (rc != BMQ_E_NOSPACE) break;
+        if (total > out_capacity || !out_route_ids) return rc; // the caller's buffer is the problem
+        if (attempt == 2) return set_err(e, BMQ_E_NOMEM, "device output buffer growth did not converge");
         std::lock_guard<std::mutex> g(e->mu);
-        HIPCHK(e, hipMemcpy(out_row_ptr, e->cur->s_row_ptr.p, sizeof(uint32_t) * (n_topics + 1), hipMemcpyDeviceToHost));
-        if (total > out_capacity || (total && !out_route_ids)) return set_err(e, BMQ_E_NOSPACE, "output buffer too small");
-        if (total) HIPCHK(e, hipMemcpy(out_route_ids, e->cur->s_ids.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
-        return BMQ_OK;
+        rc = regrow_ids_and_relaunch(e, S, total, BLOCKING_REGROW);
     }
-    return set_err(e, BMQ_E_NOMEM, "device output buffer growth did not converge");
+    if (rc) return rc;
+    std::lock_guard<std::mutex> g(e->mu);
+    HIPCHK(e, hipMemcpy(out_row_ptr, S.s_row_ptr.p, sizeof(uint32_t) * (n_topics + 1), hipMemcpyDeviceToHost));
+    if (total > out_capacity || (total && !out_route_ids)) return set_err(e, BMQ_E_NOSPACE, "output buffer too small");
+    if (total) HIPCHK(e, hipMemcpy(out_route_ids, S.s_ids.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
+    return BMQ_OK;
 }
 
 // ---- asynchronous host-buffer match: two batches in flight ---------------------------------------------------------------
@@ -1693,52 +1842,21 @@ int bmq_match_submit_fmt(bmq_engine* e, const uint8_t* tenants, const uint32_t* 
         return set_err(e, BMQ_E_INVAL, "null pointer or empty batch");
     std::lock_guard<std::mutex> g(e->mu);
     HIPCHK(e, hipSetDevice(e->device));
-    int k = -1;
-    for (int i = 0; i < BMQ_MAX_TICKETS; i++)
-        if (!e->slots[1 + i].pending && !e->slots[1 + i].submitted) {
-            k = i;
-            break;
-        }
-    if (k < 0) return set_err(e, BMQ_E_STATE, "every ticket is in flight: call bmq_match_wait first");
+    const int k = take_ticket(e);
+    if (k < 0) return k;
     bmq_engine::BatchSlot& S = e->slots[1 + k]; // ticket k: never the slot the blocking entry points stage into
-    const size_t tb = n_tenants ? tenant_off[n_tenants] : 0, pb = topic_off[n_topics];
-    HIPCHK(e, S.s_tenants.ensure(tb + 16));
-    HIPCHK(e, S.s_topics.ensure(pb + 16));
-    HIPCHK(e, S.s_tenant_off.ensure(sizeof(uint32_t) * ((size_t)n_tenants + 1)));
-    HIPCHK(e, S.s_topic_tenant.ensure(sizeof(uint32_t) * (size_t)n_topics));
-    HIPCHK(e, S.s_topic_off.ensure(sizeof(uint32_t) * ((size_t)n_topics + 1)));
-    HIPCHK(e, S.s_row_ptr.ensure(sizeof(uint32_t) * ((size_t)n_topics + 1)));
-    HIPCHK(e, S.b_total.ensure(sizeof(unsigned long long)));
-    const bool with_ids = format == BMQ_FMT_IDS || format == BMQ_FMT_GROUPED;
-    if (with_ids) {
-        S.dev_cap = std::max<uint64_t>(S.s_ids.cap / 4, std::max<uint64_t>((uint64_t)n_topics * 24, 1024));
-        HIPCHK(e, S.s_ids.ensure(S.dev_cap * 4));
-    }
     if ((rc = ensure_batch_scratch(e, S, n_tenants, n_topics))) return rc;
     // upload on the copy-in stream: it overlaps the kernels of the batch submitted before (pinned sources: bmq_host_alloc)
-    if (n_tenants) {
-        HIPCHK(e, hipMemcpyAsync(S.s_tenant_off.p, tenant_off, sizeof(uint32_t) * ((size_t)n_tenants + 1), hipMemcpyHostToDevice, e->s_in));
-        if (tb) HIPCHK(e, hipMemcpyAsync(S.s_tenants.p, tenants, tb, hipMemcpyHostToDevice, e->s_in));
-    }
-    HIPCHK(e, hipMemcpyAsync(S.s_topic_tenant.p, topic_tenant, sizeof(uint32_t) * (size_t)n_topics, hipMemcpyHostToDevice, e->s_in));
-    if (pb) HIPCHK(e, hipMemcpyAsync(S.s_topics.p, topics, pb, hipMemcpyHostToDevice, e->s_in));
-    HIPCHK(e, hipMemcpyAsync(S.s_topic_off.p, topic_off, sizeof(uint32_t) * ((size_t)n_topics + 1), hipMemcpyHostToDevice, e->s_in));
+    const bool with_ids = format == BMQ_FMT_IDS || format == BMQ_FMT_GROUPED;
+    BatchInput d;
+    const BatchInput in{tenants, tenant_off, n_tenants, topic_tenant, topics, topic_off, n_topics};
+    if ((rc = stage_input(e, S, in, e->s_in, with_ids ? 24 : 0, d))) return rc;
     HIPCHK(e, hipEventRecord(S.ev_in, e->s_in));
     HIPCHK(e, hipStreamWaitEvent(e->stream, S.ev_in, 0));
-    BatchArgs a{};
-    a.tenants = S.s_tenants.as<uint8_t>();
-    a.tenant_off = S.s_tenant_off.as<uint32_t>();
-    a.n_tenants = n_tenants;
-    a.topic_tenant = S.s_topic_tenant.as<uint32_t>();
-    a.topics = S.s_topics.as<uint8_t>();
-    a.topic_off = S.s_topic_off.as<uint32_t>();
-    a.n_topics = n_topics;
-    a.out_row_ptr = S.s_row_ptr.as<uint32_t>();
     // COUNTS / RANGES: no id is written -- k_expand still lays down the row pointers (= the fan-out of every topic) and the totals,
     // sees that nothing fits a buffer of 0 ids, and leaves (ST_NOSPACE, which these formats expect)
-    a.out_ids = with_ids ? S.s_ids.as<uint32_t>() : nullptr;
-    a.out_capacity = with_ids ? S.dev_cap : 0;
-    a.out_total = S.b_total.as<unsigned long long>();
+    uint32_t* const ids = with_ids ? S.s_ids.as<uint32_t>() : nullptr;
+    BatchArgs a = dist_args(d, S.s_row_ptr.as<uint32_t>(), ids, S.dev_cap, S.b_total.as<uint64_t>());
     S.format = format;
     if ((rc = launch_dist(e, S, a))) {
         S.format = BMQ_FMT_IDS;
@@ -1754,48 +1872,21 @@ int bmq_match_wait(bmq_engine* e, int ticket, uint32_t* out_row_ptr, uint32_t* o
     if (!e || ticket < 0 || ticket >= BMQ_MAX_TICKETS || !out_row_ptr || !out_needed) return BMQ_E_INVAL;
     if (e->device < 0) return set_err(e, BMQ_E_NODEVICE, "engine is host-only");
     bmq_engine::BatchSlot& S = e->slots[1 + ticket];
+    std::unique_lock<std::mutex> g(e->mu, std::defer_lock);
     uint64_t total = 0;
-    {
-        std::lock_guard<std::mutex> g(e->mu);
-        if (!S.submitted) return set_err(e, BMQ_E_STATE, "no such ticket in flight");
-        if (S.format != BMQ_FMT_IDS || S.devptr) return set_err(e, BMQ_E_STATE, "the ticket was submitted with another result format");
-        HIPCHK(e, hipSetDevice(e->device));
-    }
-    (void)hipEventSynchronize(S.ev_done); // outside the lock: other threads may submit / apply meanwhile
-    std::unique_lock<std::mutex> g(e->mu);
-    int rc = BMQ_OK;
-    {
-        for (int attempt = 0; attempt < 3; attempt++) {
-            rc = finish_dist(e, S, &total); // grows internal scratch and re-runs if a kernel asked for it
-            if (rc != BMQ_E_NOSPACE || total <= S.dev_cap) break;
-            S.dev_cap = total; // the slot's own id buffer was too small: it knows the size now
-            if (S.s_ids.ensure(S.dev_cap * 4) != hipSuccess) {
-                rc = set_err(e, BMQ_E_NOMEM, "out of device memory (result buffer)");
-                break;
-            }
-            BatchArgs a = S.last;
-            a.out_ids = S.s_ids.as<uint32_t>();
-            a.out_capacity = S.dev_cap;
-            if ((rc = launch_dist(e, S, a))) break;
-        }
-    }
+    int rc = ticket_begin(e, ticket, BMQ_FMT_IDS, false, g, &total);
+    if (!g.owns_lock()) return rc; // refused before the wait: the ticket stays as it was
     *out_needed = total;
     const bool fits = total <= out_capacity && (total == 0 || out_route_ids);
-    hipError_t he = hipSuccess;
-    if (rc == BMQ_OK) {
-        // download on the copy-out stream: it overlaps the kernels of the batch submitted after this one.  The slot stays taken
-        // until the copy has finished; the engine lock is not held meanwhile.
-        he = hipMemcpyAsync(out_row_ptr, S.s_row_ptr.p, sizeof(uint32_t) * ((size_t)S.n_rows + 1), hipMemcpyDeviceToHost, e->s_out);
+    if (rc == BMQ_OK) { // download on the copy-out stream: it overlaps the kernels of the batch submitted after this one
+        const size_t row_bytes = sizeof(uint32_t) * ((size_t)S.n_rows + 1);
+        hipError_t he = hipMemcpyAsync(out_row_ptr, S.s_row_ptr.p, row_bytes, hipMemcpyDeviceToHost, e->s_out);
         if (he == hipSuccess && fits && total)
             he = hipMemcpyAsync(out_route_ids, S.s_ids.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost, e->s_out);
-        g.unlock();
-        if (he == hipSuccess) he = hipStreamSynchronize(e->s_out);
-        g.lock();
+        rc = download_end(e, g, he);
     }
-    S.submitted = false;
-    S.pending = false;
+    ticket_release(S);
     if (rc) return rc;
-    if (he != hipSuccess) return set_err(e, BMQ_E_HIP, std::string("result download: ") + hipGetErrorString(he));
     return fits ? BMQ_OK : set_err(e, BMQ_E_NOSPACE, "output buffer too small");
 }
 
@@ -1811,27 +1902,12 @@ int bmq_match_submit_dev(bmq_engine* e, const uint8_t* d_tenants, const uint32_t
     if ((uintptr_t)d_topics & 15) return set_err(e, BMQ_E_INVAL, "the topic byte buffer must be 16-byte aligned");
     std::lock_guard<std::mutex> g(e->mu);
     HIPCHK(e, hipSetDevice(e->device));
-    int k = -1;
-    for (int i = 0; i < BMQ_MAX_TICKETS; i++)
-        if (!e->slots[1 + i].pending && !e->slots[1 + i].submitted) {
-            k = i;
-            break;
-        }
-    if (k < 0) return set_err(e, BMQ_E_STATE, "every ticket is in flight: call bmq_match_wait first");
+    const int k = take_ticket(e);
+    if (k < 0) return k;
     bmq_engine::BatchSlot& S = e->slots[1 + k];
     if ((rc = ensure_batch_scratch(e, S, n_tenants, n_topics))) return rc;
-    BatchArgs a{};
-    a.tenants = d_tenants;
-    a.tenant_off = d_tenant_off;
-    a.n_tenants = n_tenants;
-    a.topic_tenant = d_topic_tenant;
-    a.topics = d_topics;
-    a.topic_off = d_topic_off;
-    a.n_topics = n_topics;
-    a.out_row_ptr = d_out_row_ptr;
-    a.out_ids = d_out_route_ids;
-    a.out_capacity = d_out_route_ids ? out_capacity : 0;
-    a.out_total = (unsigned long long*)d_out_total;
+    BatchArgs a = dist_args({d_tenants, d_tenant_off, n_tenants, d_topic_tenant, d_topics, d_topic_off, n_topics}, d_out_row_ptr, d_out_route_ids,
+                            out_capacity, d_out_total);
     S.format = BMQ_FMT_IDS;
     if ((rc = launch_dist(e, S, a))) return rc;
     S.submitted = true;
@@ -1844,20 +1920,12 @@ int bmq_match_submit_dev(bmq_engine* e, const uint8_t* d_tenants, const uint32_t
 int bmq_match_wait_dev(bmq_engine* e, int ticket, uint64_t* out_total) {
     if (!e || ticket < 0 || ticket >= BMQ_MAX_TICKETS) return BMQ_E_INVAL;
     if (e->device < 0) return set_err(e, BMQ_E_NODEVICE, "engine is host-only");
-    bmq_engine::BatchSlot& S = e->slots[1 + ticket];
-    {
-        std::lock_guard<std::mutex> g(e->mu);
-        if (!S.submitted || !S.devptr) return set_err(e, BMQ_E_STATE, "no such device-buffer ticket in flight");
-        HIPCHK(e, hipSetDevice(e->device));
-    }
-    (void)hipEventSynchronize(S.ev_done); // outside the lock: other threads may submit / apply meanwhile
-    std::lock_guard<std::mutex> g(e->mu);
+    std::unique_lock<std::mutex> g(e->mu, std::defer_lock);
     uint64_t total = 0;
-    const int rc = finish_dist(e, S, &total); // grows internal scratch and re-runs if a kernel asked for it
+    const int rc = ticket_begin(e, ticket, BMQ_FMT_IDS, true, g, &total);
+    if (!g.owns_lock()) return rc;
     if (out_total) *out_total = total;
-    S.submitted = false;
-    S.pending = false;
-    S.devptr = false;
+    ticket_release(e->slots[1 + ticket]);
     return rc;
 }
 

@@ -4,71 +4,21 @@
 //   COUNTS  : DistWorkerCoProc.batchDist replies with the fan-out per topic and nothing else (DW/DistWorkerCoProc.java:535-538)
 //   RANGES  : the matched (begin, count) id ranges (bmq_format_kernels.h); the consumer that walks the routes expands them itself
 //   GROUPED : the (topic, route) pairs regrouped by DelivererKey (bmq_fanout.h), what DeliverExecutorGroup.submit builds next
-// Included at the end of bmq_engine.hip.
-namespace {
-
-// Common front of the waits: the ticket's batch is complete (re-run if a scratch buffer had to grow).  COUNTS / RANGES batches end in
-// ST_NOSPACE by design (no id buffer): that is success here.
-int fmt_wait_begin(bmq_engine* e, int ticket, int format, std::unique_lock<std::mutex>& g, uint64_t* total) {
-    bmq_engine::BatchSlot& S = e->slots[1 + ticket];
-    {
-        std::lock_guard<std::mutex> g0(e->mu);
-        if (!S.submitted) return set_err(e, BMQ_E_STATE, "no such ticket in flight");
-        if (S.format != format || S.devptr) return set_err(e, BMQ_E_STATE, "the ticket was submitted with another result format");
-        HIPCHK(e, hipSetDevice(e->device));
-    }
-    (void)hipEventSynchronize(S.ev_done); // outside the lock: other threads may submit / apply meanwhile
-    g.lock();
-    int rc = BMQ_OK;
-    for (int attempt = 0; attempt < 3; attempt++) {
-        rc = finish_dist(e, S, total);
-        if (format != BMQ_FMT_GROUPED) {
-            if (rc == BMQ_E_NOSPACE) rc = BMQ_OK;
-            break;
-        }
-        if (rc != BMQ_E_NOSPACE || *total <= S.dev_cap) break;
-        S.dev_cap = *total; // the slot's own id buffer was too small: it knows the size now
-        if (S.s_ids.ensure(S.dev_cap * 4) != hipSuccess) {
-            rc = set_err(e, BMQ_E_NOMEM, "out of device memory (result buffer)");
-            break;
-        }
-        BatchArgs a = S.last;
-        a.out_ids = S.s_ids.as<uint32_t>();
-        a.out_capacity = S.dev_cap;
-        if ((rc = launch_dist(e, S, a))) break;
-    }
-    return rc;
-}
-void fmt_release(bmq_engine::BatchSlot& S) {
-    S.submitted = false;
-    S.pending = false;
-    S.format = BMQ_FMT_IDS;
-}
-// download on the copy-out stream without the engine lock (the next batch's kernels run meanwhile)
-int fmt_download_end(bmq_engine* e, std::unique_lock<std::mutex>& g, hipError_t he) {
-    g.unlock();
-    if (he == hipSuccess) he = hipStreamSynchronize(e->s_out);
-    g.lock();
-    if (he != hipSuccess) return set_err(e, BMQ_E_HIP, std::string("result download: ") + hipGetErrorString(he));
-    return BMQ_OK;
-}
-
-} // namespace
-
+// Included at the end of bmq_engine.hip; the waits stand on its ticket_begin / download_end / ticket_release.
 extern "C" int bmq_match_wait_counts(bmq_engine* e, int ticket, uint32_t* out_row_ptr, uint64_t* out_total) {
     if (!e || ticket < 0 || ticket >= BMQ_MAX_TICKETS || !out_row_ptr) return BMQ_E_INVAL;
     if (e->device < 0) return set_err(e, BMQ_E_NODEVICE, "engine is host-only");
     bmq_engine::BatchSlot& S = e->slots[1 + ticket];
     std::unique_lock<std::mutex> g(e->mu, std::defer_lock);
     uint64_t total = 0;
-    int rc = fmt_wait_begin(e, ticket, BMQ_FMT_COUNTS, g, &total);
+    int rc = ticket_begin(e, ticket, BMQ_FMT_COUNTS, false, g, &total);
     if (!g.owns_lock()) return rc; // refused before the wait: the ticket stays as it was
     if (rc == BMQ_OK) {
         const hipError_t he = hipMemcpyAsync(out_row_ptr, S.s_row_ptr.p, sizeof(uint32_t) * ((size_t)S.n_rows + 1), hipMemcpyDeviceToHost, e->s_out);
-        rc = fmt_download_end(e, g, he);
+        rc = download_end(e, g, he);
     }
     if (out_total) *out_total = total;
-    fmt_release(S);
+    ticket_release(S);
     return rc;
 }
 
@@ -80,7 +30,7 @@ extern "C" int bmq_match_wait_ranges(bmq_engine* e, int ticket, uint32_t* out_ro
     bmq_engine::BatchSlot& S = e->slots[1 + ticket];
     std::unique_lock<std::mutex> g(e->mu, std::defer_lock);
     uint64_t total = 0;
-    int rc = fmt_wait_begin(e, ticket, BMQ_FMT_RANGES, g, &total);
+    int rc = ticket_begin(e, ticket, BMQ_FMT_RANGES, false, g, &total);
     if (!g.owns_lock()) return rc;
     *out_info = bmq_ranges_info{};
     out_info->n_ids = total;
@@ -117,9 +67,9 @@ extern "C" int bmq_match_wait_ranges(bmq_engine* e, int ticket, uint32_t* out_ro
         if (he == hipSuccess && out_row_ptr) he = hipMemcpyAsync(out_row_ptr, S.s_row_ptr.p, sizeof(uint32_t) * n1, hipMemcpyDeviceToHost, e->s_out);
         if (he == hipSuccess && fits && n_r) he = hipMemcpyAsync(out_ranges, S.f_ranges.p, sizeof(MatchRange) * n_r, hipMemcpyDeviceToHost, e->s_out);
         if (he == hipSuccess && fits && n_s) he = hipMemcpyAsync(out_side_ids, S.f_side.p, sizeof(uint32_t) * n_s, hipMemcpyDeviceToHost, e->s_out);
-        rc = fmt_download_end(e, g, he);
+        rc = download_end(e, g, he);
     }
-    fmt_release(S);
+    ticket_release(S);
     if (rc) return rc;
     return fits ? BMQ_OK : set_err(e, BMQ_E_NOSPACE, "range buffers too small");
 }
@@ -131,7 +81,7 @@ extern "C" int bmq_match_wait_grouped(bmq_engine* e, int ticket, uint32_t* out_t
     bmq_engine::BatchSlot& S = e->slots[1 + ticket];
     std::unique_lock<std::mutex> g(e->mu, std::defer_lock);
     uint64_t total = 0;
-    int rc = fmt_wait_begin(e, ticket, BMQ_FMT_GROUPED, g, &total);
+    int rc = ticket_begin(e, ticket, BMQ_FMT_GROUPED, false, g, &total);
     if (!g.owns_lock()) return rc;
     *out_total = total;
     FanoutResult r{};
@@ -159,10 +109,10 @@ extern "C" int bmq_match_wait_grouped(bmq_engine* e, int ticket, uint32_t* out_t
                 he = hipMemcpyAsync(out_group_off, d_off, sizeof(uint32_t) * ((size_t)r.n_groups + 1), hipMemcpyDeviceToHost, e->s_out);
                 if (he == hipSuccess && r.n_groups) he = hipMemcpyAsync(out_group_rep, d_rep, sizeof(uint32_t) * r.n_groups, hipMemcpyDeviceToHost, e->s_out);
             }
-            rc = fmt_download_end(e, g, he);
+            rc = download_end(e, g, he);
         }
     }
-    fmt_release(S);
+    ticket_release(S);
     if (rc) return rc;
     if (out_n_groups) *out_n_groups = r.n_groups;
     if (out_special) *out_special = r.special;

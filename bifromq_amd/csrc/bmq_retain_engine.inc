@@ -209,6 +209,11 @@ int launch_retain(bmq_engine* e, RetainArgs& r, BatchArgs& a) {
 } // namespace
 
 static int retain_finish(bmq_engine* e, uint64_t* out_total) {
+    const auto rerun = [&] { // the same batch once more, with what this function has grown or switched on
+        RetainArgs r = e->cur->rlast;
+        BatchArgs a = e->cur->last;
+        return launch_retain(e, r, a);
+    };
     for (int attempt = 0; attempt < 16; attempt++) {
         HIPCHK(e, hipStreamSynchronize(e->stream));
         const Counters c = *e->cur->h_ctr;
@@ -218,10 +223,7 @@ static int retain_finish(bmq_engine* e, uint64_t* out_total) {
         }
         if (c.slow_count && !e->cur->ran_rdeep) { // filters of more than R_MAXL levels and the deep pass was not in the pipeline: once more with it
             e->rdeep_on = true, e->rdeep_idle = 0;
-            RetainArgs r = e->cur->rlast;
-            BatchArgs a = e->cur->last;
-            int rc = launch_retain(e, r, a);
-            if (rc) return rc;
+            if (int rc = rerun()) return rc;
             continue;
         }
         if (e->cur->ran_rdeep && (c.slow_count ? (e->rdeep_idle = 0) : ++e->rdeep_idle) >= REPAIR_IDLE_BATCHES) e->rdeep_on = false;
@@ -231,11 +233,8 @@ static int retain_finish(bmq_engine* e, uint64_t* out_total) {
                 e->ov_pair_cap *= 4;
                 if (e->ov_pair_cap >= 0xFFFFFFFFull) return set_err(e, BMQ_E_RANGE, "the overlay's matched-range buffer exceeds 2^32 entries");
             }
-            if (grow & ST_NEED_PAIRS) {
-                e->cur->pair_cap = e->cur->pair_cap * 2;
-                if (e->cur->pair_cap >= 0xFFFFFFFFull) return set_err(e, BMQ_E_RANGE, "matched-range buffer exceeds 2^32 entries");
-                HIPCHK(e, e->cur->b_pairs.ensure(sizeof(MatchRange) * e->cur->pair_cap));
-            }
+            int rc;
+            if ((grow & ST_NEED_PAIRS) && (rc = grow_pairs(e, *e->cur))) return rc;
             if (grow & ST_RETAIN_FRONT) {
                 if (e->rgcap >= (1u << 24)) return set_err(e, BMQ_E_RANGE, "retain frontier exceeds 16M ranges");
                 e->rgcap *= 4;
@@ -244,14 +243,8 @@ static int retain_finish(bmq_engine* e, uint64_t* out_total) {
                 if (e->rwcap >= (1u << 22)) return set_err(e, BMQ_E_RANGE, "retain frontier list exceeds 4M nodes");
                 e->rwcap *= 4;
             }
-            if (grow & ST_NEED_SORTLIST) {
-                e->cur->sort_cap = std::max<uint32_t>(e->cur->sort_cap * 2, c.sort_count);
-                HIPCHK(e, e->cur->b_sort_list.ensure(sizeof(uint32_t) * e->cur->sort_cap));
-            }
-            RetainArgs r = e->cur->rlast;
-            BatchArgs a = e->cur->last;
-            int rc = launch_retain(e, r, a);
-            if (rc) return rc;
+            if ((grow & ST_NEED_SORTLIST) && (rc = grow_sort_list(e, *e->cur, c.sort_count))) return rc;
+            if ((rc = rerun())) return rc;
             continue;
         }
         e->cur->pending = false;
@@ -914,24 +907,16 @@ int bmq_retain_match_batch_dev(bmq_engine* e, const uint8_t* d_tenants, const ui
                                const uint32_t* d_filter_tenant, const uint8_t* d_filters, const uint32_t* d_filter_off,
                                uint32_t n_filters, uint32_t* d_out_row_ptr, uint32_t* d_out_topic_ids, uint64_t out_capacity,
                                uint64_t* d_out_total) {
-    if (!e) return BMQ_E_INVAL;
-    if (e->device < 0) return set_err(e, BMQ_E_NODEVICE, "engine is host-only: matching requires a gfx950 device");
-    if (!e->rbuilt) return set_err(e, BMQ_E_STATE, "bmq_retain_rebuild has not been called");
+    int rc = check_retain_ready(e);
+    if (rc) return rc;
     if (n_filters == 0 || !d_out_row_ptr || !d_filter_off || !d_filters || !d_filter_tenant || !d_out_total)
         return set_err(e, BMQ_E_INVAL, "null pointer or empty batch");
-    if (!e->api.try_lock()) return set_err(e, BMQ_E_STATE, "the engine is busy with another thread's call"); // see bmq_match_batch_dev
-    struct Unlock {
-        bmq_engine* e;
-        bool keep = false;
-        ~Unlock() {
-            if (!keep) e->api.unlock();
-        }
-    } api_guard{e};
+    ApiHold api(e);
+    if (!api.owns) return set_err(e, BMQ_E_STATE, "the engine is busy with another thread's call");
     std::lock_guard<std::mutex> g(e->mu);
     if (e->cur->pending) return set_err(e, BMQ_E_STATE, "a batch is in flight: call bmq_match_finish first");
     HIPCHK(e, hipSetDevice(e->device));
-    int rc = ensure_batch_scratch(e, *e->cur, n_tenants, n_filters);
-    if (rc) return rc;
+    if ((rc = ensure_batch_scratch(e, *e->cur, n_tenants, n_filters))) return rc;
     RetainArgs r{};
     r.tenants = d_tenants;
     r.tenant_off = d_tenant_off;
@@ -941,66 +926,51 @@ int bmq_retain_match_batch_dev(bmq_engine* e, const uint8_t* d_tenants, const ui
     r.filter_off = d_filter_off;
     r.n_filters = n_filters;
     BatchArgs a{};
-    a.out_row_ptr = d_out_row_ptr;
-    a.out_ids = d_out_topic_ids;
-    a.out_capacity = d_out_topic_ids ? out_capacity : 0;
-    a.out_total = (unsigned long long*)d_out_total;
+    bind_outputs(a, d_out_row_ptr, d_out_topic_ids, out_capacity, d_out_total);
     rc = launch_retain(e, r, a);
-    if (rc == BMQ_OK) {
-        api_guard.keep = true;
-        e->cur->api_held = true;
-    }
+    if (rc == BMQ_OK) api.keep();
     return rc;
 }
 
 // host buffers in -> the complete CSR of the batch in e->cur->s_row_ptr / e->cur->s_ids (device); *total = number of ids
 // d_row / d_ids: where the CSR goes (nullptr: the engine's own s_row_ptr / s_ids, grown on demand)
-static int retain_match_to_scratch(bmq_engine* e, const uint8_t* tenants, const uint32_t* tenant_off, uint32_t n_tenants,
-                                   const uint32_t* filter_tenant, const uint8_t* filters, const uint32_t* filter_off,
-                                   uint32_t n_filters, uint64_t* total, uint32_t* d_row, uint32_t* d_ids, uint64_t d_ids_cap) {
+static int retain_match_to_scratch(bmq_engine* e, const BatchInput& in, uint64_t* total, uint32_t* d_row, uint32_t* d_ids,
+                                   uint64_t d_ids_cap) {
+    bmq_engine::BatchSlot& S = *e->cur;
+    BatchInput d;
     int rc;
-    uint64_t dev_cap;
     {
         std::lock_guard<std::mutex> g(e->mu);
         HIPCHK(e, hipSetDevice(e->device));
-        const size_t tb = n_tenants ? tenant_off[n_tenants] : 0, pb = filter_off[n_filters];
-        HIPCHK(e, e->cur->s_tenants.ensure(tb + 16));
-        HIPCHK(e, e->cur->s_topics.ensure(pb + 16));
-        if ((rc = upload(e, e->cur->s_tenant_off, tenant_off, sizeof(uint32_t) * (n_tenants ? n_tenants + 1 : 0)))) return rc;
-        if (tb) HIPCHK(e, hipMemcpyAsync(e->cur->s_tenants.p, tenants, tb, hipMemcpyHostToDevice, e->stream));
-        if ((rc = upload(e, e->cur->s_topic_tenant, filter_tenant, sizeof(uint32_t) * n_filters))) return rc;
-        if (pb) HIPCHK(e, hipMemcpyAsync(e->cur->s_topics.p, filters, pb, hipMemcpyHostToDevice, e->stream));
-        if ((rc = upload(e, e->cur->s_topic_off, filter_off, sizeof(uint32_t) * (n_filters + 1)))) return rc;
-        HIPCHK(e, e->cur->s_row_ptr.ensure(sizeof(uint32_t) * (n_filters + 1)));
-        HIPCHK(e, e->cur->b_total.ensure(sizeof(unsigned long long)));
-        dev_cap = d_ids ? d_ids_cap : std::max<uint64_t>(e->cur->s_ids.cap / 4, std::max<uint64_t>((uint64_t)n_filters * 16, 1024));
-        if (!d_ids) HIPCHK(e, e->cur->s_ids.ensure(dev_cap * 4));
+        if ((rc = stage_input(e, S, in, e->stream, d_ids ? 0 : 16, d))) return rc;
     }
-    for (int attempt = 0; attempt < 3; attempt++) {
-        rc = bmq_retain_match_batch_dev(e, e->cur->s_tenants.as<uint8_t>(), e->cur->s_tenant_off.as<uint32_t>(), n_tenants,
-                                        e->cur->s_topic_tenant.as<uint32_t>(), e->cur->s_topics.as<uint8_t>(), e->cur->s_topic_off.as<uint32_t>(),
-                                        n_filters, d_row ? d_row : e->cur->s_row_ptr.as<uint32_t>(), d_ids ? d_ids : e->cur->s_ids.as<uint32_t>(), dev_cap,
-                                        e->cur->b_total.as<uint64_t>());
-        if (rc) return rc;
+    rc = bmq_retain_match_batch_dev(e, d.tenants, d.tenant_off, d.n_tenants, d.row_tenant, d.rows, d.row_off, d.n_rows,
+                                    d_row ? d_row : S.s_row_ptr.as<uint32_t>(), d_ids ? d_ids : S.s_ids.as<uint32_t>(),
+                                    d_ids ? d_ids_cap : S.dev_cap, S.b_total.as<uint64_t>());
+    for (int attempt = 0; rc == BMQ_OK; attempt++) { // launched: finish; the slot's id buffer too small: once more with the size it told
         rc = bmq_match_finish(e, total);
-        if (rc == BMQ_E_NOSPACE && !d_ids) { // the engine's own id buffer was too small: it knows the size now
-            std::lock_guard<std::mutex> g(e->mu);
-            dev_cap = *total;
-            HIPCHK(e, e->cur->s_ids.ensure(dev_cap * 4));
-            continue;
-        }
-        return rc;
+        if (rc != BMQ_E_NOSPACE || d_ids) break;
+        if (attempt == 2) return set_err(e, BMQ_E_NOMEM, "device output buffer growth did not converge");
+        std::lock_guard<std::mutex> g(e->mu);
+        rc = regrow_ids_and_relaunch(e, S, *total, BLOCKING_REGROW);
     }
-    return set_err(e, BMQ_E_NOMEM, "device output buffer growth did not converge");
+    return rc;
 }
 
-static int retain_host_args_ok(bmq_engine* e, const uint8_t* tenants, const uint32_t* tenant_off, uint32_t n_tenants,
-                               const uint32_t* filter_tenant, const uint8_t* filters, const uint32_t* filter_off,
-                               const uint32_t* out_row_ptr, const uint64_t* out_needed) {
-    if (e->device < 0) return set_err(e, BMQ_E_NODEVICE, "engine is host-only: matching requires a gfx950 device");
-    if (!e->rbuilt) return set_err(e, BMQ_E_STATE, "bmq_retain_rebuild has not been called");
+// An empty batch with somewhere to put the empty CSR needs no device work: answered here (true; *rc -- a host-only engine still says
+// what it is).
+static bool retain_empty_batch(bmq_engine* e, uint32_t n_filters, uint32_t* out_row_ptr, uint64_t* out_needed, int* rc) {
+    if (n_filters != 0 || !out_row_ptr || !out_needed) return false;
+    *out_needed = 0;
+    out_row_ptr[0] = 0;
+    *rc = e->device < 0 ? BMQ_E_NODEVICE : BMQ_OK;
+    return true;
+}
+
+static int retain_host_args_ok(bmq_engine* e, const BatchInput& in, const uint32_t* out_row_ptr, const uint64_t* out_needed) {
+    if (int rc = check_retain_ready(e)) return rc;
     if (!out_row_ptr || !out_needed) return set_err(e, BMQ_E_INVAL, "null output pointer");
-    if (!filters || !filter_off || !filter_tenant || (n_tenants && (!tenants || !tenant_off)))
+    if (!in.rows || !in.row_off || !in.row_tenant || (in.n_tenants && (!in.tenants || !in.tenant_off)))
         return set_err(e, BMQ_E_INVAL, "null input pointer");
     return BMQ_OK;
 }
@@ -1011,16 +981,13 @@ int bmq_retain_match_batch(bmq_engine* e, const uint8_t* tenants, const uint32_t
                            uint64_t* out_needed) {
     std::unique_lock<std::recursive_mutex> api_lock;
     if (e) api_lock = std::unique_lock<std::recursive_mutex>(e->api);
+    const BatchInput in{tenants, tenant_off, n_tenants, filter_tenant, filters, filter_off, n_filters};
+    int rc;
     if (!e) return BMQ_E_INVAL;
-    if (n_filters == 0 && out_row_ptr && out_needed) {
-        *out_needed = 0;
-        out_row_ptr[0] = 0;
-        return e->device < 0 ? BMQ_E_NODEVICE : BMQ_OK;
-    }
-    int rc = retain_host_args_ok(e, tenants, tenant_off, n_tenants, filter_tenant, filters, filter_off, out_row_ptr, out_needed);
-    if (rc) return rc;
+    if (retain_empty_batch(e, n_filters, out_row_ptr, out_needed, &rc)) return rc;
+    if ((rc = retain_host_args_ok(e, in, out_row_ptr, out_needed))) return rc;
     uint64_t total = 0;
-    rc = retain_match_to_scratch(e, tenants, tenant_off, n_tenants, filter_tenant, filters, filter_off, n_filters, &total, nullptr, nullptr, 0);
+    rc = retain_match_to_scratch(e, in, &total, nullptr, nullptr, 0);
     *out_needed = total;
     if (rc) return rc;
     std::lock_guard<std::mutex> g(e->mu);
@@ -1036,14 +1003,11 @@ int bmq_retain_match_limited(bmq_engine* e, const uint8_t* tenants, const uint32
                              uint64_t out_capacity, uint64_t* out_needed, uint32_t* out_match_count) {
     std::unique_lock<std::recursive_mutex> api_lock;
     if (e) api_lock = std::unique_lock<std::recursive_mutex>(e->api);
+    const BatchInput in{tenants, tenant_off, n_tenants, filter_tenant, filters, filter_off, n_filters};
+    int rc;
     if (!e) return BMQ_E_INVAL;
-    if (n_filters == 0 && out_row_ptr && out_needed) {
-        *out_needed = 0;
-        out_row_ptr[0] = 0;
-        return e->device < 0 ? BMQ_E_NODEVICE : BMQ_OK;
-    }
-    int rc = retain_host_args_ok(e, tenants, tenant_off, n_tenants, filter_tenant, filters, filter_off, out_row_ptr, out_needed);
-    if (rc) return rc;
+    if (retain_empty_batch(e, n_filters, out_row_ptr, out_needed, &rc)) return rc;
+    if ((rc = retain_host_args_ok(e, in, out_row_ptr, out_needed))) return rc;
     if (!limit) return set_err(e, BMQ_E_INVAL, "null limit array");
     uint32_t max_lim = 0;
     for (uint32_t i = 0; i < n_filters; i++) max_lim = std::max(max_lim, limit[i]);
@@ -1068,15 +1032,14 @@ int bmq_retain_match_limited(bmq_engine* e, const uint8_t* tenants, const uint32
             HIPCHK(e, e->cur->s_lim_ids.ensure(sizeof(uint32_t) * (size_t)n_filters * std::max(1u, max_lim)));
             e->rlim = RetainLimit{true, d_limit, now_ms, e->cur->s_lim_tmp.as<uint32_t>(), d_kept, d_counts};
         }
-        rc = retain_match_to_scratch(e, tenants, tenant_off, n_tenants, filter_tenant, filters, filter_off, n_filters, &total, d_new_row,
-                                     e->cur->s_lim_ids.as<uint32_t>(), (uint64_t)n_filters * std::max(1u, max_lim));
+        rc = retain_match_to_scratch(e, in, &total, d_new_row, e->cur->s_lim_ids.as<uint32_t>(), (uint64_t)n_filters * std::max(1u, max_lim));
         {
             std::lock_guard<std::mutex> g(e->mu);
             e->rlim.active = false;
         }
         if (rc) return rc;
     } else { // large limits: the complete CSR, then the first limit[i] live ids of every row
-        rc = retain_match_to_scratch(e, tenants, tenant_off, n_tenants, filter_tenant, filters, filter_off, n_filters, &total, nullptr, nullptr, 0);
+        rc = retain_match_to_scratch(e, in, &total, nullptr, nullptr, 0);
         if (rc) return rc;
         std::lock_guard<std::mutex> g(e->mu);
         HIPCHK(e, e->cur->s_lim_ids.ensure(sizeof(uint32_t) * std::max<uint64_t>(total, 1)));
