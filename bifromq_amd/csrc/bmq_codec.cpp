@@ -1,6 +1,8 @@
 // bmq_codec.cpp -- route-key codec on the host (see bmq_codec.h).
 #include "bmq_codec.h"
 
+#include "bmq_key_core.h"
+
 #include <cstring>
 #include <vector>
 
@@ -13,36 +15,7 @@ namespace bmq {
 // SCHEMA/KVSchemaUtil.java:127-130).
 int32_t java_string_hash(std::string_view s) {
     uint32_t h = 0;
-    const size_t n = s.size();
-    size_t i = 0;
-    while (i < n) {
-        const uint32_t c = (uint8_t)s[i];
-        uint32_t cp;
-        if (c < 0x80) {
-            cp = c;
-            i += 1;
-        } else if ((c & 0xE0) == 0xC0 && i + 1 < n) {
-            cp = ((c & 0x1F) << 6) | ((uint8_t)s[i + 1] & 0x3F);
-            i += 2;
-        } else if ((c & 0xF0) == 0xE0 && i + 2 < n) {
-            cp = ((c & 0x0F) << 12) | (((uint8_t)s[i + 1] & 0x3F) << 6) | ((uint8_t)s[i + 2] & 0x3F);
-            i += 3;
-        } else if ((c & 0xF8) == 0xF0 && i + 3 < n) {
-            cp = ((c & 0x07) << 18) | (((uint8_t)s[i + 1] & 0x3F) << 12) | (((uint8_t)s[i + 2] & 0x3F) << 6) |
-                 ((uint8_t)s[i + 3] & 0x3F);
-            i += 4;
-        } else {
-            cp = 0xFFFD;
-            i += 1;
-        }
-        if (cp >= 0x10000) { // surrogate pair
-            cp -= 0x10000;
-            h = 31u * h + (0xD800u + (cp >> 10));
-            h = 31u * h + (0xDC00u + (cp & 0x3FF));
-        } else {
-            h = 31u * h + cp;
-        }
-    }
+    for_each_utf16_unit((const uint8_t*)s.data(), s.size(), [&](uint32_t u) { h = 31u * h + u; }); // (the walk: bmq_key_core.h)
     return (int32_t)h;
 }
 
@@ -93,35 +66,6 @@ bool decode_route_key(std::string_view k, RouteKeyParts& out) {
 // retain store key schema
 // ------------------------------------------------------------------------------------------------------------
 namespace {
-template <class F> void for_each_utf16_unit(std::string_view s, F&& f) { // same decoding as java_string_hash
-    const size_t n = s.size();
-    size_t i = 0;
-    while (i < n) {
-        const uint32_t c = (uint8_t)s[i];
-        uint32_t cp;
-        if (c < 0x80) {
-            cp = c;
-            i += 1;
-        } else if ((c & 0xE0) == 0xC0 && i + 1 < n) {
-            cp = ((c & 0x1F) << 6) | ((uint8_t)s[i + 1] & 0x3F);
-            i += 2;
-        } else if ((c & 0xF0) == 0xE0 && i + 2 < n) {
-            cp = ((c & 0x0F) << 12) | (((uint8_t)s[i + 1] & 0x3F) << 6) | ((uint8_t)s[i + 2] & 0x3F);
-            i += 3;
-        } else if ((c & 0xF8) == 0xF0 && i + 3 < n) {
-            cp = ((c & 0x07) << 18) | (((uint8_t)s[i + 1] & 0x3F) << 12) | (((uint8_t)s[i + 2] & 0x3F) << 6) | ((uint8_t)s[i + 3] & 0x3F);
-            i += 4;
-        } else {
-            cp = 0xFFFD;
-            i += 1;
-        }
-        if (cp >= 0x10000) {
-            cp -= 0x10000;
-            f(0xD800u + (cp >> 10));
-            f(0xDC00u + (cp & 0x3FF));
-        } else f(cp);
-    }
-}
 std::vector<std::string_view> split_levels(std::string_view s) { // TopicUtil.parse(topic, false): empty levels kept
     std::vector<std::string_view> out;
     size_t b = 0;
@@ -139,14 +83,8 @@ void tenant_begin_key(std::string& k, std::string_view tenant) { // 0x00 | u16be
 }
 } // namespace
 
-uint8_t retain_level_hash_byte(std::string_view level) {
-    uint32_t h = 0x811C9DC5u;
-    for_each_utf16_unit(level, [&](uint32_t u) {
-        h ^= u;
-        h *= 0x01000193u;
-    });
-    return (uint8_t)(h & 0xFF);
-}
+// (the UTF-16 walk and the FNV-1a step are bmq_key_core.h's: the key kernels run the same definition on the device)
+uint8_t retain_level_hash_byte(std::string_view level) { return level_hash_byte((const uint8_t*)level.data(), level.size()); }
 
 std::string retain_message_key(std::string_view tenant, std::string_view topic) {
     const auto levels = split_levels(topic);

@@ -225,6 +225,19 @@ __global__ __launch_bounds__(BK) void k_r_node_write(RetainMut m, const uint32_t
     const uint32_t i = blockIdx.x * BK + threadIdx.x;
     if (i < n) ov_node_write_one(m, nodes, i, offs, out);
 }
+// id -> retainMessageKey (key_len_one / key_write_one, bmq_retain_core.h): one lane per id.  lens[n] = 0 is the scan's last input.  A lane
+// composes its whole key -- header, LevelHash bytes, escaped topic -- byte by byte at out + offs[i]: keys are 10-300 bytes at arbitrary byte
+// offsets, the level hashes are a serial walk over the same bytes, and neighbouring lanes write neighbouring keys, so the partial lines of a
+// wave meet in L2 before they leave for HBM (shape, measurements and resource usage: profiles/retain_keys/README.md).
+__global__ __launch_bounds__(256) void k_r_key_len(RetainMut m, RetainKeyStore ks, const uint32_t* ids, uint32_t n, unsigned long long* lens) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) lens[i] = key_len_one(m, ks, ids[i]);
+    else if (i == n) lens[i] = 0ull;
+}
+__global__ __launch_bounds__(256) void k_r_key_write(RetainMut m, RetainKeyStore ks, const uint32_t* ids, uint32_t n, const unsigned long long* offs, uint8_t* out) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) key_write_one(m, ks, ids[i], out + offs[i], offs[i + 1] - offs[i]);
+}
 __global__ __launch_bounds__(64) void k_r_find_tenant(RetainMut m, const uint8_t* name, uint32_t len, uint32_t* out) {
     if (threadIdx.x || blockIdx.x) return;
     LevelScan lv;
@@ -589,6 +602,19 @@ struct DevExec {
     }
     bool r_find_tenant(const RetainMut& m, const uint8_t* name, uint32_t len, uint32_t* out) {
         hipLaunchKernelGGL(k_r_find_tenant, dim3(1), dim3(64), 0, stream, m, name, len, out);
+        return launched();
+    }
+    // lens[0 .. n] = key lengths of ids[0, n) and a closing 0, offs[0 .. n] = their exclusive 64-bit sums (offs[n] = all key bytes)
+    bool r_key_offsets(const RetainMut& m, const RetainKeyStore& ks, const uint32_t* ids, uint32_t n, unsigned long long* lens, unsigned long long* offs) {
+        hipLaunchKernelGGL(k_r_key_len, grid((unsigned long long)n + 1, 256), dim3(256), 0, stream, m, ks, ids, n, lens);
+        if (!launched()) return false;
+        size_t bytes = 0;
+        if (!BMQ_X(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, lens, offs, (int)n + 1, stream))) return false;
+        if (!ensure_tmp(bytes)) return false;
+        return BMQ_X(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, lens, offs, (int)n + 1, stream));
+    }
+    bool r_key_write(const RetainMut& m, const RetainKeyStore& ks, const uint32_t* ids, uint32_t n, const unsigned long long* offs, uint8_t* out) {
+        hipLaunchKernelGGL(k_r_key_write, grid(n, 256), dim3(256), 0, stream, m, ks, ids, n, offs, out);
         return launched();
     }
 #undef BMQ_X

@@ -298,6 +298,20 @@ struct HostExec {
         par(n, [&](size_t i) { ov_node_write_one(m, nodes, (uint32_t)i, offs, out); });
         return true;
     }
+    bool r_key_offsets(const RetainMut& m, const RetainKeyStore& ks, const uint32_t* ids, uint32_t n, unsigned long long* lens, unsigned long long* offs) {
+        par(n, [&](size_t i) { lens[i] = key_len_one(m, ks, ids[i]); });
+        lens[n] = 0ull;
+        unsigned long long run = 0;
+        for (size_t i = 0; i <= n; i++) {
+            offs[i] = run;
+            run += lens[i];
+        }
+        return true;
+    }
+    bool r_key_write(const RetainMut& m, const RetainKeyStore& ks, const uint32_t* ids, uint32_t n, const unsigned long long* offs, uint8_t* out) {
+        par(n, [&](size_t i) { key_write_one(m, ks, ids[i], out + offs[i], offs[i + 1] - offs[i]); });
+        return true;
+    }
     bool r_find_tenant(const RetainMut& m, const uint8_t* name, uint32_t len, uint32_t* out) {
         LevelScan lv;
         unsigned long long pos = 0;

@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "bmq_build_core.h"
+#include "bmq_key_core.h"
 #include "bmq_retain.h"
 
 namespace bmq {
@@ -469,6 +470,94 @@ BMQ_HD void ov_topic_write_one(const RetainMut& m, const uint32_t* ids, uint32_t
         if (n.parent == 0u) break; // that was the tenant id
         if (m.onodes[n.parent].parent != 0u) out[--end] = '/';
         t = n.parent;
+    }
+}
+// ------------------------------------------------------------------------------------------------------------
+// id -> retainMessageKey (RetainStoreCoProc.match: reader.get(retainMessageKey(tenant, topic)) per hit, RS/RetainStoreCoProc.java:167-190;
+// gc deletes the same keys, :258-277).  The encoder is bmq_key_core.h's.
+// ------------------------------------------------------------------------------------------------------------
+// The strings of the BULK-LOADED ids of one generation in exec memory (the index itself holds no parent pointers and no node -> label map:
+// bmq_retain.h).  An id is a rank, so the topics lie back to back in id order and a tenant is a rank range.  Built on first use from the
+// host's copy of the load, dropped with the generation (RetainDyn: bmq_retain_dyn.h).  Overlay ids need none: their ONode chain has parents.
+struct RetainKeyStore {
+    const uint8_t* topics;               // topic bytes of id 0, 1, ... back to back
+    const unsigned long long* topic_off; // [n_ids + 1]
+    const uint32_t* tenant_lo;           // [n_tenants + 1] first rank of every tenant that has topics, ascending; [n_tenants] = n_ids
+    const uint8_t* tenants;              // their ids, back to back
+    const uint32_t* tenant_off;          // [n_tenants + 1]
+    uint32_t n_tenants;
+    uint32_t n_ids;                      // == RetainMut.base_n of the generation it was built for (0: no store / nothing bulk-loaded)
+};
+// the tenant (index into tenant_lo) that owns rank id; id < ks.n_ids, so ks.n_tenants >= 1
+BMQ_HD uint32_t key_store_tenant(const RetainKeyStore& ks, uint32_t id) {
+    uint32_t lo = 0, hi = ks.n_tenants; // tenant_lo[lo] <= id < tenant_lo[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (ks.tenant_lo[mid] <= id) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// is `id` a topic that is retained now, and whose strings this call can reach?  Decided from dead_bits where the index lives.
+BMQ_HD bool key_id_live(const RetainMut& m, const RetainKeyStore& ks, uint32_t id) {
+    if (id >= m.id_cap || id_dead(m.dead_bits, id)) return false; // out of range, never handed out (those bits are set), or removed
+    if (id < m.base_n) return id < ks.n_ids;
+    const uint32_t node = m.id_node[id];
+    return node != NONE && node < m.ov_cap && node != 0u;
+}
+// length of the key of ids[i]; 0: the id is out of range, was never handed out, or its topic is not retained now
+BMQ_HD unsigned long long key_len_one(const RetainMut& m, const RetainKeyStore& ks, uint32_t id) {
+    if (!key_id_live(m, ks, id)) return 0ull;
+    if (id < m.base_n) {
+        const uint32_t t = key_store_tenant(ks, id);
+        const unsigned long long pb = ks.topic_off[id], pe = ks.topic_off[id + 1];
+        uint32_t levels = 1;
+        for (unsigned long long p = pb; p < pe; p++) levels += ks.topics[p] == '/';
+        return retain_key_len(ks.tenant_off[t + 1] - ks.tenant_off[t], (uint32_t)(pe - pb), levels);
+    }
+    uint32_t total = 0, levels = 0, t = m.id_node[id]; // as ov_topic_len_one: up the chain to the tenant's node
+    while (m.onodes[t].parent != 0u) {
+        total += m.onodes[t].str_len & ~ON_SYS;
+        levels++;
+        t = m.onodes[t].parent;
+    }
+    if (levels == 0) return 0ull; // (a tenant node carries no topic)
+    return retain_key_len(m.onodes[t].str_len & ~ON_SYS, total + levels - 1, levels);
+}
+// the key of `id` into out[0, len): len = key_len_one(m, ks, id) of the same state (nothing is written for len 0)
+BMQ_HD void key_write_one(const RetainMut& m, const RetainKeyStore& ks, uint32_t id, uint8_t* out, unsigned long long len) {
+    if (len == 0 || !key_id_live(m, ks, id)) return;
+    if (id < m.base_n) {
+        const uint32_t t = key_store_tenant(ks, id);
+        const uint32_t tl = ks.tenant_off[t + 1] - ks.tenant_off[t];
+        const unsigned long long pb = ks.topic_off[id];
+        const uint32_t pl = (uint32_t)(ks.topic_off[id + 1] - pb);
+        const uint32_t levels = (uint32_t)(len - 5u - tl - pl);
+        const uint32_t at = retain_key_head(out, ks.tenants + ks.tenant_off[t], tl);
+        retain_key_tail(out + at, ks.topics + pb, pl, levels);
+        return;
+    }
+    // an overlay topic: one label per node, the last level first (as ov_topic_write_one).  The hash bytes fill up from the back too.
+    uint32_t levels = 0, t = m.id_node[id];
+    while (m.onodes[t].parent != 0u) {
+        levels++;
+        t = m.onodes[t].parent;
+    }
+    const ONode& tn = m.onodes[t];
+    const uint32_t tl = tn.str_len & ~ON_SYS;
+    uint32_t at = retain_key_head(out, m.opool + tn.str_off, tl);
+    out[at] = (uint8_t)((levels >> 8) & 0xFF);
+    out[at + 1] = (uint8_t)(levels & 0xFF);
+    uint8_t* hash = out + at + 2;
+    unsigned long long end = len;
+    uint32_t lv = levels;
+    for (uint32_t n = m.id_node[id]; n != t; n = m.onodes[n].parent) {
+        const ONode& o = m.onodes[n];
+        const uint32_t l = o.str_len & ~ON_SYS;
+        end -= l;
+        for (uint32_t k = 0; k < l; k++) out[end + k] = m.opool[o.str_off + k];
+        hash[--lv] = level_hash_byte(m.opool + o.str_off, l);
+        if (o.parent != t) out[--end] = 0; // TopicUtil.escape of the '/' in front of this level
     }
 }
 // The scan of RetainStoreCoProc.gc (RS/RetainStoreCoProc.java:257-277): flag[id] = 1 for every retained id whose message has

@@ -279,6 +279,90 @@ public:
             return xfail();
         return true;
     }
+    // ---- id -> retainMessageKey (key_len_one / key_write_one).  The strings of the bulk-loaded ids come from a store in exec memory that is
+    // built on first use in a generation (or by keys_prepare) from the host's copy of the load and dropped with the generation: reset() frees
+    // it, so a bulk load that nobody asks keys of pays nothing for it.  bytes (may be null) = what the store holds in exec memory.
+    bool keys_prepare(const RetainIndexHost& h, uint64_t* bytes) {
+        error.clear();
+        if (!ready) return fail("the retained-topic index has not been built");
+        if (!ks_ready) {
+            if (h.n_topics != base_n) return fail("the bulk load on the host is not the one this generation was built from");
+            std::vector<uint8_t> topics, tenants;
+            std::vector<unsigned long long> toff((size_t)base_n + 1, 0);
+            std::vector<uint32_t> lo, tnoff{0};
+            uint32_t rank = 0;
+            for (const RTenantState* t : h.order) { // by id_base: a tenant is the rank range [id_base, id_base + topics)
+                if (t->topics.empty()) continue;
+                if (t->id_base != rank || (uint64_t)rank + t->topics.size() > base_n) return fail("the tenants of the bulk load do not tile its id range");
+                lo.push_back(rank);
+                tenants.insert(tenants.end(), t->name.begin(), t->name.end());
+                tnoff.push_back((uint32_t)tenants.size());
+                for (const std::string& p : t->topics) {
+                    topics.insert(topics.end(), p.begin(), p.end());
+                    toff[++rank] = topics.size();
+                }
+            }
+            if (rank != base_n) return fail("the tenants of the bulk load do not tile its id range");
+            lo.push_back(base_n);
+            drop_key_store();
+            ks_n_tenants = (uint32_t)lo.size() - 1;
+            ks_topics = (uint8_t*)x.alloc(topics.size() + 16);
+            ks_tenants = (uint8_t*)x.alloc(tenants.size() + 16);
+            ks_topic_off = take<unsigned long long>(toff.size());
+            ks_tenant_lo = take<uint32_t>(lo.size());
+            ks_tenant_off = take<uint32_t>(tnoff.size());
+            if (!ks_topics || !ks_tenants || !ks_topic_off || !ks_tenant_lo || !ks_tenant_off) {
+                drop_key_store();
+                return fail("out of memory (retain key store)");
+            }
+            if (!x.copy_in_async(ks_topics, topics.data(), topics.size()) || !x.copy_in_async(ks_tenants, tenants.data(), tenants.size()) ||
+                !x.copy_in_async(ks_topic_off, toff.data(), 8 * toff.size()) || !x.copy_in_async(ks_tenant_lo, lo.data(), 4 * lo.size()) ||
+                !x.copy_in_async(ks_tenant_off, tnoff.data(), 4 * tnoff.size()) || !x.sync()) {
+                drop_key_store();
+                return xfail();
+            }
+            ks_bytes = topics.size() + tenants.size() + 8 * toff.size() + 4 * lo.size() + 4 * tnoff.size();
+            ks_ready = true;
+        }
+        if (bytes) *bytes = ks_bytes;
+        return true;
+    }
+    bool keys_ready() const { return ks_ready; }
+    // keys of ids[0, n) -- exec memory: the kept ids of a match never leave the device -- composed on the executor's stream behind whatever is
+    // in flight: offs[0 .. n] (exec memory) = where every key starts, total = offs[n], bytes (exec memory) = the keys back to back.
+    // Returns after the lengths are known (one read of `total`); the write kernel is in the stream.
+    bool keys_compose(const RetainIndexHost& h, const uint32_t* ids, uint32_t n, const unsigned long long*& offs, const uint8_t*& bytes, uint64_t& total) {
+        total = 0;
+        if (!keys_prepare(h, nullptr)) return false;
+        if (!ensure(k_off, k_off_cap, 16 * ((size_t)n + 1))) return false;
+        unsigned long long* lens = (unsigned long long*)k_off;
+        unsigned long long* o = lens + n + 1;
+        const RetainMut m = mut();
+        const RetainKeyStore ks = key_store();
+        unsigned long long t = 0;
+        if (!x.r_key_offsets(m, ks, ids, n, lens, o) || !x.copy_out(&t, o + n, 8)) return xfail();
+        if (!ensure(k_out, k_out_cap, (size_t)t + 16)) return false;
+        if (t && !x.r_key_write(m, ks, ids, n, o, k_out)) return xfail();
+        offs = o;
+        bytes = k_out;
+        total = t;
+        return true;
+    }
+    // ... for ids in host memory, with the buffer protocol of bmq_retain_message_keys: out_off[0 .. n] always, the bytes if they fit
+    bool keys_by_id(const RetainIndexHost& h, const uint32_t* ids, uint32_t n, uint8_t* out, uint64_t cap, unsigned long long* out_off, bool& nospace) {
+        nospace = false;
+        if (!ensure(k_ids, k_ids_cap, 4 * (size_t)n + 16)) return false;
+        if (!x.copy_in_async(k_ids, ids, 4 * (size_t)n)) return xfail();
+        const unsigned long long* offs = nullptr;
+        const uint8_t* bytes = nullptr;
+        uint64_t total = 0;
+        if (!keys_compose(h, (const uint32_t*)k_ids, n, offs, bytes, total)) return false;
+        if (!x.copy_out(out_off, offs, 8 * ((size_t)n + 1))) return xfail();
+        nospace = total > cap || (total && !out);
+        if (!nospace && total && !x.copy_out(out, bytes, total)) return xfail();
+        return true;
+    }
+
     bool topic_info(uint32_t id, unsigned long long& ts, uint32_t& expiry, unsigned long long& expire_at_ms, bool& live) {
         if (!ready || id >= info.id_bound) return fail("no such retained topic");
         unsigned long long w = 0;
@@ -322,8 +406,10 @@ public:
 
     void drop() {
         for (void* p : {(void*)d_expire_at, (void*)d_ts, (void*)d_expiry, (void*)d_id_node, (void*)d_id_tnode, (void*)d_dead, (void*)d_rank, (void*)d_last,
-                        (void*)d_nodes, (void*)d_edges, (void*)d_pool, (void*)d_ctr, (void*)d_stage, (void*)q_buf, (void*)o_buf})
+                        (void*)d_nodes, (void*)d_edges, (void*)d_pool, (void*)d_ctr, (void*)d_stage, (void*)q_buf, (void*)o_buf, (void*)k_ids, (void*)k_off,
+                        (void*)k_out})
             if (p) x.release(p);
+        drop_key_store(); // (its ids are the ranks of the generation that ends here)
         d_expire_at = d_ts = nullptr;
         d_expiry = d_id_node = d_id_tnode = nullptr;
         d_dead = nullptr;
@@ -333,9 +419,9 @@ public:
         d_edges = nullptr;
         d_pool = nullptr;
         d_ctr = nullptr;
-        d_stage = q_buf = o_buf = nullptr;
+        d_stage = q_buf = o_buf = k_ids = k_off = k_out = nullptr;
         id_cap = ov_cap = pool_cap = edge_slots = 0;
-        stage_cap = q_cap = o_cap = 0;
+        stage_cap = q_cap = o_cap = k_ids_cap = k_off_cap = k_out_cap = 0;
         ready = false;
     }
 
@@ -356,6 +442,37 @@ private:
     uint8_t *d_stage = nullptr, *q_buf = nullptr, *o_buf = nullptr;
     size_t stage_cap = 0, q_cap = 0, o_cap = 0;
     unsigned long long seq = 0;
+    // the key store (RetainKeyStore) and the scratch of the key calls
+    uint8_t *ks_topics = nullptr, *ks_tenants = nullptr;
+    unsigned long long* ks_topic_off = nullptr;
+    uint32_t *ks_tenant_lo = nullptr, *ks_tenant_off = nullptr;
+    uint32_t ks_n_tenants = 0;
+    uint64_t ks_bytes = 0;
+    bool ks_ready = false;
+    uint8_t *k_ids = nullptr, *k_off = nullptr, *k_out = nullptr;
+    size_t k_ids_cap = 0, k_off_cap = 0, k_out_cap = 0;
+
+    void drop_key_store() {
+        for (void* p : {(void*)ks_topics, (void*)ks_tenants, (void*)ks_topic_off, (void*)ks_tenant_lo, (void*)ks_tenant_off})
+            if (p) x.release(p);
+        ks_topics = ks_tenants = nullptr;
+        ks_topic_off = nullptr;
+        ks_tenant_lo = ks_tenant_off = nullptr;
+        ks_n_tenants = 0;
+        ks_bytes = 0;
+        ks_ready = false;
+    }
+    RetainKeyStore key_store() const {
+        RetainKeyStore ks{};
+        ks.topics = ks_topics;
+        ks.topic_off = ks_topic_off;
+        ks.tenant_lo = ks_tenant_lo;
+        ks.tenants = ks_tenants;
+        ks.tenant_off = ks_tenant_off;
+        ks.n_tenants = ks_n_tenants;
+        ks.n_ids = ks_ready ? base_n : 0u;
+        return ks;
+    }
 
     static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
     uint32_t n_words() const { return (id_cap + 63) / 64; }

@@ -997,23 +997,17 @@ int bmq_retain_match_batch(bmq_engine* e, const uint8_t* tenants, const uint32_t
     return BMQ_OK;
 }
 
-int bmq_retain_match_limited(bmq_engine* e, const uint8_t* tenants, const uint32_t* tenant_off, uint32_t n_tenants,
-                             const uint32_t* filter_tenant, const uint8_t* filters, const uint32_t* filter_off,
-                             uint32_t n_filters, const uint32_t* limit, uint64_t now_ms, uint32_t* out_row_ptr, uint32_t* out_topic_ids,
-                             uint64_t out_capacity, uint64_t* out_needed, uint32_t* out_match_count) {
-    std::unique_lock<std::recursive_mutex> api_lock;
-    if (e) api_lock = std::unique_lock<std::recursive_mutex>(e->api);
-    const BatchInput in{tenants, tenant_off, n_tenants, filter_tenant, filters, filter_off, n_filters};
+// The device part of RetainStoreCoProc.match(limit, now) for a host batch (the arguments were checked): the kept ids into e->cur->s_lim_ids, their
+// row pointers (n + 1) into *out_d_row, the match counts (n) into *out_d_counts -- all device memory, the last kernels possibly still in the
+// stream.  What bmq_retain_match_limited copies out, and what bmq_retain_keys_match composes the keys of where it lies.
+static int retain_limited_to_scratch(bmq_engine* e, const BatchInput& in, const uint32_t* limit, uint64_t now_ms, uint32_t** out_d_row, uint32_t** out_d_counts) {
+    const uint32_t n_filters = in.n_rows;
     int rc;
-    if (!e) return BMQ_E_INVAL;
-    if (retain_empty_batch(e, n_filters, out_row_ptr, out_needed, &rc)) return rc;
-    if ((rc = retain_host_args_ok(e, in, out_row_ptr, out_needed))) return rc;
-    if (!limit) return set_err(e, BMQ_E_INVAL, "null limit array");
     uint32_t max_lim = 0;
     for (uint32_t i = 0; i < n_filters; i++) max_lim = std::max(max_lim, limit[i]);
     uint64_t total = 0;
     uint32_t* d_limit;
-    uint32_t* d_counts;
+    uint32_t* d_counts = nullptr;
     uint32_t* d_kept;
     {
         std::lock_guard<std::mutex> g(e->mu);
@@ -1025,6 +1019,8 @@ int bmq_retain_match_limited(bmq_engine* e, const uint8_t* tenants, const uint32
         HIPCHK(e, hipMemcpyAsync(d_limit, limit, sizeof(uint32_t) * n_filters, hipMemcpyHostToDevice, e->stream));
     }
     uint32_t* d_new_row = d_kept + n_filters + 1; // (kept has n + 1 entries: the scan's last input)
+    *out_d_row = d_new_row;
+    *out_d_counts = d_counts;
     if (max_lim <= LIM_FAST) { // walk + select: nothing is expanded
         {
             std::lock_guard<std::mutex> g(e->mu);
@@ -1051,6 +1047,23 @@ int bmq_retain_match_limited(bmq_engine* e, const uint8_t* tenants, const uint32
                            e->cur->s_ids.as<uint32_t>(), ex, (unsigned long long)now_ms, n_filters, e->cur->s_lim_ids.as<uint32_t>());
         HIPCHK(e, hipGetLastError());
     }
+    return BMQ_OK;
+}
+
+int bmq_retain_match_limited(bmq_engine* e, const uint8_t* tenants, const uint32_t* tenant_off, uint32_t n_tenants,
+                             const uint32_t* filter_tenant, const uint8_t* filters, const uint32_t* filter_off,
+                             uint32_t n_filters, const uint32_t* limit, uint64_t now_ms, uint32_t* out_row_ptr, uint32_t* out_topic_ids,
+                             uint64_t out_capacity, uint64_t* out_needed, uint32_t* out_match_count) {
+    std::unique_lock<std::recursive_mutex> api_lock;
+    if (e) api_lock = std::unique_lock<std::recursive_mutex>(e->api);
+    const BatchInput in{tenants, tenant_off, n_tenants, filter_tenant, filters, filter_off, n_filters};
+    int rc;
+    if (!e) return BMQ_E_INVAL;
+    if (retain_empty_batch(e, n_filters, out_row_ptr, out_needed, &rc)) return rc;
+    if ((rc = retain_host_args_ok(e, in, out_row_ptr, out_needed))) return rc;
+    if (!limit) return set_err(e, BMQ_E_INVAL, "null limit array");
+    uint32_t *d_new_row = nullptr, *d_counts = nullptr;
+    if ((rc = retain_limited_to_scratch(e, in, limit, now_ms, &d_new_row, &d_counts))) return rc;
     std::lock_guard<std::mutex> g(e->mu);
     HIPCHK(e, hipMemcpyAsync(out_row_ptr, d_new_row, sizeof(uint32_t) * (n_filters + 1), hipMemcpyDeviceToHost, e->stream));
     if (out_match_count) HIPCHK(e, hipMemcpyAsync(out_match_count, d_counts, sizeof(uint32_t) * n_filters, hipMemcpyDeviceToHost, e->stream));
@@ -1059,6 +1072,95 @@ int bmq_retain_match_limited(bmq_engine* e, const uint8_t* tenants, const uint32
     *out_needed = kept;
     if (kept > out_capacity || (kept && !out_topic_ids)) return set_err(e, BMQ_E_NOSPACE, "output buffer too small");
     if (kept) HIPCHK(e, hipMemcpy(out_topic_ids, e->cur->s_lim_ids.p, sizeof(uint32_t) * kept, hipMemcpyDeviceToHost));
+    return BMQ_OK;
+}
+
+// ---- id -> retainMessageKey on the device (key_len_one / key_write_one: bmq_retain_core.h; the store of the bulk-loaded strings: RetainDyn) ----
+int bmq_retain_keys_prepare(bmq_engine* e, uint64_t* out_store_bytes) {
+    std::unique_lock<std::recursive_mutex> api_lock;
+    if (e) api_lock = std::unique_lock<std::recursive_mutex>(e->api);
+    if (!e) return BMQ_E_INVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (out_store_bytes) *out_store_bytes = 0;
+    if (!e->rbuilt) return set_err(e, BMQ_E_STATE, "no retained-topic index");
+    if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
+    uint64_t bytes = 0;
+    const bool ok = with_retain(e, [&](auto& rt) {
+        const bool r = rt.keys_prepare(e->rhost, &bytes);
+        if (!r) e->err = rt.error;
+        return r;
+    });
+    if (!ok) return set_err(e, e->err.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : BMQ_E_HIP, e->err);
+    if (out_store_bytes) *out_store_bytes = bytes;
+    return BMQ_OK;
+}
+
+int bmq_retain_keys_by_id(const bmq_engine* ce, const uint32_t* topic_ids, uint32_t n, uint8_t* out, uint64_t cap, uint64_t* out_off) {
+    bmq_engine* e = const_cast<bmq_engine*>(ce);
+    std::unique_lock<std::recursive_mutex> api_lock;
+    if (e) api_lock = std::unique_lock<std::recursive_mutex>(e->api);
+    if (!e || !out_off || (n && !topic_ids)) return BMQ_E_INVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    memset(out_off, 0, sizeof(uint64_t) * ((size_t)n + 1));
+    if (!e->rbuilt || n == 0) return BMQ_OK;
+    if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
+    bool nospace = false;
+    const bool ok = with_retain(e, [&](auto& rt) {
+        const bool r = rt.keys_by_id(e->rhost, topic_ids, n, out, cap, (unsigned long long*)out_off, nospace);
+        if (!r) e->err = rt.error;
+        return r;
+    });
+    if (!ok) return set_err(e, e->err.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : BMQ_E_HIP, e->err);
+    if (nospace) return set_err(e, BMQ_E_NOSPACE, "output buffer too small");
+    return BMQ_OK;
+}
+
+int bmq_retain_keys_match(bmq_engine* e, const uint8_t* tenants, const uint32_t* tenant_off, uint32_t n_tenants, const uint32_t* filter_tenant,
+                          const uint8_t* filters, const uint32_t* filter_off, uint32_t n_filters, const uint32_t* limit, uint64_t now_ms,
+                          uint32_t* out_row_ptr, uint32_t* out_topic_ids, uint64_t out_capacity, uint64_t* out_needed, uint32_t* out_match_count,
+                          uint64_t* out_key_off, uint8_t* out_keys, uint64_t keys_cap, uint64_t* out_needed_key_bytes) {
+    std::unique_lock<std::recursive_mutex> api_lock;
+    if (e) api_lock = std::unique_lock<std::recursive_mutex>(e->api);
+    const BatchInput in{tenants, tenant_off, n_tenants, filter_tenant, filters, filter_off, n_filters};
+    int rc;
+    if (!e) return BMQ_E_INVAL;
+    if (out_key_off && out_needed_key_bytes && retain_empty_batch(e, n_filters, out_row_ptr, out_needed, &rc)) {
+        out_key_off[0] = 0;
+        *out_needed_key_bytes = 0;
+        return rc;
+    }
+    if ((rc = retain_host_args_ok(e, in, out_row_ptr, out_needed))) return rc;
+    if (!limit) return set_err(e, BMQ_E_INVAL, "null limit array");
+    if (!out_key_off || !out_needed_key_bytes) return set_err(e, BMQ_E_INVAL, "null output pointer");
+    if (n_filters == 0) return set_err(e, BMQ_E_INVAL, "null pointer or empty batch");
+    uint32_t *d_row = nullptr, *d_counts = nullptr;
+    if ((rc = retain_limited_to_scratch(e, in, limit, now_ms, &d_row, &d_counts))) return rc;
+    std::lock_guard<std::mutex> g(e->mu);
+    HIPCHK(e, hipMemcpyAsync(out_row_ptr, d_row, sizeof(uint32_t) * (n_filters + 1), hipMemcpyDeviceToHost, e->stream));
+    if (out_match_count) HIPCHK(e, hipMemcpyAsync(out_match_count, d_counts, sizeof(uint32_t) * n_filters, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    const uint64_t kept = out_row_ptr[n_filters];
+    *out_needed = kept;
+    *out_needed_key_bytes = 0;
+    out_key_off[0] = 0;
+    if (kept == 0) return BMQ_OK; // nothing kept: no key kernel, no scan over nothing
+    // the keys of the kept ids, composed where the select left them (s_lim_ids); the lengths are known before anything is copied out
+    const unsigned long long* d_koff = nullptr;
+    const uint8_t* d_keys = nullptr;
+    uint64_t key_bytes = 0;
+    if (!e->drt->keys_compose(e->rhost, e->cur->s_lim_ids.as<uint32_t>(), (uint32_t)kept, d_koff, d_keys, key_bytes))
+        return set_err(e, e->drt->error.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : BMQ_E_HIP, e->drt->error);
+    *out_needed_key_bytes = key_bytes;
+    if (kept > out_capacity || !out_topic_ids) { // (out_key_off has out_capacity + 1 entries: nothing of the rows fits)
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        return set_err(e, BMQ_E_NOSPACE, "output buffer too small");
+    }
+    HIPCHK(e, hipMemcpyAsync(out_topic_ids, e->cur->s_lim_ids.p, sizeof(uint32_t) * kept, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(out_key_off, d_koff, sizeof(uint64_t) * (kept + 1), hipMemcpyDeviceToHost, e->stream));
+    const bool fits = key_bytes <= keys_cap && (key_bytes == 0 || out_keys);
+    if (fits && key_bytes) HIPCHK(e, hipMemcpyAsync(out_keys, d_keys, key_bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (!fits) return set_err(e, BMQ_E_NOSPACE, "key buffer too small");
     return BMQ_OK;
 }
 

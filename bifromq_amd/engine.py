@@ -796,6 +796,55 @@ class Engine:
             raw = out.tobytes()
             return [raw[int(off[i]):int(off[i + 1])] for i in range(n)]
 
+    def retain_keys_prepare(self) -> int:
+        """bmq_retain_keys_prepare: build this generation's device-resident string store now (idempotent) -> the bytes it holds"""
+        n = C.c_uint64()
+        self._check(_lib.lib().bmq_retain_keys_prepare(self.h, C.byref(n)))
+        return int(n.value)
+
+    def retain_keys_by_id(self, topic_ids) -> List[bytes]:
+        """bmq_retain_keys_by_id: retain_message_keys composed where the index lives (b"" for an id that is unknown or not retained now)"""
+        ids = np.ascontiguousarray(topic_ids, dtype=np.uint32)
+        n = len(ids)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        cap = max(4096, 96 * n)
+        while True:
+            out = np.zeros(cap, dtype=np.uint8)
+            rc = _lib.lib().bmq_retain_keys_by_id(self.h, _ptr(ids) if n else None, n, _ptr(out), cap, _ptr(off))
+            if rc == -3:
+                cap = int(off[n]) + 16
+                continue
+            self._check(rc)
+            raw = out.tobytes()
+            return [raw[int(off[i]):int(off[i + 1])] for i in range(n)]
+
+    def retain_match_keys(self, tenants: Sequence, filter_tenant, filters: Sequence, limits, now_ms: int = 0, packed_filters=None, keys_cap: int = 0):
+        """bmq_retain_keys_match: retain_match_limited plus retainMessageKey of every kept id, composed on the device ->
+        (row_ptr[n+1], kept topic ids, match count per filter, key_off[kept+1], key bytes); the key of ids[j] is
+        key_bytes[key_off[j]:key_off[j+1]]."""
+        tdata, toff = pack(tenants)
+        pdata, poff = pack(filters) if packed_filters is None else packed_filters
+        n = len(poff) - 1
+        ft = np.ascontiguousarray(filter_tenant, dtype=np.uint32)
+        lim = np.ascontiguousarray(limits, dtype=np.uint32)
+        assert len(lim) == n and len(ft) == n
+        row = np.zeros(n + 1, dtype=np.uint32)
+        counts = np.zeros(max(n, 1), dtype=np.uint32)
+        cap = int(min(int(lim.astype(np.uint64).sum()), 1 << 28)) + 1
+        kcap = keys_cap or 64 * cap
+        need, kneed = C.c_uint64(), C.c_uint64()
+        while True:
+            ids = np.zeros(cap, dtype=np.uint32)
+            koff = np.zeros(cap + 1, dtype=np.uint64)
+            keys = np.zeros(max(kcap, 1), dtype=np.uint8)
+            rc = _lib.lib().bmq_retain_keys_match(self.h, _ptr(tdata), _ptr(toff), len(toff) - 1, _ptr(ft), _ptr(pdata), _ptr(poff), n, _ptr(lim), now_ms,
+                                                  _ptr(row), _ptr(ids), cap, C.byref(need), _ptr(counts), _ptr(koff), _ptr(keys), kcap, C.byref(kneed))
+            if rc == -3 and (need.value > cap or kneed.value > kcap):
+                cap, kcap = max(cap, need.value), max(kcap, kneed.value)
+                continue
+            self._check(rc)
+            return row, ids[:need.value], counts[:n], koff[:need.value + 1], keys[:kneed.value].tobytes()
+
     def retain_topic_info(self, topic_id: int) -> Tuple[int, int, int]:
         """-> (timestamp_hlc, expiry_seconds, expire_at_ms)"""
         ts, ex, at = C.c_uint64(), C.c_uint32(), C.c_uint64()

@@ -895,8 +895,8 @@ int bmq_retain_tenant_counts(const bmq_engine* e, uint8_t* out_tenants, uint64_t
  * (bmq_retain_expired, bmq_retain_live_ids, a match):
  *   bmq_retain_message_keys  out_off[n + 1] / out: retainMessageKey(tenant, topic) of every id (the keys gc deletes and match gets with
  *                            reader.get), equal to bmq_retain_message_key of bmq_retain_topics id for id; EMPTY for an id that is unknown
- *                            or not retained now.  Host code under one engine lock.  BMQ_E_NOSPACE if cap < out_off[n] (offsets are
- *                            still written).
+ *                            or not retained now.  Host code under one engine lock (bmq_retain_keys_by_id composes the same bytes on
+ *                            the device).  BMQ_E_NOSPACE if cap < out_off[n] (offsets are still written).
  *   bmq_retain_remove_ids    the post-commit index removal (:270-275) BY ID: every live id goes dead exactly as a remove op of
  *                            bmq_retain_apply_batch leaves it (dead bit, expire_at = 0, the counts behind bmq_retain_info), then the
  *                            rank directory is rebuilt -- one kernel over the ids, nothing is looked up level by level -- on the engine
@@ -933,6 +933,33 @@ int bmq_retain_match_limited(bmq_engine* e, const uint8_t* tenants, const uint32
                              const uint32_t* filter_tenant, const uint8_t* filters, const uint32_t* filter_off,
                              uint32_t n_filters, const uint32_t* limit, uint64_t now_ms, uint32_t* out_row_ptr,
                              uint32_t* out_topic_ids, uint64_t out_capacity, uint64_t* out_needed, uint32_t* out_match_count);
+/* The second half of RetainStoreCoProc.match(tenant, filter, limit, now) (RS/RetainStoreCoProc.java:167-190): for every hit the reference
+ * calls reader.get(retainMessageKey(tenant, topic)) (:181), and gc deletes the same keys (:258-277).  The calls below compose
+ * retainMessageKey (KVSchemaUtil.java:44-73, LevelHash.java:30-50; the format of bmq_retain_message_key) where the index lives, by two
+ * kernels on the engine stream -- key lengths + a 64-bit scan, then the bytes -- behind whatever is in flight; host-only engines run the
+ * same functions on host threads.  The strings of the bulk-loaded ids (ranks: the index holds no labels for them) come from a store in
+ * device memory that is built from the host's copy of the load on the first of these calls in a generation and dropped at every
+ * generation change (bmq_retain_rebuild*, bmq_retain_compact, bmq_retain_compact_swap): a load nobody asks keys of pays nothing.
+ *   bmq_retain_keys_prepare  builds the store now if this generation has none (idempotent); *out_store_bytes (may be NULL) = the bytes it
+ *                            holds.  BMQ_E_STATE: no retained-topic index is loaded.
+ *   bmq_retain_keys_by_id    the contract of bmq_retain_message_keys word for word, and the same bytes: out_off[n + 1] / out =
+ *                            retainMessageKey(tenant, topic) of every id, EMPTY for an id that is unknown or not retained now -- decided on
+ *                            the device from the dead bitmap, no host copy of it is made.  BMQ_E_NOSPACE if cap < out_off[n] (offsets
+ *                            are still written).  bmq_retain_message_keys stays the host-side cross-check.
+ *   bmq_retain_keys_match    bmq_retain_match_limited (same rows, ids and match counts for the same input) plus the key of every kept id in
+ *                            row order: out_key_off[kept + 1] (room for out_capacity + 1 entries) / out_keys.  The kept ids do not leave
+ *                            the device between the select and the key kernels.  A kept id is live at now_ms, so no key is empty; when
+ *                            nothing is kept no key kernel runs.  *out_needed = kept ids and *out_needed_key_bytes = key bytes are always
+ *                            reported; BMQ_E_NOSPACE if either buffer is too small (ids too few: nothing but the row pointers, the counts
+ *                            and the two sizes is written; key bytes too few: ids and key offsets are).  Host-only engines:
+ *                            BMQ_E_NODEVICE, as for every match. */
+int bmq_retain_keys_prepare(bmq_engine* e, uint64_t* out_store_bytes /* may be NULL */);
+int bmq_retain_keys_by_id(const bmq_engine* e, const uint32_t* topic_ids, uint32_t n, uint8_t* out, uint64_t cap, uint64_t* out_off);
+int bmq_retain_keys_match(bmq_engine* e, const uint8_t* tenants, const uint32_t* tenant_off, uint32_t n_tenants,
+                          const uint32_t* filter_tenant, const uint8_t* filters, const uint32_t* filter_off,
+                          uint32_t n_filters, const uint32_t* limit, uint64_t now_ms, uint32_t* out_row_ptr,
+                          uint32_t* out_topic_ids, uint64_t out_capacity, uint64_t* out_needed, uint32_t* out_match_count,
+                          uint64_t* out_key_off, uint8_t* out_keys, uint64_t keys_cap, uint64_t* out_needed_key_bytes);
 int bmq_retain_match_batch_dev(bmq_engine* e, const uint8_t* d_tenants, const uint32_t* d_tenant_off,
                                uint32_t n_tenants, const uint32_t* d_filter_tenant, const uint8_t* d_filters,
                                const uint32_t* d_filter_off, uint32_t n_filters, uint32_t* d_out_row_ptr,

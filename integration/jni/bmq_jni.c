@@ -26,6 +26,7 @@
 #define NM(name) Java_org_apache_bifromq_dist_worker_gpu_NativeMatcher_##name
 /* the statistics and the GC by id of both co-processors: integration/java/org/apache/bifromq/retain/store/gpu/NativeStore.java */
 #define NS(name) Java_org_apache_bifromq_retain_store_gpu_NativeStore_##name
+#define NK(name) Java_org_apache_bifromq_retain_store_gpu_NativeKeys_##name
 
 static void throw_state(JNIEnv* env, bmq_engine* e, const char* what, int rc) {
     char msg[512];
@@ -516,6 +517,26 @@ JNIEXPORT jlong JNICALL NS(retainMessageKeys)(JNIEnv* env, jclass c, jlong h, jo
     const int rc = bmq_retain_message_keys(ENGINE(h), (const uint32_t*)ADDR(ids), (uint32_t)n, (uint8_t*)ADDR(out), CAP(out), off);
     return result_of(env, ENGINE(h), "bmq_retain_message_keys", rc, off ? off[n] : 0);
 }
+/* long retainKeysById(long engine, IntBuffer ids, int n, ByteBuffer out, LongBuffer outOff)    retainMessageKeys composed on the device (two kernels
+ * on the engine stream over the generation's device-resident string store; no host copy of the dead bitmap): the same contract and the same bytes;
+ * -> bytes, or -(needed) */
+JNIEXPORT jlong JNICALL NK(retainKeysById)(JNIEnv* env, jclass c, jlong h, jobject ids, jint n, jobject out, jobject outOff) {
+    (void)c;
+    uint64_t* off = (uint64_t*)ADDR(outOff);
+    const int rc = bmq_retain_keys_by_id(ENGINE(h), (const uint32_t*)ADDR(ids), (uint32_t)n, (uint8_t*)ADDR(out), CAP(out), off);
+    return result_of(env, ENGINE(h), "bmq_retain_keys_by_id", rc, off ? off[n] : 0);
+}
+/* long retainKeysPrepare(long engine)    builds the string store of this generation now (otherwise the first retainKeysById / retainMatchKeys does) -> its bytes */
+JNIEXPORT jlong JNICALL NK(retainKeysPrepare)(JNIEnv* env, jclass c, jlong h) {
+    (void)c;
+    uint64_t bytes = 0;
+    const int rc = bmq_retain_keys_prepare(ENGINE(h), &bytes);
+    if (rc != BMQ_OK) {
+        throw_state(env, ENGINE(h), "bmq_retain_keys_prepare", rc);
+        return 0;
+    }
+    return (jlong)bytes;
+}
 /* long retainRemoveIds(long engine, IntBuffer ids, int n, long generation)     the post-commit half of gc, by id -> topics removed; throws if the
  * generation has changed (the ids belong to the one before) or an id was never handed out */
 JNIEXPORT jlong JNICALL NS(retainRemoveIds)(JNIEnv* env, jclass c, jlong h, jobject ids, jint n, jlong generation) {
@@ -609,6 +630,29 @@ JNIEXPORT jlong JNICALL NM(retainMatchLimited)(JNIEnv* env, jclass c, jlong h, j
                                             (uint32_t)nFilters, (const uint32_t*)ADDR(limits), (uint64_t)nowMs, (uint32_t*)ADDR(outRowPtr),
                                             (uint32_t*)ADDR(outTopicIds), CAP(outTopicIds), &need, (uint32_t*)ADDR(outCounts));
     return result_of(env, ENGINE(h), "bmq_retain_match_limited", rc, need);
+}
+/* NativeKeys: long retainMatchKeys(long engine, ..the arguments of NativeMatcher.retainMatchLimited.., LongBuffer outKeyOff, ByteBuffer outKeys, long[] needed)
+ * retainMatchLimited plus retainMessageKey of every kept id in row order (outKeyOff[kept + 1] byte offsets into outKeys): what RetainStoreCoProc.match
+ * hands to reader.get.  needed = {kept ids, key bytes}, always; -> kept ids, or -1 when a buffer was too small */
+JNIEXPORT jlong JNICALL NK(retainMatchKeys)(JNIEnv* env, jclass c, jlong h, jobject tenants, jobject tenantOff, jint nTenants, jobject filterTenant,
+                                            jobject filters, jobject filterOff, jint nFilters, jobject limits, jlong nowMs, jobject outRowPtr,
+                                            jobject outTopicIds, jobject outCounts, jobject outKeyOff, jobject outKeys, jlongArray needed) {
+    (void)c;
+    uint64_t need = 0, key_bytes = 0, cap = CAP(outTopicIds);
+    if (CAP(outKeyOff) < cap + 1) cap = CAP(outKeyOff) ? CAP(outKeyOff) - 1 : 0;
+    const int rc = bmq_retain_keys_match(ENGINE(h), (const uint8_t*)ADDR(tenants), (const uint32_t*)ADDR(tenantOff), (uint32_t)nTenants,
+                                         (const uint32_t*)ADDR(filterTenant), (const uint8_t*)ADDR(filters), (const uint32_t*)ADDR(filterOff),
+                                         (uint32_t)nFilters, (const uint32_t*)ADDR(limits), (uint64_t)nowMs, (uint32_t*)ADDR(outRowPtr),
+                                         (uint32_t*)ADDR(outTopicIds), cap, &need, (uint32_t*)ADDR(outCounts), (uint64_t*)ADDR(outKeyOff),
+                                         (uint8_t*)ADDR(outKeys), CAP(outKeys), &key_bytes);
+    const jlong v[2] = {(jlong)need, (jlong)key_bytes};
+    if (needed) (*env)->SetLongArrayRegion(env, needed, 0, 2, v);
+    if (rc == BMQ_E_NOSPACE) return -1;
+    if (rc != BMQ_OK) {
+        throw_state(env, ENGINE(h), "bmq_retain_keys_match", rc);
+        return 0;
+    }
+    return (jlong)need;
 }
 /* int retainTopic(long engine, int topicId, ByteBuffer out, long[] tenantLenOut)   -> total length (tenant bytes then topic bytes) */
 JNIEXPORT jint JNICALL NM(retainTopic)(JNIEnv* env, jclass c, jlong h, jint id, jobject out, jlongArray tenantLenOut) {

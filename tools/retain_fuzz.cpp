@@ -9,7 +9,10 @@
 //     id), stamps are those of the last add, the image walk (dead ids dropped) + a walk over the overlay trie done the way the kernel
 //     does it equal the brute force, the GC scan and the live-id listing equal the model, overlay ids resolve to their strings;
 //   * removal by id (remove_id_one: live ids, dead ones, repeats, the 64 ids of one word in one batch) interleaved with the batches and
-//     the compactions, and after every step the retained topics per tenant (census_bulk_one, census_topic_one) against the model.
+//     the compactions, and after every step the retained topics per tenant (census_bulk_one, census_topic_one) against the model;
+//   * id -> retainMessageKey (key_len_one / key_write_one over the string store of the bulk-loaded ids: what k_r_key_len / k_r_key_write
+//     run): after every step the keys of every id in [0, id_bound + 8) against retain_message_key of the model's strings (bmq_codec.cpp),
+//     empty for every id that is dead, was never handed out or lies behind the bound.
 // Build + run: make -C bifromq_amd/csrc fuzz   (tests/test_host.py runs a short round of both builds)
 #include <algorithm>
 #include <cstdio>
@@ -20,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "../bifromq_amd/csrc/bmq_codec.h"
 #include "../bifromq_amd/csrc/bmq_exec_host.h"
 #include "../bifromq_amd/csrc/bmq_retain.h"
 #include "../bifromq_amd/csrc/bmq_retain_dyn.h"
@@ -218,7 +222,7 @@ int main(int argc, char** argv) {
     RetainDyn<HostExec> rt(hx);
     rt.tiny = true;
     RetainIndexView bview{};
-    uint64_t checks = 0, n_ops = 0, n_batches = 0, n_id_removals = 0;
+    uint64_t checks = 0, n_ops = 0, n_batches = 0, n_id_removals = 0, n_keys = 0;
     auto base_view = [&]() {
         RetainIndexView v{};
         v.nodes = h.nodes.data();
@@ -424,6 +428,32 @@ int main(int argc, char** argv) {
                 k++;
             }
         }
+        { // the key of every id: the per-item key functions through the host executor against the codec over the model's strings
+            std::map<uint32_t, Key> live_by_id;
+            for (auto& kv : live) live_by_id[kv.second] = kv.first;
+            std::vector<uint32_t> all((size_t)rt.info.id_bound + 8);
+            for (size_t i = 0; i < all.size(); i++) all[i] = (uint32_t)i;
+            if (round % 3 == 0) std::reverse(all.begin(), all.end());
+            if (round % 5 == 0) all.push_back(0xFFFFFFFFu), all.push_back(all[0]);
+            std::vector<unsigned long long> off(all.size() + 1, 77);
+            std::string want;
+            std::vector<unsigned long long> want_off{0};
+            for (uint32_t id : all) {
+                auto f = live_by_id.find(id);
+                if (f != live_by_id.end()) want += retain_message_key(f->second.first, f->second.second);
+                want_off.push_back(want.size());
+            }
+            std::vector<uint8_t> out(want.size() + 1, 0xEE);
+            bool nospace = false;
+            if (!want.empty()) { // one byte short: the offsets come, the bytes do not
+                if (!rt.keys_by_id(h, all.data(), (uint32_t)all.size(), out.data(), want.size() - 1, off.data(), nospace)) FAIL("round %d: keys_by_id failed: %s\n", round, rt.error.c_str());
+                if (!nospace || off != want_off || out[0] != 0xEE) FAIL("round %d: keys_by_id with a short buffer: nospace %d\n", round, (int)nospace);
+            }
+            if (!rt.keys_by_id(h, all.data(), (uint32_t)all.size(), out.data(), want.size(), off.data(), nospace)) FAIL("round %d: keys_by_id failed: %s\n", round, rt.error.c_str());
+            if (nospace || off != want_off) FAIL("round %d: key offsets differ from the model (%llu bytes against %zu)\n", round, off.back(), want.size());
+            if (want.compare(0, want.size(), (const char*)out.data(), want.size()) != 0 || out[want.size()] != 0xEE) FAIL("round %d: key bytes differ from retain_message_key\n", round);
+            n_keys += live_by_id.size();
+        }
         for (int s = 0; s < 40 && !live.empty(); s++) { // stamps of the last add
             auto it = live.begin();
             std::advance(it, rnd(live.size()));
@@ -498,7 +528,7 @@ int main(int argc, char** argv) {
             }
         }
     }
-    printf("retain_fuzz ok: seed %llu, %d rounds, %u threads, %llu ops in %llu batches, %llu topics removed by id, %llu filter checks\n", (unsigned long long)seed, rounds,
-           threads, (unsigned long long)n_ops, (unsigned long long)n_batches, (unsigned long long)n_id_removals, (unsigned long long)checks);
+    printf("retain_fuzz ok: seed %llu, %d rounds, %u threads, %llu ops in %llu batches, %llu topics removed by id, %llu filter checks, %llu keys\n", (unsigned long long)seed, rounds,
+           threads, (unsigned long long)n_ops, (unsigned long long)n_batches, (unsigned long long)n_id_removals, (unsigned long long)checks, (unsigned long long)n_keys);
     return 0;
 }
