@@ -23,6 +23,7 @@ ABI_SYMBOLS = [
     "bmq_exchange_csr", "bmq_exchange_wait", "bmq_partition_batch_dev", "bmq_retain_message_key", "bmq_retain_filter_route", "bmq_retain_rebuild", "bmq_retain_rebuild_ex", "bmq_retain_apply", "bmq_retain_apply_ex", "bmq_retain_topic",
     "bmq_retain_topic_info", "bmq_retain_find_all", "bmq_retain_expired", "bmq_retain_apply_batch", "bmq_retain_compact", "bmq_retain_compact_begin", "bmq_retain_compact_build", "bmq_retain_compact_swap", "bmq_retain_compact_abort", "bmq_retain_info_get",
     "bmq_retain_live_ids", "bmq_retain_topics", "bmq_retain_tenant_counts", "bmq_retain_message_keys", "bmq_retain_remove_ids", "bmq_retain_keys_prepare", "bmq_retain_keys_by_id", "bmq_retain_keys_match",
+    "bmq_retain_count_in", "bmq_retain_ids_in", "bmq_retain_compact_begin_in", "bmq_retain_import",
     "bmq_retain_match_batch", "bmq_retain_match_batch_dev", "bmq_retain_match_limited", "bmq_batcher_create", "bmq_batcher_destroy",
     "bmq_batcher_match_all", "bmq_batcher_submit", "bmq_batcher_stats_get", "bmq_poller_stats_get", "bmq_poller_control",
     "bmq_route_cache_create", "bmq_route_cache_destroy", "bmq_route_cache_get", "bmq_route_cache_get_async", "bmq_route_cache_get_batch", "bmq_batcher_match_batch", "bmq_route_cache_is_cached", "bmq_route_cache_apply",
@@ -135,6 +136,10 @@ def lib() -> C.CDLL:
             "bmq_version": (C.c_char_p, []),
             "bmq_rebuild": (C.c_int, [vp, vp, vp, u32]),
             "bmq_retain_compact_begin": (C.c_int, [vp]),
+            "bmq_retain_compact_begin_in": (C.c_int, [vp, C.c_uint8, C.c_char_p, u32, C.c_char_p, u32]),
+            "bmq_retain_count_in": (C.c_int, [vp, C.c_uint8, C.c_char_p, u32, C.c_char_p, u32, P(u64), P(u64)]),
+            "bmq_retain_ids_in": (C.c_int, [vp, C.c_uint8, C.c_char_p, u32, C.c_char_p, u32, vp, u32, P(u32)]),
+            "bmq_retain_import": (C.c_int, [vp, vp, C.c_uint8, C.c_char_p, u32, C.c_char_p, u32, P(u64), P(u64)]),
             "bmq_retain_compact_build": (C.c_int, [vp]),
             "bmq_retain_compact_swap": (C.c_int, [vp, P(u64), P(u64)]),
             "bmq_retain_compact_abort": (C.c_int, [vp]),

@@ -191,6 +191,7 @@ struct bmq_engine {
             uint32_t expiry;
         };
         std::vector<Op> log;                      // IRetainTopicIndex.add / remove since begin, in order: replayed before the swap
+        Boundary bound;                           // bmq_retain_compact_begin_in: the next generation keeps the topics whose key lies inside (flags 0: all)
         uint64_t log_bytes = 0;
         bool log_overflow = false;
     } rcmp;

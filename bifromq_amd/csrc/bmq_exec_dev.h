@@ -238,6 +238,38 @@ __global__ __launch_bounds__(256) void k_r_key_write(RetainMut m, RetainKeyStore
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) key_write_one(m, ks, ids[i], out + offs[i], offs[i + 1] - offs[i]);
 }
+// The boundary predicate over the retained-topic ids (retain_key_in_boundary, bmq_retain_core.h): one lane per id of [0, n_ids), in the
+// launch shape of k_b_boundary -- the first BND_LDS bytes of each present boundary key staged in LDS per workgroup (a longer key is read
+// where it lies: a uniform address), a bounded grid that strides over the ids, ballot + popcount for the topics and a cross-lane sum for
+// the key bytes, ONE atomic per wave and counter.  ctr[0] += topics inside, ctr[1] += their key bytes (want_bytes: the lengths cost a second
+// walk over the topic, so they are computed only when asked for); flags (may be null) [id] = 1 inside / 0 for the select that lists the ids.
+// Neighbouring lanes hold neighbouring ranks: of one tenant mostly, so the head compare reads the same tenant bytes (a broadcast) and a
+// wave whose tenant differs from the boundary key's is done after it; only the ids of the boundary key's own tenant walk their topic.
+__global__ __launch_bounds__(256) void k_r_boundary(RetainMut m, RetainKeyStore ks, uint32_t n_ids, KeyBoundary b, uint8_t* flags, uint32_t want_bytes,
+                                                    unsigned long long* ctr) {
+    __shared__ uint8_t s_key[2][BND_LDS];
+    if ((b.flags & 1u) && b.start_len <= BND_LDS) {
+        for (uint32_t p = threadIdx.x; p < b.start_len; p += 256) s_key[0][p] = b.start[p];
+    }
+    if ((b.flags & 2u) && b.end_len <= BND_LDS) {
+        for (uint32_t p = threadIdx.x; p < b.end_len; p += 256) s_key[1][p] = b.end[p];
+    }
+    __syncthreads();
+    if ((b.flags & 1u) && b.start_len <= BND_LDS) b.start = s_key[0];
+    if ((b.flags & 2u) && b.end_len <= BND_LDS) b.end = s_key[1];
+    unsigned long long topics = 0, bytes = 0; // topics: the wave's (the same in every lane); bytes: this lane's until the cross-lane sum
+    for (unsigned long long base = (unsigned long long)blockIdx.x * 256; base < n_ids; base += (unsigned long long)gridDim.x * 256) {
+        const unsigned long long i = base + threadIdx.x;
+        const unsigned long long len = i < n_ids ? boundary_id_one(m, ks, (uint32_t)i, b, flags, want_bytes) : 0ull;
+        topics += (unsigned long long)__popcll(__ballot(len != 0));
+        bytes += want_bytes ? len : 0ull;
+    }
+    for (int d = 32; d > 0; d >>= 1) bytes += __shfl_xor(bytes, d, 64);
+    if ((threadIdx.x & 63u) == 0 && topics != 0) {
+        atomicAdd(ctr, topics);
+        atomicAdd(ctr + 1, bytes);
+    }
+}
 __global__ __launch_bounds__(64) void k_r_find_tenant(RetainMut m, const uint8_t* name, uint32_t len, uint32_t* out) {
     if (threadIdx.x || blockIdx.x) return;
     LevelScan lv;
@@ -566,11 +598,22 @@ struct DevExec {
         if (q.n_ids == 0) return zero(out_count, sizeof(uint32_t));
         hipLaunchKernelGGL(k_r_gc_flags, grid(q.n_ids, 256), dim3(256), 0, stream, m, q, flags);
         if (!launched()) return false;
+        return r_flagged_ids(flags, q.n_ids, out_ids, out_count);
+    }
+    // the ids of [0, n) whose flag byte is set, ascending -> out_ids[0 .. *out_count)
+    bool r_flagged_ids(const uint8_t* flags, uint32_t n, uint32_t* out_ids, uint32_t* out_count) {
         hipcub::CountingInputIterator<uint32_t> iota(0u);
         size_t bytes = 0;
-        if (!BMQ_X(hipcub::DeviceSelect::Flagged(nullptr, bytes, iota, flags, out_ids, out_count, (int)q.n_ids, stream))) return false;
+        if (!BMQ_X(hipcub::DeviceSelect::Flagged(nullptr, bytes, iota, flags, out_ids, out_count, (int)n, stream))) return false;
         if (!ensure_tmp(bytes)) return false;
-        return BMQ_X(hipcub::DeviceSelect::Flagged(tmp, bytes, iota, flags, out_ids, out_count, (int)q.n_ids, stream));
+        return BMQ_X(hipcub::DeviceSelect::Flagged(tmp, bytes, iota, flags, out_ids, out_count, (int)n, stream));
+    }
+    // ctr[0] += live ids of [0, n_ids) whose key lies inside `b`, ctr[1] += their key bytes if want_bytes; flags (may be null) [id] = inside
+    // (k_r_boundary; b's keys: exec memory)
+    bool r_boundary(const RetainMut& m, const RetainKeyStore& ks, uint32_t n_ids, const KeyBoundary& b, uint8_t* flags, bool want_bytes, unsigned long long* ctr) {
+        if (n_ids == 0) return true;
+        hipLaunchKernelGGL(k_r_boundary, dim3(std::min((n_ids + 255u) / 256u, BND_BLOCKS)), dim3(256), 0, stream, m, ks, n_ids, b, flags, want_bytes ? 1u : 0u, ctr);
+        return launched();
     }
     bool r_remove_ids(const RetainMut& m, const uint32_t* ids, uint32_t n, uint32_t n_ids) {
         hipLaunchKernelGGL(k_r_remove_ids, grid(n, 256), dim3(256), 0, stream, m, ids, n, n_ids);

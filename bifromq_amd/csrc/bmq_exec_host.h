@@ -270,6 +270,27 @@ struct HostExec {
         *out_count = n;
         return true;
     }
+    bool r_flagged_ids(const uint8_t* flags, uint32_t n, uint32_t* out_ids, uint32_t* out_count) {
+        uint32_t k = 0;
+        for (uint32_t id = 0; id < n; id++)
+            if (flags[id]) out_ids[k++] = id;
+        *out_count = k;
+        return true;
+    }
+    // ctr[0] += live ids of [0, n_ids) whose key lies inside `b`, ctr[1] += their key bytes if want_bytes; flags (may be null) [id] = inside
+    // (k_r_boundary on the device)
+    bool r_boundary(const RetainMut& m, const RetainKeyStore& ks, uint32_t n_ids, const KeyBoundary& b, uint8_t* flags, bool want_bytes, unsigned long long* ctr) {
+        std::atomic<unsigned long long> topics{0}, bytes{0};
+        par(n_ids, [&](size_t i) {
+            if (const unsigned long long len = boundary_id_one(m, ks, (uint32_t)i, b, flags, want_bytes ? 1u : 0u)) {
+                topics.fetch_add(1, std::memory_order_relaxed);
+                if (want_bytes) bytes.fetch_add(len, std::memory_order_relaxed);
+            }
+        });
+        ctr[0] += topics.load();
+        ctr[1] += bytes.load();
+        return true;
+    }
     bool r_remove_ids(const RetainMut& m, const uint32_t* ids, uint32_t n, uint32_t n_ids) {
         par(n, [&](size_t i) { remove_id_one(m, ids, (uint32_t)i, n_ids); });
         return true;

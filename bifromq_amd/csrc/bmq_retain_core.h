@@ -560,6 +560,98 @@ BMQ_HD void key_write_one(const RetainMut& m, const RetainKeyStore& ks, uint32_t
         if (o.parent != t) out[--end] = 0; // TopicUtil.escape of the '/' in front of this level
     }
 }
+// ------------------------------------------------------------------------------------------------------------
+// KV boundary of the retain store's range (RetainStoreCoProc.reset(Boundary), RS/RetainStoreCoProc.java:133-137): is the key of id inside?
+// ------------------------------------------------------------------------------------------------------------
+// No id range is a key range (tenants are ranked in byte order, keys sort by tenant LENGTH first; inside a tenant by level count and hash
+// bytes before the topic), so the answer is a predicate over ids.  The key is never written anywhere: its four segments are walked in
+// order against the boundary key and the first difference decides -- almost always inside `00 | u16be(tl) | tenant`.
+struct KeyCursor { // the byte string the key is compared with, and how far the compare has come
+    const uint8_t* k;
+    unsigned long long n, p;
+};
+// the key's next byte against the cursor's: < 0 / > 0 decides the compare (a cursor at its end: the key is the longer one), 0 = go on
+BMQ_HD int key_cursor_step(KeyCursor& c, uint32_t b) {
+    if (c.p >= c.n) return 1;
+    const uint32_t y = c.k[c.p++];
+    return b == y ? 0 : (b < y ? -1 : 1);
+}
+// `00 | u16be(tl) | tenant`
+BMQ_HD int key_cursor_head(KeyCursor& c, const uint8_t* tenant, uint32_t tl) {
+    int r;
+    if ((r = key_cursor_step(c, 0u)) || (r = key_cursor_step(c, (tl >> 8) & 0xFFu)) || (r = key_cursor_step(c, tl & 0xFFu))) return r;
+    for (uint32_t k = 0; k < tl; k++)
+        if ((r = key_cursor_step(c, tenant[k]))) return r;
+    return 0;
+}
+// overlay node of forward level j of a topic of `levels` levels that ends at node `last`: the chain has parents only
+BMQ_HD uint32_t ov_level_node(const RetainMut& m, uint32_t last, uint32_t levels, uint32_t j) {
+    uint32_t n = last;
+    for (uint32_t up = levels - 1u - j; up != 0u; up--) n = m.onodes[n].parent;
+    return n;
+}
+// retainMessageKey(id) against key[0, key_len) in unsigned byte order, a proper prefix first (the order of key_compare, bmq_build_core.h):
+// < 0, 0, > 0.  id is a live id of this state (key_id_live); an id that is not compares as the empty key.
+BMQ_HD int retain_key_cmp(const RetainMut& m, const RetainKeyStore& ks, uint32_t id, const uint8_t* key, unsigned long long key_len) {
+    KeyCursor c{key, key_len, 0ull};
+    int r = 0;
+    if (!key_id_live(m, ks, id)) return key_len ? -1 : 0;
+    if (id < m.base_n) { // a rank: tenant and topic lie in the key store, the topic in one piece
+        const uint32_t t = key_store_tenant(ks, id);
+        if ((r = key_cursor_head(c, ks.tenants + ks.tenant_off[t], ks.tenant_off[t + 1] - ks.tenant_off[t]))) return r;
+        const uint8_t* p = ks.topics + ks.topic_off[id];
+        const uint32_t pl = (uint32_t)(ks.topic_off[id + 1] - ks.topic_off[id]);
+        uint32_t levels = 1;
+        for (uint32_t i = 0; i < pl; i++) levels += p[i] == '/';
+        if ((r = key_cursor_step(c, (levels >> 8) & 0xFFu)) || (r = key_cursor_step(c, levels & 0xFFu))) return r;
+        for (uint32_t i = 0, b = 0; i <= pl; i++) { // a LevelHash byte per level
+            if (i < pl && p[i] != '/') continue;
+            if ((r = key_cursor_step(c, level_hash_byte(p + b, i - b)))) return r;
+            b = i + 1;
+        }
+        for (uint32_t i = 0; i < pl; i++) // the topic, TopicUtil.escape
+            if ((r = key_cursor_step(c, p[i] == '/' ? 0u : p[i]))) return r;
+        return c.p < c.n ? -1 : 0;
+    }
+    // an overlay topic: the tenant's node is on record per id; the levels hang on a chain that is walked from the LAST level up
+    const uint32_t last = m.id_node[id], t = m.id_tnode[id] & ~ID_SYS;
+    if (t >= m.ov_cap) return key_len ? -1 : 0;
+    const ONode& tn = m.onodes[t];
+    if ((r = key_cursor_head(c, m.opool + tn.str_off, tn.str_len & ~ON_SYS))) return r;
+    uint32_t levels = 0;
+    for (uint32_t n = last; n != t && n != 0u; n = m.onodes[n].parent) levels++;
+    if ((r = key_cursor_step(c, (levels >> 8) & 0xFFu)) || (r = key_cursor_step(c, levels & 0xFFu))) return r;
+    // forward level j = levels - 1 - j steps up: quadratic in the level count, no per-lane array -- and only for ids whose tenant is the
+    // tenant of the boundary key (everything else was decided above)
+    for (uint32_t j = 0; j < levels; j++) {
+        const ONode& o = m.onodes[ov_level_node(m, last, levels, j)];
+        if ((r = key_cursor_step(c, level_hash_byte(m.opool + o.str_off, o.str_len & ~ON_SYS)))) return r;
+    }
+    for (uint32_t j = 0; j < levels; j++) {
+        const ONode& o = m.onodes[ov_level_node(m, last, levels, j)];
+        const uint32_t l = o.str_len & ~ON_SYS;
+        if (j && (r = key_cursor_step(c, 0u))) return r;
+        for (uint32_t k = 0; k < l; k++)
+            if ((r = key_cursor_step(c, m.opool[o.str_off + k]))) return r;
+    }
+    return c.p < c.n ? -1 : 0;
+}
+// BoundaryUtil.inRange (base-kv/.../utils/BoundaryUtil.java:241-252) for the key of id; an id that is not live is never inside
+BMQ_HD bool retain_key_in_boundary(const RetainMut& m, const RetainKeyStore& ks, uint32_t id, const KeyBoundary& b) {
+    if (!key_id_live(m, ks, id)) return false;
+    if ((b.flags & 1u) && retain_key_cmp(m, ks, id, b.start, b.start_len) < 0) return false;
+    if ((b.flags & 2u) && retain_key_cmp(m, ks, id, b.end, b.end_len) >= 0) return false;
+    return true;
+}
+// one id of the boundary pass: 0 = outside (or not live), else 1 -- or the key's length when the caller wants the bytes.  flags (may be
+// null): a byte per id for the select that lists the ids.
+BMQ_HD unsigned long long boundary_id_one(const RetainMut& m, const RetainKeyStore& ks, uint32_t id, const KeyBoundary& b, uint8_t* flags, uint32_t want_bytes) {
+    const bool in = retain_key_in_boundary(m, ks, id, b);
+    if (flags) flags[id] = in ? 1 : 0;
+    if (!in) return 0ull;
+    return want_bytes ? key_len_one(m, ks, id) : 1ull;
+}
+
 // The scan of RetainStoreCoProc.gc (RS/RetainStoreCoProc.java:257-277): flag[id] = 1 for every retained id whose message has
 // expired at `now` (expireTime <= now; override_expiry >= 0 replaces the stored interval: GCRequest.expirySeconds).
 // tenant scan (has_tenant): only ids of that tenant -- bulk-loaded ranks [t_lo, t_hi), overlay ids below tenant node t_node -- and,

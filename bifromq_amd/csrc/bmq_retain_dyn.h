@@ -395,6 +395,48 @@ public:
         return true;
     }
 
+    // ---- the ids whose retainMessageKey lies inside a KV boundary (retain_key_in_boundary): ONE pass of the boundary kernel over the ids
+    // handed out, on the executor's stream behind whatever is in flight.  flags bit 0 / 1: start / end present (host memory; a present key
+    // may be empty).  topics = live ids inside; key_bytes (may be null: the lengths are not computed) = the sum of their key lengths; ids (may
+    // be null: no flag bytes are written, nothing is selected) = those ids, ascending.  Needs the key store: built here if the generation
+    // has none, as keys_compose does.
+    bool boundary_select(const RetainIndexHost& h, uint32_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len, uint64_t& topics,
+                         uint64_t* key_bytes, std::vector<uint32_t>* ids) {
+        topics = 0;
+        if (key_bytes) *key_bytes = 0;
+        if (ids) ids->clear();
+        if (!keys_prepare(h, nullptr)) return false;
+        const uint32_t n = (uint32_t)info.id_bound;
+        if (n == 0) return true;
+        if (!(flags & 1u)) start_len = 0;
+        if (!(flags & 2u)) end_len = 0;
+        const size_t off_ctr = align16((size_t)n), off_cnt = off_ctr + 16, off_start = off_cnt + 16, off_end = align16(off_start + start_len + 16),
+                     off_ids = align16(off_end + end_len + 16);
+        if (!ensure(q_buf, q_cap, off_ids + (ids ? 4 * (size_t)n : 0))) return false;
+        unsigned long long* d_sums = (unsigned long long*)(q_buf + off_ctr);
+        uint32_t* d_cnt = (uint32_t*)(q_buf + off_cnt);
+        KeyBoundary kb{};
+        kb.start = q_buf + off_start;
+        kb.end = q_buf + off_end;
+        kb.start_len = start_len;
+        kb.end_len = end_len;
+        kb.flags = flags & 3u;
+        if (!x.zero(q_buf + off_ctr, 32) || !x.copy_in_async(q_buf + off_start, start, start_len) || !x.copy_in_async(q_buf + off_end, end, end_len)) return xfail();
+        unsigned long long sums[2] = {0, 0};
+        if (!x.r_boundary(mut(), key_store(), n, kb, ids ? q_buf : nullptr, key_bytes != nullptr, d_sums)) return xfail();
+        if (ids && !x.r_flagged_ids(q_buf, n, (uint32_t*)(q_buf + off_ids), d_cnt)) return xfail();
+        if (!x.copy_out(sums, d_sums, 16)) return xfail(); // waits for the pass
+        topics = sums[0];
+        if (key_bytes) *key_bytes = sums[1];
+        if (ids) {
+            uint32_t cnt = 0;
+            if (!x.copy_out(&cnt, d_cnt, 4)) return xfail();
+            ids->resize(cnt);
+            if (cnt && !x.copy_out(ids->data(), q_buf + off_ids, 4 * (size_t)cnt)) return xfail();
+        }
+        return true;
+    }
+
     // timestamp / expiry interval of every id handed out (compaction re-loads the live ones)
     bool payload(std::vector<unsigned long long>& ts, std::vector<uint32_t>& expiry) {
         ts.assign(info.id_bound ? info.id_bound : 1, 0);

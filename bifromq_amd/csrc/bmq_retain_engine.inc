@@ -729,15 +729,37 @@ int bmq_retain_tenant_counts(const bmq_engine* ce, uint8_t* out_tenants, uint64_
 // Maintenance: merge what bmq_retain_apply* changed into a fresh bulk load -- removed topics and their ids go, overlay topics become
 // ranks again (every subtree one id range: the fast path of '+' and '#').  A new generation of ids.
 // the live retained topics with their stamps, as bmq_retain_rebuild_ex takes them (under e->mu)
-static int retain_live_items_locked(bmq_engine* e, std::vector<RetainIndexHost::Item>& items) {
+// ids (ascending) of the retained topics whose retainMessageKey lies inside `b`, their number and (key_bytes != null) the sum of their key
+// lengths: one pass of k_r_boundary over the ids handed out (under e->mu)
+static int retain_boundary_locked(bmq_engine* e, const Boundary& b, uint64_t& topics, uint64_t* key_bytes, std::vector<uint32_t>* ids) {
+    topics = 0;
+    if (key_bytes) *key_bytes = 0;
+    if (ids) ids->clear();
+    if (!e->rbuilt) return BMQ_OK;
+    if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
+    const bool ok = with_retain(e, [&](auto& rt) {
+        const bool r = rt.boundary_select(e->rhost, b.flags, (const uint8_t*)b.start.data(), (uint32_t)b.start.size(), (const uint8_t*)b.end.data(), (uint32_t)b.end.size(),
+                                          topics, key_bytes, ids);
+        if (!r) e->err = rt.error;
+        return r;
+    });
+    if (!ok) return set_err(e, e->err.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : BMQ_E_HIP, e->err);
+    return BMQ_OK;
+}
+
+static int retain_live_items_locked(bmq_engine* e, std::vector<RetainIndexHost::Item>& items, const Boundary& bound = Boundary{}) {
     std::vector<uint32_t> ids;
     std::vector<unsigned long long> ts;
     std::vector<uint32_t> ex;
+    if (bound.bounded()) { // only the topics whose key lies inside: the predicate runs where the index lives
+        uint64_t n_in = 0;
+        if (int rc = retain_boundary_locked(e, bound, n_in, nullptr, &ids)) return rc;
+    }
     GcQuery q{};
     q.live_only = 1;
     q.override_expiry = -1;
     const bool ok = with_retain(e, [&](auto& rt) {
-        const bool r = rt.select(q, nullptr, 0, ids) && rt.payload(ts, ex);
+        const bool r = (bound.bounded() || rt.select(q, nullptr, 0, ids)) && rt.payload(ts, ex);
         if (!r) e->err = rt.error;
         return r;
     });
@@ -764,16 +786,23 @@ static int retain_live_items_locked(bmq_engine* e, std::vector<RetainIndexHost::
 // both back into a fresh bulk load, but under the engine lock: 2 s for 1 M topics (the host-side load).  The three calls below take the
 // load out of the lock:  begin = snapshot of the live topics (tens of ms under the lock); build = the load into an index of its own, no
 // lock held, matching and bmq_retain_apply* go on (what they change is logged); swap = upload + replay of the log under the lock.
-int bmq_retain_compact_begin(bmq_engine* e) {
+int bmq_retain_compact_begin(bmq_engine* e) { return bmq_retain_compact_begin_in(e, 0, nullptr, 0, nullptr, 0); }
+// ... for a range that SHRINKS (RetainStoreCoProc.reset(Boundary) after a split): the snapshot takes only the topics whose key lies inside
+// the boundary, and the swap replays only the logged ops whose key does.  The serving generation matches and mutates over all its topics
+// until the swap.
+int bmq_retain_compact_begin_in(bmq_engine* e, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len) {
     if (!e) return BMQ_E_INVAL;
     std::lock_guard<std::recursive_mutex> api_lock(e->api);
     std::lock_guard<std::mutex> gc(e->cmp_mu);
     std::lock_guard<std::mutex> g(e->mu);
+    Boundary bound;
+    if (!parse_boundary(flags, start, start_len, end, end_len, bound)) return set_err(e, BMQ_E_INVAL, "malformed boundary (start >= end, or a present key without bytes)");
     if (e->rcmp.active) return set_err(e, BMQ_E_STATE, "a retain compaction is running: bmq_retain_compact_swap or bmq_retain_compact_abort first");
     if (!e->rbuilt) return set_err(e, BMQ_E_STATE, "no retained-topic index");
     if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
     e->rcmp = bmq_engine::RetainCompaction{};
-    if (int rc = retain_live_items_locked(e, e->rcmp.items)) return rc;
+    e->rcmp.bound = bound;
+    if (int rc = retain_live_items_locked(e, e->rcmp.items, bound)) return rc;
     e->rcmp.active = true;
     return BMQ_OK;
 }
@@ -822,7 +851,18 @@ int bmq_retain_compact_swap(bmq_engine* e, uint64_t* out_carried, uint64_t* out_
     {
         std::lock_guard<std::mutex> g(e->mu);
         log.swap(e->rcmp.log);
+        const Boundary bound = e->rcmp.bound;
         e->rcmp = bmq_engine::RetainCompaction{};
+        if (bound.bounded()) { // the range has shrunk: an op whose key lies outside is not this range's any more (adds and removals alike)
+            size_t kept = 0;
+            for (size_t i = 0; i < log.size(); i++)
+                if (bound.contains(retain_message_key(log[i].tenant, log[i].topic))) {
+                    if (kept != i) log[kept] = std::move(log[i]);
+                    kept++;
+                }
+            log.resize(kept);
+            n_log = kept;
+        }
     }
     for (size_t lo = 0; lo < log.size();) {
         const size_t hi = std::min(log.size(), lo + 65536);
@@ -901,6 +941,120 @@ int bmq_retain_compact(bmq_engine* e) {
     }
     if (!e->rhost.rebuild(std::move(items))) return set_err(e, BMQ_E_INVAL, e->rhost.error);
     return retain_publish(e);
+}
+
+// ---- the retain store's range by KV boundary: RetainStoreCoProc.reset(Boundary) without the KV scan --------------------------------------
+int bmq_retain_count_in(const bmq_engine* ce, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len,
+                        uint64_t* out_topics, uint64_t* out_key_bytes) {
+    bmq_engine* e = const_cast<bmq_engine*>(ce);
+    std::unique_lock<std::recursive_mutex> api_lock;
+    if (e) api_lock = std::unique_lock<std::recursive_mutex>(e->api);
+    if (!e) return BMQ_E_INVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    Boundary bound;
+    if (!parse_boundary(flags, start, start_len, end, end_len, bound)) return set_err(e, BMQ_E_INVAL, "malformed boundary (start >= end, or a present key without bytes)");
+    uint64_t topics = 0, bytes = 0;
+    if (int rc = retain_boundary_locked(e, bound, topics, out_key_bytes ? &bytes : nullptr, nullptr)) return rc;
+    if (out_topics) *out_topics = topics;
+    if (out_key_bytes) *out_key_bytes = bytes;
+    return BMQ_OK;
+}
+
+int bmq_retain_ids_in(const bmq_engine* ce, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len, uint32_t* out_ids,
+                      uint32_t cap, uint32_t* out_n) {
+    bmq_engine* e = const_cast<bmq_engine*>(ce);
+    std::unique_lock<std::recursive_mutex> api_lock;
+    if (e) api_lock = std::unique_lock<std::recursive_mutex>(e->api);
+    if (!e || !out_n) return BMQ_E_INVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    *out_n = 0;
+    Boundary bound;
+    if (!parse_boundary(flags, start, start_len, end, end_len, bound)) return set_err(e, BMQ_E_INVAL, "malformed boundary (start >= end, or a present key without bytes)");
+    uint64_t topics = 0;
+    std::vector<uint32_t> ids;
+    if (int rc = retain_boundary_locked(e, bound, topics, nullptr, &ids)) return rc;
+    *out_n = (uint32_t)ids.size();
+    for (size_t i = 0; i < ids.size() && i < cap && out_ids; i++) out_ids[i] = ids[i];
+    return ids.size() > cap ? BMQ_E_NOSPACE : BMQ_OK;
+}
+
+// Locks: dst->api for the whole call, then ONE engine lock at a time and never nested -- dst->mu to check, src->mu for the snapshot (ids
+// inside the boundary, stamps, strings: src goes on serving afterwards), dst's own locks per chunk through the ordinary apply path.
+int bmq_retain_import(bmq_engine* dst, bmq_engine* src, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len,
+                      uint64_t* out_imported, uint64_t* out_replaced) {
+    if (!dst || !src) return BMQ_E_INVAL;
+    std::lock_guard<std::recursive_mutex> api_lock(dst->api);
+    Boundary bound;
+    bool dst_empty = false;
+    {
+        std::lock_guard<std::mutex> g(dst->mu);
+        if (dst == src) return set_err(dst, BMQ_E_INVAL, "bmq_retain_import: source and destination are the same engine");
+        if (!parse_boundary(flags, start, start_len, end, end_len, bound)) return set_err(dst, BMQ_E_INVAL, "malformed boundary (start >= end, or a present key without bytes)");
+        // the new sibling of a split: nothing to merge with, so the import is a bulk load (ranks, the fast path of '+' and '#')
+        dst_empty = !dst->rbuilt || (!dst->rcmp.active && (dst->drt ? dst->drt->info.n_live : dst->hrt->info.n_live) == 0);
+        if (dst_empty)
+            for (auto& sl : dst->slots)
+                if (sl.pending) return set_err(dst, BMQ_E_STATE, "a batch is in flight: finish / wait for it first");
+    }
+    if (out_imported) *out_imported = 0;
+    if (out_replaced) *out_replaced = 0;
+    std::vector<RetainIndexHost::Item> items;
+    int src_rc = BMQ_OK;
+    std::string src_msg;
+    {
+        std::lock_guard<std::mutex> g(src->mu);
+        if (src->device >= 0 && hipSetDevice(src->device) != hipSuccess) src_rc = BMQ_E_HIP, src_msg = "source engine: hipSetDevice failed";
+        else if (src->rbuilt && (src_rc = retain_live_items_locked(src, items, bound)) != BMQ_OK) src_msg = "source engine: " + src->err;
+    }
+    if (src_rc != BMQ_OK) {
+        std::lock_guard<std::mutex> g(dst->mu);
+        return set_err(dst, src_rc, src_msg);
+    }
+    if (dst_empty) {
+        std::lock_guard<std::mutex> g(dst->mu);
+        if (dst->device >= 0) HIPCHK(dst, hipSetDevice(dst->device));
+        const uint64_t n = items.size();
+        if (!dst->rhost.rebuild(std::move(items))) return set_err(dst, BMQ_E_INVAL, dst->rhost.error);
+        if (int rc = retain_publish(dst)) return rc;
+        if (out_imported) *out_imported = n;
+        return BMQ_OK;
+    }
+    // a merge: add ops through the ordinary apply path (a compaction running on dst logs them like any apply).  A topic dst holds already
+    // has its stamps replaced: counted from dst's live count around every chunk (dst->api keeps other mutators out).
+    uint64_t imported = 0, replaced = 0;
+    for (size_t lo = 0; lo < items.size();) {
+        const size_t hi = std::min(items.size(), lo + 65536);
+        std::vector<uint8_t> tb, pb, ops(hi - lo, 0);
+        std::vector<uint32_t> toff{0}, poff{0}, ot, ex;
+        std::vector<uint64_t> ts;
+        std::unordered_map<std::string, uint32_t> tix;
+        for (size_t i = lo; i < hi; i++) {
+            const auto& it = items[i];
+            auto f = tix.find(it.tenant);
+            if (f == tix.end()) {
+                f = tix.emplace(it.tenant, (uint32_t)tix.size()).first;
+                tb.insert(tb.end(), it.tenant.begin(), it.tenant.end());
+                toff.push_back((uint32_t)tb.size());
+            }
+            ot.push_back(f->second);
+            pb.insert(pb.end(), it.topic.begin(), it.topic.end());
+            poff.push_back((uint32_t)pb.size());
+            ts.push_back(it.has_ts ? it.ts : 0ull);
+            ex.push_back(it.has_ts ? it.expiry : 0xFFFFFFFFu);
+        }
+        tb.resize(tb.size() + 16, 0), pb.resize(pb.size() + 16, 0);
+        const uint64_t before = dst->drt ? dst->drt->info.n_live : dst->hrt->info.n_live;
+        const int rc = retain_apply_common(dst, tb.data(), toff.data(), (uint32_t)tix.size(), ot.data(), pb.data(), poff.data(), ops.data(), ts.data(), ex.data(),
+                                           (uint32_t)(hi - lo), nullptr);
+        if (rc) return rc;
+        const uint64_t fresh = (dst->drt ? dst->drt->info.n_live : dst->hrt->info.n_live) - before;
+        imported += fresh;
+        replaced += (hi - lo) - fresh;
+        lo = hi;
+    }
+    if (out_imported) *out_imported = imported;
+    if (out_replaced) *out_replaced = replaced;
+    return BMQ_OK;
 }
 
 int bmq_retain_match_batch_dev(bmq_engine* e, const uint8_t* d_tenants, const uint32_t* d_tenant_off, uint32_t n_tenants,

@@ -675,10 +675,41 @@ class Engine:
                                                      _ptr(poff), len(poff) - 1, _ptr(ts), _ptr(ex)))
         return self
 
-    def retain_compact_begin(self):
-        """bmq_retain_compact_begin: snapshot of the live retained topics -- the next generation starts from it"""
-        self._check(_lib.lib().bmq_retain_compact_begin(self.h))
+    def retain_compact_begin(self, start=None, end=None):
+        """bmq_retain_compact_begin[_in]: snapshot of the live retained topics -- the next generation starts from it; with a boundary it
+        takes the topics with start <= retainMessageKey < end only (the range that shrinks in a split)"""
+        if start is None and end is None:
+            self._check(_lib.lib().bmq_retain_compact_begin(self.h))
+        else:
+            self._check(_lib.lib().bmq_retain_compact_begin_in(self.h, *self._boundary(start, end)))
         return self
+
+    def retain_count_in(self, start=None, end=None) -> Tuple[int, int]:
+        """bmq_retain_count_in: (retained topics whose key lies inside the boundary, the sum of their key lengths); nothing is changed"""
+        topics, key_bytes = C.c_uint64(), C.c_uint64()
+        self._check(_lib.lib().bmq_retain_count_in(self.h, *self._boundary(start, end), C.byref(topics), C.byref(key_bytes)))
+        return int(topics.value), int(key_bytes.value)
+
+    def retain_ids_in(self, start=None, end=None) -> List[int]:
+        """bmq_retain_ids_in: ids of the retained topics whose key lies inside the boundary, ascending"""
+        b = self._boundary(start, end)
+        cap = 1024
+        n = C.c_uint32()
+        while True:
+            out = np.zeros(cap, dtype=np.uint32)
+            rc = _lib.lib().bmq_retain_ids_in(self.h, *b, _ptr(out), cap, C.byref(n))
+            if rc == -3:
+                cap = n.value
+                continue
+            self._check(rc)
+            return out[:n.value].tolist()
+
+    def retain_import(self, src: "Engine", start=None, end=None) -> Tuple[int, int]:
+        """bmq_retain_import: every retained topic of src whose key lies inside the boundary is put into this engine with its stamps,
+        without a KV scan -> (imported, replaced)"""
+        imported, replaced = C.c_uint64(), C.c_uint64()
+        self._check(_lib.lib().bmq_retain_import(self.h, src.h, *self._boundary(start, end), C.byref(imported), C.byref(replaced)))
+        return int(imported.value), int(replaced.value)
 
     def retain_compact_build(self):
         """bmq_retain_compact_build: loads the snapshot into an index of its own; no engine lock held (matching / add / remove go on)"""

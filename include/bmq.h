@@ -854,6 +854,39 @@ int bmq_retain_compact_begin(bmq_engine* e);
 int bmq_retain_compact_build(bmq_engine* e);
 int bmq_retain_compact_swap(bmq_engine* e, uint64_t* out_carried /* may be NULL */, uint64_t* out_replayed /* may be NULL */);
 int bmq_retain_compact_abort(bmq_engine* e);
+/* Split and merge of the retain store's base-kv range WITHOUT a KV scan: IKVRangeCoProc.reset(Boundary) fires on every split and merge, and
+ * RetainStoreCoProc answers it with load(), a scan of the whole range (RS/RetainStoreCoProc.java:133-137,279-296).  The retained-topic index
+ * holds no KV keys, and no id range is a key range (tenants are ranked in byte order, keys sort by tenant length first), so "is
+ * retainMessageKey(id) inside [start, end)" is a predicate over the ids, evaluated where the index lives: one kernel pass that walks the
+ * key's segments against the boundary keys and stops at the first difference, without composing the key (bmq_retain_core.h: retain_key_cmp;
+ * host-only engines run the same function on host threads).  Boundary arguments as for bmq_routes_count_in: flags bit 0 / 1 = start / end
+ * present, a present key may be empty, both present with start >= end is BMQ_E_INVAL; order = unsigned bytes, a proper prefix first
+ * (BoundaryUtil.inRange).  The key store of bmq_retain_keys_prepare is built on the first call of a generation.
+ *   bmq_retain_count_in          retained topics whose key lies inside the boundary and (out_key_bytes != NULL) the sum of their key lengths
+ *                                -- keys only, no values.  Read-only, one pass; locks and state as bmq_retain_expired.  No index loaded: 0.
+ *   bmq_retain_ids_in            their ids, ascending; buffer protocol of bmq_retain_live_ids.
+ *   bmq_retain_compact_begin_in  bmq_retain_compact_begin for a range that SHRINKS (flags = 0 is bmq_retain_compact_begin): the snapshot takes
+ *                                only the topics inside; _build / _swap / _abort as before.  The serving generation matches and mutates over
+ *                                ALL its topics until the swap; at the swap, logged ops (adds, removes, bmq_retain_remove_ids) whose key lies
+ *                                outside are not replayed: *out_carried = topics inside, *out_replayed = ops replayed.  Afterwards the engine
+ *                                does not police mutations against the boundary.
+ *   bmq_retain_import            every retained topic of src whose key lies inside the boundary goes into dst with its timestamp_hlc /
+ *                                expiry_seconds.  src is locked only while ids, stamps and strings are snapshotted, then goes on serving; a
+ *                                topic mutated during the call is imported as it was at the snapshot.  An EMPTY dst (no index, or no retained
+ *                                topic and no compaction running: the new sibling of a split) is bulk-loaded -- ranks, the fast path of '+'
+ *                                and '#', a new generation; *out_imported = topics.  Otherwise chunks of at most 65 536 add ops go through the
+ *                                ordinary apply path (a compaction running on dst logs them): a topic dst holds already has its stamps
+ *                                replaced and counts in *out_replaced, the others in *out_imported.  dst == src: BMQ_E_INVAL.  Host-only and
+ *                                device engines may be paired, and two devices (the strings cross the host: the bulk builder is a host builder).
+ * A split of range A at key s:  bmq_retain_import(B, A, start = s)  then  bmq_retain_compact_begin_in(A, end = s), _build, _swap.
+ * A merge of B into A:          bmq_retain_import(A, B, flags = 0). */
+int bmq_retain_count_in(const bmq_engine* e, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len,
+                        uint64_t* out_topics /* may be NULL */, uint64_t* out_key_bytes /* may be NULL */);
+int bmq_retain_ids_in(const bmq_engine* e, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len,
+                      uint32_t* out_ids, uint32_t cap, uint32_t* out_n);
+int bmq_retain_compact_begin_in(bmq_engine* e, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len);
+int bmq_retain_import(bmq_engine* dst, bmq_engine* src, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end,
+                      uint32_t end_len, uint64_t* out_imported /* may be NULL */, uint64_t* out_replaced /* may be NULL */);
 typedef struct bmq_retain_info {
     uint64_t n_topics;        /* retained topics now */
     uint64_t n_tenants;       /* tenants of the last bulk load */

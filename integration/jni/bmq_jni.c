@@ -27,6 +27,7 @@
 /* the statistics and the GC by id of both co-processors: integration/java/org/apache/bifromq/retain/store/gpu/NativeStore.java */
 #define NS(name) Java_org_apache_bifromq_retain_store_gpu_NativeStore_##name
 #define NK(name) Java_org_apache_bifromq_retain_store_gpu_NativeKeys_##name
+#define NR(name) Java_org_apache_bifromq_retain_store_gpu_NativeRange_##name
 
 static void throw_state(JNIEnv* env, bmq_engine* e, const char* what, int rc) {
     char msg[512];
@@ -548,6 +549,92 @@ JNIEXPORT jlong JNICALL NS(retainRemoveIds)(JNIEnv* env, jclass c, jlong h, jobj
         return 0;
     }
     return (jlong)removed;
+}
+/* ---- the retain store's range by KV boundary (RetainStoreCoProc.reset(Boundary) without the KV scan); start / end: null = the side is absent ---- */
+#define BOUNDARY_IN(start, end)                                                                                                        \
+    jsize sl = start ? (*env)->GetArrayLength(env, start) : 0, el = end ? (*env)->GetArrayLength(env, end) : 0;                        \
+    jbyte* sb = start ? (*env)->GetByteArrayElements(env, start, NULL) : NULL;                                                         \
+    jbyte* eb = end ? (*env)->GetByteArrayElements(env, end, NULL) : NULL;                                                             \
+    const uint8_t bflags = (uint8_t)((start ? 1 : 0) | (end ? 2 : 0))
+#define BOUNDARY_OUT(start, end)                                                                                                       \
+    if (start) (*env)->ReleaseByteArrayElements(env, start, sb, JNI_ABORT);                                                            \
+    if (end) (*env)->ReleaseByteArrayElements(env, end, eb, JNI_ABORT)
+/* void retainCountIn(long engine, byte[] start, byte[] end, long[] out2)     out2 = {retained topics whose key lies inside, their key bytes} */
+JNIEXPORT void JNICALL NR(retainCountIn)(JNIEnv* env, jclass c, jlong h, jbyteArray start, jbyteArray end, jlongArray out) {
+    (void)c;
+    BOUNDARY_IN(start, end);
+    uint64_t topics = 0, bytes = 0;
+    const int rc = bmq_retain_count_in(ENGINE(h), bflags, (const uint8_t*)sb, (uint32_t)sl, (const uint8_t*)eb, (uint32_t)el, &topics, &bytes);
+    BOUNDARY_OUT(start, end);
+    if (rc != BMQ_OK) {
+        throw_state(env, ENGINE(h), "bmq_retain_count_in", rc);
+        return;
+    }
+    const jlong v[2] = {(jlong)topics, (jlong)bytes};
+    (*env)->SetLongArrayRegion(env, out, 0, 2, v);
+}
+/* long retainIdsIn(long engine, byte[] start, byte[] end, IntBuffer outIds)     their ids, ascending -> count, or -(needed) */
+JNIEXPORT jlong JNICALL NR(retainIdsIn)(JNIEnv* env, jclass c, jlong h, jbyteArray start, jbyteArray end, jobject outIds) {
+    (void)c;
+    BOUNDARY_IN(start, end);
+    uint32_t n = 0;
+    const int rc = bmq_retain_ids_in(ENGINE(h), bflags, (const uint8_t*)sb, (uint32_t)sl, (const uint8_t*)eb, (uint32_t)el, (uint32_t*)ADDR(outIds),
+                                     (uint32_t)CAP(outIds), &n);
+    BOUNDARY_OUT(start, end);
+    return result_of(env, ENGINE(h), "bmq_retain_ids_in", rc, n);
+}
+/* void retainCompactBeginIn(long engine, byte[] start, byte[] end)     retainCompactBegin for a range that shrinks: the next generation takes the
+ * topics whose key lies inside only; retainCompactBuild / retainCompactSwap / retainCompactAbort as before */
+JNIEXPORT void JNICALL NR(retainCompactBeginIn)(JNIEnv* env, jclass c, jlong h, jbyteArray start, jbyteArray end) {
+    (void)c;
+    BOUNDARY_IN(start, end);
+    const int rc = bmq_retain_compact_begin_in(ENGINE(h), bflags, (const uint8_t*)sb, (uint32_t)sl, (const uint8_t*)eb, (uint32_t)el);
+    BOUNDARY_OUT(start, end);
+    if (rc != BMQ_OK) throw_state(env, ENGINE(h), "bmq_retain_compact_begin_in", rc);
+}
+/* void retainReset(long engine, byte[] start, byte[] end, long[] out2)     RetainStoreCoProc.reset(Boundary) in one call: retainCompactBeginIn, the
+ * build (no engine lock held: matching and add / remove go on) and the swap; a failure behind the begin aborts the half-built generation.
+ * out2 = {topics kept, logged ops replayed} */
+JNIEXPORT void JNICALL NR(retainReset)(JNIEnv* env, jclass c, jlong h, jbyteArray start, jbyteArray end, jlongArray out) {
+    (void)c;
+    BOUNDARY_IN(start, end);
+    uint64_t carried = 0, replayed = 0;
+    const char* what = "bmq_retain_compact_begin_in";
+    int rc = bmq_retain_compact_begin_in(ENGINE(h), bflags, (const uint8_t*)sb, (uint32_t)sl, (const uint8_t*)eb, (uint32_t)el);
+    BOUNDARY_OUT(start, end);
+    if (rc == BMQ_OK) {
+        what = "bmq_retain_compact_build";
+        if ((rc = bmq_retain_compact_build(ENGINE(h))) == BMQ_OK) {
+            what = "bmq_retain_compact_swap";
+            rc = bmq_retain_compact_swap(ENGINE(h), &carried, &replayed);
+        }
+        if (rc != BMQ_OK) {
+            throw_state(env, ENGINE(h), what, rc); /* (reads bmq_last_error before the abort replaces it) */
+            (void)bmq_retain_compact_abort(ENGINE(h));
+            return;
+        }
+    }
+    if (rc != BMQ_OK) {
+        throw_state(env, ENGINE(h), what, rc);
+        return;
+    }
+    const jlong v[2] = {(jlong)carried, (jlong)replayed};
+    (*env)->SetLongArrayRegion(env, out, 0, 2, v);
+}
+/* void retainImport(long dst, long src, byte[] start, byte[] end, long[] out2)     every retained topic of src whose key lies inside goes into dst
+ * with its stamps; out2 = {imported, replaced} */
+JNIEXPORT void JNICALL NR(retainImport)(JNIEnv* env, jclass c, jlong dst, jlong src, jbyteArray start, jbyteArray end, jlongArray out) {
+    (void)c;
+    BOUNDARY_IN(start, end);
+    uint64_t imported = 0, replaced = 0;
+    const int rc = bmq_retain_import(ENGINE(dst), ENGINE(src), bflags, (const uint8_t*)sb, (uint32_t)sl, (const uint8_t*)eb, (uint32_t)el, &imported, &replaced);
+    BOUNDARY_OUT(start, end);
+    if (rc != BMQ_OK) {
+        throw_state(env, ENGINE(dst), "bmq_retain_import", rc);
+        return;
+    }
+    const jlong v[2] = {(jlong)imported, (jlong)replaced};
+    (*env)->SetLongArrayRegion(env, out, 0, 2, v);
 }
 /* out[0] = tenants, out[1] = bytes of their ids: what the census calls need (also when they return -1: a buffer was too small) */
 static jlong census_result(JNIEnv* env, bmq_engine* e, const char* what, int rc, uint32_t n, uint64_t bytes, jlongArray needed) {

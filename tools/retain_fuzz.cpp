@@ -13,6 +13,12 @@
 //   * id -> retainMessageKey (key_len_one / key_write_one over the string store of the bulk-loaded ids: what k_r_key_len / k_r_key_write
 //     run): after every step the keys of every id in [0, id_bound + 8) against retain_message_key of the model's strings (bmq_codec.cpp),
 //     empty for every id that is dead, was never handed out or lies behind the bound.
+//   * the KV boundary of the range (retain_key_cmp / retain_key_in_boundary through RetainDyn::boundary_select: what k_r_boundary runs): after
+//     every step count_in / ids_in of boundaries cut out of the model's keys (whole keys, prefixes that end in every segment, neighbours of
+//     keys) against `start <= key < end` over retain_message_key; every fourth step the steps of a split -- the topics inside a boundary
+//     loaded into an index of their own (an import into an empty range), ops inside and outside the boundary of which only the inside ones are
+//     replayed there (the bounded generation change), the other half added on top through the apply path (an import into a non-empty range) --
+//     each against the key-set model.
 // Build + run: make -C bifromq_amd/csrc fuzz   (tests/test_host.py runs a short round of both builds)
 #include <algorithm>
 #include <cstdio>
@@ -223,7 +229,7 @@ int main(int argc, char** argv) {
     rt.tiny = true;
     RetainIndexView bview{};
     uint64_t checks = 0, n_ops = 0, n_batches = 0, n_id_removals = 0, n_keys = 0;
-    auto base_view = [&]() {
+    auto view_of = [](const RetainIndexHost& h) {
         RetainIndexView v{};
         v.nodes = h.nodes.data();
         v.edges = h.edges.data();
@@ -235,6 +241,77 @@ int main(int argc, char** argv) {
         v.dict_group_mask = (uint32_t)h.dict.size() / DICT_GROUP - 1;
         v.pool = h.pool.data();
         return v;
+    };
+    auto base_view = [&]() { return view_of(h); };
+    uint64_t n_bounds = 0;
+    using Stamp = std::pair<uint64_t, uint32_t>;
+    // BoundaryUtil.inRange over the model's key
+    auto inside = [](const std::string& k, uint32_t flags, const std::string& s, const std::string& e) {
+        return (!(flags & 1u) || k.compare(s) >= 0) && (!(flags & 2u) || k.compare(e) < 0);
+    };
+    // (tenant, topic) -> stamps of what an index retains now, through its own listing calls
+    auto state_of = [&](RetainDyn<HostExec>& r, const RetainIndexHost& hh, std::map<Key, Stamp>& out, const std::vector<uint32_t>* only) -> bool {
+        std::vector<uint32_t> ids;
+        GcQuery q{};
+        q.live_only = 1;
+        q.override_expiry = -1;
+        if (only) ids = *only;
+        else if (!r.select(q, nullptr, 0, ids)) return false;
+        std::vector<unsigned long long> ts;
+        std::vector<uint32_t> ex, ov, lens;
+        std::vector<uint8_t> bytes;
+        if (!r.payload(ts, ex)) return false;
+        for (uint32_t id : ids)
+            if (id >= hh.n_topics) ov.push_back(id);
+        if (!r.overlay_topics(ov.data(), (uint32_t)ov.size(), lens, bytes)) return false;
+        size_t off = 0, k = 0;
+        out.clear();
+        for (uint32_t id : ids) {
+            Key key;
+            if (id < hh.n_topics) {
+                std::string_view tn, tp;
+                if (!hh.topic(id, tn, tp)) return false;
+                key = {std::string(tn), std::string(tp)};
+            } else {
+                key = {std::string((const char*)bytes.data() + off, lens[2 * k]), std::string((const char*)bytes.data() + off + lens[2 * k], lens[2 * k + 1] - lens[2 * k])};
+                off += lens[2 * k + 1];
+                k++;
+            }
+            out[key] = {ts[id], ex[id]};
+        }
+        return true;
+    };
+    auto items_of = [](const std::map<Key, Stamp>& m) {
+        std::vector<RetainIndexHost::Item> items;
+        for (auto& kv : m) {
+            RetainIndexHost::Item it;
+            it.tenant = kv.first.first, it.topic = kv.first.second;
+            it.ts = kv.second.first, it.expiry = kv.second.second;
+            it.has_ts = !(it.ts == 0 && it.expiry == 0xFFFFFFFFu);
+            items.push_back(std::move(it));
+        }
+        return items;
+    };
+    // ops (add with its stamps / remove) through the apply path of an index, one op per tenant table entry
+    struct MOp {
+        Key k;
+        uint8_t op;
+        Stamp st;
+    };
+    auto apply_ops = [&](RetainDyn<HostExec>& r, const std::vector<MOp>& ops) -> bool {
+        if (ops.empty()) return true;
+        std::string tb, pb;
+        std::vector<uint32_t> toff{0}, poff{0}, ot, ex;
+        std::vector<uint8_t> op;
+        std::vector<unsigned long long> ts;
+        for (size_t i = 0; i < ops.size(); i++) {
+            tb += ops[i].k.first, toff.push_back((uint32_t)tb.size());
+            pb += ops[i].k.second, poff.push_back((uint32_t)pb.size());
+            ot.push_back((uint32_t)i), op.push_back(ops[i].op), ts.push_back(ops[i].st.first), ex.push_back(ops[i].st.second);
+        }
+        tb.append(16, '\0'), pb.append(16, '\0');
+        return r.apply((const uint8_t*)tb.data(), toff.data(), (uint32_t)ops.size(), ot.data(), (const uint8_t*)pb.data(), poff.data(), op.data(), ts.data(), ex.data(),
+                       (uint32_t)ops.size(), nullptr);
     };
     for (int round = 0; round < rounds; round++) {
         const bool full = round == 0 || rnd(8) == 0;
@@ -454,6 +531,88 @@ int main(int argc, char** argv) {
             if (want.compare(0, want.size(), (const char*)out.data(), want.size()) != 0 || out[want.size()] != 0xEE) FAIL("round %d: key bytes differ from retain_message_key\n", round);
             n_keys += live_by_id.size();
         }
+        { // the KV boundary: count_in / ids_in against `start <= key < end` over the model's keys
+            std::vector<std::pair<std::string, uint32_t>> keyed;
+            for (auto& kv : live) keyed.push_back({retain_message_key(kv.first.first, kv.first.second), kv.second});
+            auto cut = [&]() -> std::string {
+                if (keyed.empty() || rnd(12) == 0) return rnd(2) ? std::string() : std::string(1 + rnd(4), (char)(rnd(2) ? 0xFF : 0x00));
+                std::string k = keyed[rnd(keyed.size())].first;
+                switch (rnd(6)) {
+                case 0: return k;
+                case 1: return k.substr(0, rnd(k.size()));                 // ends in any segment: a proper prefix sorts first
+                case 2: return k + std::string(1 + rnd(300), '\0');
+                case 3: k.back() = (char)((uint8_t)k.back() + 1); return k;
+                case 4: k[rnd(k.size())] ^= (char)(1 + rnd(255)); return k; // one byte off, anywhere
+                default: return k.substr(0, 3 + ((uint8_t)k[2] | ((uint8_t)k[1] << 8)));   // the head exactly
+                }
+            };
+            for (int b = 0; b < 24; b++) {
+                std::string s = cut(), e = cut();
+                const uint32_t flags = b == 0 ? 0u : (uint32_t)(1 + rnd(3));
+                if (flags == 3u && s.compare(e) >= 0) std::swap(s, e);
+                if (flags == 3u && s == e) e += '\0';
+                uint64_t topics = 0, kbytes = 0, want_bytes = 0;
+                std::vector<uint32_t> got, want;
+                if (!rt.boundary_select(h, flags, (const uint8_t*)s.data(), (uint32_t)s.size(), (const uint8_t*)e.data(), (uint32_t)e.size(), topics, b % 2 ? &kbytes : nullptr,
+                                        b % 3 ? &got : nullptr))
+                    FAIL("round %d: boundary_select failed: %s\n", round, rt.error.c_str());
+                for (auto& kv : keyed)
+                    if (inside(kv.first, flags, s, e)) want.push_back(kv.second), want_bytes += kv.first.size();
+                std::sort(want.begin(), want.end());
+                if (topics != want.size() || (b % 2 && kbytes != want_bytes) || (b % 3 && got != want))
+                    FAIL("round %d: boundary (flags %u): %llu topics / %llu bytes / %zu ids, the model %zu / %llu\n", round, flags, (unsigned long long)topics,
+                         (unsigned long long)kbytes, got.size(), want.size(), (unsigned long long)want_bytes);
+                n_bounds++;
+            }
+            if (round % 4 == 0 && !keyed.empty()) { // the steps of a split at a key of the model
+                const std::string c = cut();
+                std::map<Key, Stamp> all, lower, upper, got;
+                for (auto& kv : live) (inside(retain_message_key(kv.first.first, kv.first.second), 2u, "", c) ? lower : upper)[kv.first] = stamp[kv.first];
+                // an import into an EMPTY range: the ids inside [c, +inf), their strings and stamps, bulk-loaded
+                uint64_t topics = 0;
+                std::vector<uint32_t> ids;
+                if (!rt.boundary_select(h, 1u, (const uint8_t*)c.data(), (uint32_t)c.size(), nullptr, 0, topics, nullptr, &ids) || !state_of(rt, h, got, &ids))
+                    FAIL("round %d: split: snapshot failed: %s\n", round, rt.error.c_str());
+                if (got != upper) FAIL("round %d: split: the upper half has %zu topics, the model %zu\n", round, got.size(), upper.size());
+                RetainIndexHost h2;
+                RetainDyn<HostExec> rt2(hx);
+                rt2.tiny = true;
+                if (!h2.rebuild(items_of(got))) FAIL("round %d: split: rebuild failed\n", round);
+                const RetainIndexView v2 = view_of(h2);
+                if (!rt2.reset(v2, h2) || !state_of(rt2, h2, got, nullptr)) FAIL("round %d: split: load failed\n", round);
+                if (got != upper || rt2.info.base_n != upper.size()) FAIL("round %d: split: the loaded sibling differs from the model\n", round);
+                // the bounded generation change of the sibling's own range: ops inside and outside, only the inside ones are replayed
+                std::vector<MOp> ops, kept;
+                for (int i = 0; i < 40; i++) {
+                    MOp o;
+                    if (!live.empty() && rnd(2)) {
+                        auto it = live.begin();
+                        std::advance(it, rnd(live.size()));
+                        o.k = it->first;
+                    } else o.k = {tenants[rnd(tenants.size())], rand_topic()};
+                    o.op = (uint8_t)rnd(2);
+                    o.st = {(uint64_t)(1000 + rnd(100000)) << 16, (uint32_t)rnd(500)};
+                    ops.push_back(o);
+                    if (!inside(retain_message_key(o.k.first, o.k.second), 1u, c, "")) continue;
+                    kept.push_back(o);
+                    if (o.op == 0) upper[o.k] = o.st;
+                    else upper.erase(o.k);
+                }
+                if (!apply_ops(rt2, kept) || !state_of(rt2, h2, got, nullptr)) FAIL("round %d: split: replay failed: %s\n", round, rt2.error.c_str());
+                if (got != upper) FAIL("round %d: split: after the replay the sibling has %zu topics, the model %zu\n", round, got.size(), upper.size());
+                uint64_t in2 = 0;
+                if (!rt2.boundary_select(h2, 2u, nullptr, 0, (const uint8_t*)c.data(), (uint32_t)c.size(), in2, nullptr, nullptr) || in2 != 0)
+                    FAIL("round %d: split: %llu topics of the sibling lie below the cut\n", round, (unsigned long long)in2);
+                // an import into a NON-EMPTY range (the merge back): the lower half as add ops on top
+                std::vector<MOp> adds;
+                for (auto& kv : lower) adds.push_back({kv.first, 0, kv.second});
+                const uint64_t before = rt2.info.n_live;
+                if (!apply_ops(rt2, adds) || !state_of(rt2, h2, got, nullptr)) FAIL("round %d: merge: apply failed: %s\n", round, rt2.error.c_str());
+                all = upper;
+                for (auto& kv : lower) all[kv.first] = kv.second;
+                if (got != all || rt2.info.n_live - before != lower.size()) FAIL("round %d: merge: %zu topics, the model %zu\n", round, got.size(), all.size());
+            }
+        }
         for (int s = 0; s < 40 && !live.empty(); s++) { // stamps of the last add
             auto it = live.begin();
             std::advance(it, rnd(live.size()));
@@ -528,7 +687,8 @@ int main(int argc, char** argv) {
             }
         }
     }
-    printf("retain_fuzz ok: seed %llu, %d rounds, %u threads, %llu ops in %llu batches, %llu topics removed by id, %llu filter checks, %llu keys\n", (unsigned long long)seed, rounds,
-           threads, (unsigned long long)n_ops, (unsigned long long)n_batches, (unsigned long long)n_id_removals, (unsigned long long)checks, (unsigned long long)n_keys);
+    printf("retain_fuzz ok: seed %llu, %d rounds, %u threads, %llu ops in %llu batches, %llu topics removed by id, %llu filter checks, %llu keys, %llu boundaries\n", (unsigned long long)seed, rounds,
+           threads, (unsigned long long)n_ops, (unsigned long long)n_batches, (unsigned long long)n_id_removals, (unsigned long long)checks, (unsigned long long)n_keys,
+           (unsigned long long)n_bounds);
     return 0;
 }
