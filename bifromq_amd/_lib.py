@@ -21,7 +21,7 @@ ABI_SYMBOLS = [
     "bmq_match_finish", "bmq_set_kernel_timing", "bmq_match_submit", "bmq_match_wait", "bmq_match_submit_fmt", "bmq_match_submit_dev", "bmq_match_wait_dev", "bmq_match_wait_counts", "bmq_match_wait_ranges", "bmq_match_wait_grouped", "bmq_host_alloc", "bmq_host_free", "bmq_sync", "bmq_stats_get", "bmq_stream", "bmq_match_all", "bmq_route_key_encode",
     "bmq_route_key_decode", "bmq_java_string_hash", "bmq_range_lookup", "bmq_comm_unique_id", "bmq_comm_init", "bmq_comm_destroy", "bmq_exchange_fanout",
     "bmq_exchange_csr", "bmq_exchange_wait", "bmq_partition_batch_dev", "bmq_retain_message_key", "bmq_retain_filter_route", "bmq_retain_rebuild", "bmq_retain_rebuild_ex", "bmq_retain_apply", "bmq_retain_apply_ex", "bmq_retain_topic",
-    "bmq_retain_topic_info", "bmq_retain_find_all", "bmq_retain_expired", "bmq_retain_apply_batch", "bmq_retain_compact", "bmq_retain_compact_begin", "bmq_retain_compact_build", "bmq_retain_compact_swap", "bmq_retain_compact_abort", "bmq_retain_info_get",
+    "bmq_retain_topic_info", "bmq_retain_find_all", "bmq_retain_expired", "bmq_retain_apply_batch", "bmq_retain_compact", "bmq_retain_compact_begin", "bmq_retain_compact_build", "bmq_retain_compact_swap", "bmq_retain_compact_abort", "bmq_retain_info_get", "bmq_retain_build_info_get",
     "bmq_retain_live_ids", "bmq_retain_topics", "bmq_retain_tenant_counts", "bmq_retain_message_keys", "bmq_retain_remove_ids", "bmq_retain_keys_prepare", "bmq_retain_keys_by_id", "bmq_retain_keys_match",
     "bmq_retain_count_in", "bmq_retain_ids_in", "bmq_retain_compact_begin_in", "bmq_retain_import",
     "bmq_retain_match_batch", "bmq_retain_match_batch_dev", "bmq_retain_match_limited", "bmq_batcher_create", "bmq_batcher_destroy",
@@ -47,7 +47,7 @@ class Config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("wave_queue_cap", C.c_uint32),
                 ("wave_pair_cap", C.c_uint32), ("slow_scratch_mb", C.c_uint32), ("kernel_timing", C.c_uint32),
                 ("dedup_min_topics", C.c_uint32), ("dedup_sorted", C.c_uint32), ("region_slack", C.c_uint32), ("tail_records", C.c_uint32),
-                ("child_filters", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+                ("child_filters", C.c_uint32), ("retain_builder", C.c_uint32), ("reserved", C.c_uint32 * 1)]
 
 
 class Stats(C.Structure):
@@ -94,6 +94,12 @@ class RetainInfo(C.Structure):
     _fields_ = [("n_topics", C.c_uint64), ("n_tenants", C.c_uint64), ("id_bound", C.c_uint64), ("loaded_topics", C.c_uint64),
                 ("loaded_removed", C.c_uint64), ("added_ids", C.c_uint64), ("overlay_nodes", C.c_uint64), ("epoch", C.c_uint64),
                 ("generation", C.c_uint64)]
+
+
+class RetainBuildInfo(C.Structure):
+    _fields_ = [("builder", C.c_uint32), ("fallback", C.c_uint32), ("n_items", C.c_uint64), ("n_topics", C.c_uint64), ("n_tenants", C.c_uint64),
+                ("n_nodes", C.c_uint64), ("n_edges", C.c_uint64), ("n_edge_overflows", C.c_uint64), ("n_posts", C.c_uint64), ("n_gp_runs", C.c_uint64),
+                ("n_tokens", C.c_uint64), ("max_depth", C.c_uint32), ("ms_total", C.c_float), ("ms_sort", C.c_float), ("n_gp_overflows", C.c_uint32)]
 
 
 class ShareInfo(C.Structure):
@@ -208,6 +214,7 @@ def lib() -> C.CDLL:
             "bmq_retain_apply_batch": (C.c_int, [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, u32, vp]),
             "bmq_retain_compact": (C.c_int, [vp]),
             "bmq_retain_info_get": (C.c_int, [vp, P(RetainInfo)]),
+            "bmq_retain_build_info_get": (C.c_int, [vp, P(RetainBuildInfo)]),
             "bmq_retain_live_ids": (C.c_int, [vp, C.c_char_p, u32, vp, u32, P(u32)]),
             "bmq_retain_match_batch": (C.c_int, [vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, u64, P(u64)]),
             "bmq_retain_match_batch_dev": (C.c_int, [vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, u64, vp]),

@@ -33,6 +33,7 @@
 #include "bmq_format_kernels.h"
 #include "bmq_range_core.h"
 #include "bmq_retain.h"
+#include "bmq_retain_build.h"
 #include "bmq_retain_dyn.h"
 #include "bmq_retain_kernels.h"
 #include "bmq_share.h"
@@ -177,6 +178,11 @@ struct bmq_engine {
     std::unique_ptr<RetainDyn<HostExec>> hrt; // ... of a host-only engine (inspection, sanitizer fuzzers)
     RetainIndexView rhview{};                 // host-only engine: the bulk-loaded arrays where RetainIndexHost keeps them
     bool rbuilt = false;
+    // bmq_config.retain_builder = 1: the bulk load runs on the executor (bmq_retain_build.h) and the serving generation's arrays lie in its buffers
+    std::unique_ptr<RetainBuild<DevExec>> drb;
+    std::unique_ptr<RetainBuild<HostExec>> hrb;
+    bool rb_serving = false;      // the serving generation was built there (rhost holds the catalogue only, its image vectors are empty)
+    RetainBuildInfo rbinfo{};     // the serving generation's bulk load (bmq_retain_build_info_get)
     // bmq_retain_compact_begin / _build / _swap: the next generation of the retained-topic index, built beside the serving one (round 6)
     struct RetainCompaction {
         bool active = false;  // (guarded by mu, like the log; `next` and `items` belong to the one thread that drives the compaction)
@@ -194,6 +200,8 @@ struct bmq_engine {
         Boundary bound;                           // bmq_retain_compact_begin_in: the next generation keeps the topics whose key lies inside (flags 0: all)
         uint64_t log_bytes = 0;
         bool log_overflow = false;
+        uint64_t n_items = 0; // what bmq_retain_build_info tells of the generation once it serves
+        float ms_build = 0;
     } rcmp;
     uint64_t repoch = 0;      // +1 per retain rebuild / apply / compact
     uint64_t rgeneration = 0; // +1 per retain rebuild / compact: topic ids of different generations are unrelated
@@ -1012,7 +1020,7 @@ int bmq_engine_create(const bmq_config* cfg, bmq_engine** out) {
     if (const char* v = bmq_env("BMQ_QCAP")) c.wave_queue_cap = (uint32_t)atoi(v); // profiling experiments
     if (const char* v = bmq_env("BMQ_PCAP")) c.wave_pair_cap = (uint32_t)atoi(v);
     if ((c.wave_queue_cap != 0 && c.wave_queue_cap != 128) || (c.wave_pair_cap != 0 && c.wave_pair_cap != 128)) return BMQ_E_INVAL;
-    if (c.region_slack > 64 || c.tail_records > 1 || c.child_filters > 1) return BMQ_E_INVAL;
+    if (c.region_slack > 64 || c.tail_records > 1 || c.child_filters > 1 || c.retain_builder > 1) return BMQ_E_INVAL;
     const bool smallest = c.wave_queue_cap == 128 || c.wave_pair_cap == 128;
     c.wave_queue_cap = smallest ? WALK_QC_SMALLEST : WALK_QC_DEFAULT; // (what bmq_config reports back / BatchArgs carries: the geometry in use)
     c.wave_pair_cap = smallest ? WALK_PC_SMALLEST : WALK_PC_DEFAULT;
@@ -1057,12 +1065,14 @@ int bmq_engine_create(const bmq_config* cfg, bmq_engine** out) {
         e->dix->tail_records = c.tail_records == 0;
         e->dix->child_filters = c.child_filters == 0;
         e->drt = std::make_unique<RetainDyn<DevExec>>(e->dx);
+        if (c.retain_builder) e->drb = std::make_unique<RetainBuild<DevExec>>(e->dx);
     } else {
         e->hix = std::make_unique<DistIndex<HostExec>>(e->hx);
         if (c.region_slack) e->hix->slack_num = c.region_slack;
         e->hix->tail_records = c.tail_records == 0;
         e->hix->child_filters = c.child_filters == 0;
         e->hrt = std::make_unique<RetainDyn<HostExec>>(e->hx);
+        if (c.retain_builder) e->hrb = std::make_unique<RetainBuild<HostExec>>(e->hx);
     }
     *out = e.release();
     return BMQ_OK;
@@ -1109,6 +1119,7 @@ void bmq_engine_destroy(bmq_engine* e) {
         e->dfo.reset();
         e->dsh.reset();
         e->drt.reset();
+        e->drb.reset();
         e->dix.reset(); // frees the HBM arrays while the stream still exists
         e->dx.release(e->dx.tmp);
         e->dx.tmp = nullptr;

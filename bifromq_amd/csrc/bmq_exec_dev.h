@@ -16,6 +16,7 @@
 #include "bmq_census_kernels.h"
 #include "bmq_fanout_core.h"
 #include "bmq_fanout_kernels.h"
+#include "bmq_retain_build_kernels.h"
 #include "bmq_retain_core.h"
 #include "bmq_share_kernels.h"
 
@@ -641,6 +642,146 @@ struct DevExec {
     }
     bool r_node_write(const RetainMut& m, const uint32_t* nodes, uint32_t n, const unsigned long long* offs, uint8_t* out) {
         hipLaunchKernelGGL(k_r_node_write, grid(n, BK), dim3(BK), 0, stream, m, nodes, n, offs, out);
+        return launched();
+    }
+    // ---- bulk load of the retained-topic index (bmq_retain_build_kernels.h): one call per stage, in the order of RetainBuild::build ----
+    bool rb_sort_items(const RbArgs& B) { // a merge sort with the comparator over the packed strings; stable: of equal items the last one stays the last
+        if (B.n_items == 0) return true;
+        hipLaunchKernelGGL(k_rb_iota, grid(B.n_items, RBK), dim3(RBK), 0, stream, B.idx, B.n_items);
+        if (!launched()) return false;
+        const RbItemLess less{B.topics, B.topic_off, B.item_tenant};
+        size_t bytes = 0;
+        if (!BMQ_X(hipcub::DeviceMergeSort::StableSortKeys(nullptr, bytes, B.idx, (int)B.n_items, less, stream))) return false;
+        if (!ensure_tmp(bytes)) return false;
+        return BMQ_X(hipcub::DeviceMergeSort::StableSortKeys(tmp, bytes, B.idx, (int)B.n_items, less, stream));
+    }
+    bool rb_fill16(void* p, uint64_t n) {
+        if (n == 0) return true;
+        hipLaunchKernelGGL(k_rb_fill16, grid(n, RBK), dim3(RBK), 0, stream, (uint4*)p, (unsigned long long)n);
+        return launched();
+    }
+    bool rb_iota(uint32_t* p, uint32_t n) {
+        if (n == 0) return true;
+        hipLaunchKernelGGL(k_rb_iota, grid(n, RBK), dim3(RBK), 0, stream, p, n);
+        return launched();
+    }
+    bool sort_pairs64(const unsigned long long* keys_in, unsigned long long* keys_out, const uint32_t* vals_in, uint32_t* vals_out, uint32_t n) {
+        size_t bytes = 0; // LSD radix sort: stable
+        if (!BMQ_X(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, keys_in, keys_out, vals_in, vals_out, (int)n, 0, 64, stream))) return false;
+        if (!ensure_tmp(bytes)) return false;
+        return BMQ_X(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, (int)n, 0, 64, stream));
+    }
+    bool rb_keep(const RbArgs& B) {
+        if (B.n_items == 0) return true;
+        hipLaunchKernelGGL(k_rb_keep, grid(B.n_items, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_rank(const RbArgs& B) {
+        if (B.n_items == 0) return true;
+        hipLaunchKernelGGL(k_rb_rank, grid(B.n_items, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_shape(const RbArgs& B) {
+        if (B.n_topics == 0) return true;
+        hipLaunchKernelGGL(k_rb_shape, grid(B.n_topics, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_count(const RbArgs& B) {
+        if (B.n_tenants == 0) return true;
+        hipLaunchKernelGGL(k_rb_count, grid(B.n_tenants, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_intern(const RbArgs& B) {
+        if (B.n_nodes == 0) return true;
+        hipLaunchKernelGGL(k_rb_intern, grid(B.n_nodes, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_owner(const RbArgs& B) {
+        hipLaunchKernelGGL(k_rb_owner, grid(B.own_mask + 1u, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_place(const RbArgs& B) {
+        hipLaunchKernelGGL(k_rb_place, grid(B.own_mask + 1u, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_token(const RbArgs& B) {
+        if (B.n_nodes == 0) return true;
+        hipLaunchKernelGGL(k_rb_token, grid(B.n_nodes, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_edge(const RbArgs& B) {
+        if (B.n_nodes == 0) return true;
+        hipLaunchKernelGGL(k_rb_edge, grid(B.n_nodes, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_edge_overflow(const RbArgs& B) {
+        if (B.n_nodes == 0) return true;
+        hipLaunchKernelGGL(k_rb_edge_overflow, grid(B.n_nodes, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_post_flag(const RbArgs& B) {
+        if (B.n_nodes == 0) return true;
+        hipLaunchKernelGGL(k_rb_post_flag, grid(B.n_nodes, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_post_emit(const RbArgs& B) {
+        if (B.n_nodes == 0) return true;
+        hipLaunchKernelGGL(k_rb_post_emit, grid(B.n_nodes, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_post_gp(const RbArgs& B) {
+        if (B.n_posts == 0) return true;
+        hipLaunchKernelGGL(k_rb_post_gp, grid(B.n_posts, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_post_write(const RbArgs& B) {
+        if (B.n_posts == 0) return true;
+        hipLaunchKernelGGL(k_rb_post_write, grid(B.n_posts, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_post_tenant(const RbArgs& B) {
+        if (B.n_tenants == 0) return true;
+        hipLaunchKernelGGL(k_rb_post_tenant, grid(B.n_tenants, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_run_start(const RbArgs& B) {
+        if (B.n_posts == 0) return true;
+        hipLaunchKernelGGL(k_rb_run_start, grid(B.n_posts, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_gp(const RbArgs& B) {
+        if (B.n_runs == 0) return true;
+        hipLaunchKernelGGL(k_rb_gp, grid(B.n_runs, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_gp_overflow(const RbArgs& B) {
+        if (B.n_runs == 0) return true;
+        hipLaunchKernelGGL(k_rb_gp_overflow, grid(B.n_runs, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_tenant(const RbArgs& B) {
+        if (B.n_tenants == 0) return true;
+        hipLaunchKernelGGL(k_rb_tenant, grid(B.n_tenants, RBK), dim3(RBK), 0, stream, B);
+        return launched();
+    }
+    bool rb_head(const RbArgs& B, uint32_t d) {
+        hipLaunchKernelGGL(k_rb_head, grid(B.n_topics, RBK), dim3(RBK), 0, stream, B, d);
+        return launched();
+    }
+    bool rb_root(const RbArgs& B, const uint32_t* S1) {
+        hipLaunchKernelGGL(k_rb_root, grid(B.n_tenants, RBK), dim3(RBK), 0, stream, B, S1);
+        return launched();
+    }
+    bool rb_emit(const RbArgs& B, uint32_t d, const uint32_t* Sp, const uint32_t* Sc, const uint32_t* Sn) {
+        hipLaunchKernelGGL(k_rb_emit, grid(B.n_topics, RBK), dim3(RBK), 0, stream, B, d, Sp, Sc, Sn);
+        return launched();
+    }
+    bool rb_close(const RbArgs& B, uint32_t d, const uint32_t* Sc, const uint32_t* Sn) {
+        hipLaunchKernelGGL(k_rb_close, grid(B.n_topics, RBK), dim3(RBK), 0, stream, B, d, Sc, Sn);
+        return launched();
+    }
+    bool rb_advance(const RbArgs& B, const uint32_t* Sc) {
+        hipLaunchKernelGGL(k_rb_advance, grid(B.n_tenants, RBK), dim3(RBK), 0, stream, B, Sc);
         return launched();
     }
     bool r_find_tenant(const RetainMut& m, const uint8_t* name, uint32_t len, uint32_t* out) {

@@ -14,6 +14,7 @@
 
 #include "bmq_build_core.h"
 #include "bmq_fanout_core.h"
+#include "bmq_retain_build_core.h"
 #include "bmq_retain_core.h"
 #include "bmq_share_core.h"
 
@@ -331,6 +332,127 @@ struct HostExec {
     }
     bool r_key_write(const RetainMut& m, const RetainKeyStore& ks, const uint32_t* ids, uint32_t n, const unsigned long long* offs, uint8_t* out) {
         par(n, [&](size_t i) { key_write_one(m, ks, ids[i], out + offs[i], offs[i + 1] - offs[i]); });
+        return true;
+    }
+    // ---- bulk load of the retained-topic index (bmq_retain_build_core.h): one call per stage, in the order of RetainBuild::build ----
+    bool rb_sort_items(const RbArgs& B) { // stable: of equal items the last one stays the last
+        std::iota(B.idx, B.idx + B.n_items, 0u);
+        std::stable_sort(B.idx, B.idx + B.n_items, RbItemLess{B.topics, B.topic_off, B.item_tenant});
+        return true;
+    }
+    bool rb_fill16(void* p, uint64_t n) {
+        uint32_t* q = (uint32_t*)p;
+        par(n, [&](size_t i) { q[4 * i] = NONE, q[4 * i + 1] = q[4 * i + 2] = q[4 * i + 3] = 0u; });
+        return true;
+    }
+    bool rb_iota(uint32_t* p, uint32_t n) {
+        std::iota(p, p + n, 0u);
+        return true;
+    }
+    bool sort_pairs64(const unsigned long long* keys_in, unsigned long long* keys_out, const uint32_t* vals_in, uint32_t* vals_out, uint32_t n) {
+        std::vector<uint32_t> order(n);
+        std::iota(order.begin(), order.end(), 0u);
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t c) { return keys_in[a] < keys_in[c]; });
+        for (uint32_t i = 0; i < n; i++) {
+            keys_out[i] = keys_in[order[i]];
+            vals_out[i] = vals_in[order[i]];
+        }
+        return true;
+    }
+    bool rb_keep(const RbArgs& B) {
+        par(B.n_items, [&](size_t i) { rb_keep_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_rank(const RbArgs& B) {
+        par(B.n_items, [&](size_t i) { rb_rank_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_shape(const RbArgs& B) {
+        par(B.n_topics, [&](size_t i) { rb_shape_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_count(const RbArgs& B) {
+        par(B.n_tenants, [&](size_t i) { rb_count_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_intern(const RbArgs& B) {
+        par(B.n_nodes, [&](size_t i) { rb_intern_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_owner(const RbArgs& B) {
+        par(B.own_mask + 1u, [&](size_t i) { rb_owner_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_place(const RbArgs& B) {
+        par(B.own_mask + 1u, [&](size_t i) { rb_place_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_token(const RbArgs& B) {
+        par(B.n_nodes, [&](size_t i) { rb_token_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_edge(const RbArgs& B) {
+        par(B.n_nodes, [&](size_t i) { rb_edge_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_edge_overflow(const RbArgs& B) {
+        par(B.n_nodes, [&](size_t i) { rb_edge_overflow_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_post_flag(const RbArgs& B) {
+        par(B.n_nodes, [&](size_t i) { rb_post_flag_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_post_emit(const RbArgs& B) {
+        par(B.n_nodes, [&](size_t i) { rb_post_emit_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_post_gp(const RbArgs& B) {
+        par(B.n_posts, [&](size_t i) { rb_post_gp_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_post_write(const RbArgs& B) {
+        par(B.n_posts, [&](size_t i) { rb_post_write_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_post_tenant(const RbArgs& B) {
+        par(B.n_tenants, [&](size_t i) { rb_post_tenant_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_run_start(const RbArgs& B) {
+        par(B.n_posts, [&](size_t i) { rb_run_start_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_gp(const RbArgs& B) {
+        par(B.n_runs, [&](size_t i) { rb_gp_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_gp_overflow(const RbArgs& B) {
+        par(B.n_runs, [&](size_t i) { rb_gp_overflow_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_tenant(const RbArgs& B) {
+        par(B.n_tenants, [&](size_t i) { rb_tenant_one(B, (uint32_t)i); });
+        return true;
+    }
+    bool rb_head(const RbArgs& B, uint32_t d) {
+        par(B.n_topics, [&](size_t r) { rb_head_one(B, (uint32_t)r, d); });
+        return true;
+    }
+    bool rb_root(const RbArgs& B, const uint32_t* S1) {
+        par(B.n_tenants, [&](size_t t) { rb_root_one(B, (uint32_t)t, S1); });
+        return true;
+    }
+    bool rb_emit(const RbArgs& B, uint32_t d, const uint32_t* Sp, const uint32_t* Sc, const uint32_t* Sn) {
+        par(B.n_topics, [&](size_t r) { rb_emit_one(B, (uint32_t)r, d, Sp, Sc, Sn); });
+        return true;
+    }
+    bool rb_close(const RbArgs& B, uint32_t d, const uint32_t* Sc, const uint32_t* Sn) {
+        par(B.n_topics, [&](size_t r) { rb_close_one(B, (uint32_t)r, d, Sc, Sn); });
+        return true;
+    }
+    bool rb_advance(const RbArgs& B, const uint32_t* Sc) {
+        par(B.n_tenants, [&](size_t t) { rb_advance_one(B, (uint32_t)t, Sc); });
         return true;
     }
     bool r_find_tenant(const RetainMut& m, const uint8_t* name, uint32_t len, uint32_t* out) {

@@ -5,6 +5,18 @@ template <class F> static auto with_retain(bmq_engine* e, F&& f) { return e->drt
 
 int upload_retain(bmq_engine* e) {
     RetainIndexHost& h = e->rhost;
+    if (e->rb_serving) { // built by the executor builder (bmq_retain_build.h): the arrays lie where the walk reads them already, rhost is the catalogue
+        if (e->device < 0) {
+            e->hrb->view(e->rhview);
+            if (!e->hrt->reset(e->rhview, h)) return set_err(e, BMQ_E_NOMEM, e->hrt->error);
+            return BMQ_OK;
+        }
+        HIPCHK(e, hipSetDevice(e->device));
+        e->drb->view(e->rdev.view);
+        for (DevBuf* b : {&e->rdev.nodes, &e->rdev.edges, &e->rdev.posts, &e->rdev.gps, &e->rdev.tenants, &e->rdev.dict, &e->rdev.pool}) b->release(); // (a host-built generation's)
+        if (!e->drt->reset(e->rdev.view, h)) return set_err(e, e->dx.err.empty() ? BMQ_E_NOMEM : BMQ_E_HIP, e->drt->error);
+        return BMQ_OK;
+    }
     if (e->device < 0) { // host-only engine: the bulk-loaded arrays stay where the host builder keeps them
         RetainIndexView& v = e->rhview;
         v = RetainIndexView{};
@@ -20,6 +32,7 @@ int upload_retain(bmq_engine* e) {
         h.full_upload = h.dict_changed = false;
         h.dirty.clear();
         if (!e->hrt->reset(v, h)) return set_err(e, BMQ_E_NOMEM, e->hrt->error);
+        if (e->hrb) e->hrb->release_image(); // (an executor-built generation's)
         return BMQ_OK;
     }
     HIPCHK(e, hipSetDevice(e->device));
@@ -49,7 +62,91 @@ int upload_retain(bmq_engine* e) {
     d.view.pool = d.pool.as<uint8_t>();
     // the mutable part starts over: every bulk-loaded id live, no overlay topics (bmq_retain_dyn.h)
     if (!e->drt->reset(d.view, h)) return set_err(e, e->dx.err.empty() ? BMQ_E_NOMEM : BMQ_E_HIP, e->drt->error);
+    if (e->drb) e->drb->release_image(); // (an executor-built generation's)
     return BMQ_OK;
+}
+
+
+// ---- who bulk-loads (bmq_config.retain_builder) -------------------------------------------------------------------------------------------
+int retain_publish(bmq_engine* e);
+// what bmq_retain_build_info_get tells of a generation the HOST builder built
+RetainBuildInfo host_build_info(const RetainIndexHost& h, uint64_t n_items, float ms, uint32_t fallback) {
+    RetainBuildInfo b;
+    b.builder = 0;
+    b.fallback = fallback;
+    b.n_items = n_items;
+    b.n_topics = h.n_topics;
+    b.n_tenants = h.order.size();
+    for (const RTenantState* t : h.order) {
+        b.n_nodes += t->nodes.size();
+        b.n_posts += t->posts.size();
+        for (const RGp& g : t->gps) b.n_gp_runs += g.gp != NONE;
+        for (const std::string& p : t->topics) b.max_depth = std::max<uint32_t>(b.max_depth, 1u + (uint32_t)std::count(p.begin(), p.end(), '/'));
+    }
+    b.n_edges = b.n_nodes - b.n_tenants;
+    b.n_tokens = h.dict_h.entries.size();
+    b.ms_total = ms;
+    return b;
+}
+
+int retain_load_host(bmq_engine* e, std::vector<RetainIndexHost::Item>&& items, uint32_t fallback) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t n_items = items.size();
+    if (!e->rhost.rebuild(std::move(items))) return set_err(e, BMQ_E_INVAL, e->rhost.error);
+    e->rb_serving = false;
+    const int rc = retain_publish(e); // (ends in a synchronise)
+    e->rbinfo = host_build_info(e->rhost, n_items, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(), fallback);
+    return rc;
+}
+
+// the executor builder over the caller's packed items; *too_deep: it declined (a topic of more than RB_MAX_DEPTH levels), nothing was changed
+int retain_load_exec(bmq_engine* e, const RbInput& in, bool* too_deep) {
+    *too_deep = false;
+    if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
+    const bool ok = e->drb ? e->drb->build(in) : e->hrb->build(in);
+    if (!ok) {
+        if (e->drb ? e->drb->too_deep : e->hrb->too_deep) {
+            *too_deep = true;
+            return BMQ_OK;
+        }
+        const std::string& msg = e->drb ? e->drb->error : e->hrb->error;
+        return set_err(e, msg.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : (msg.find("too many") != std::string::npos ? BMQ_E_INVAL : BMQ_E_HIP), msg);
+    }
+    if (e->drb) retain_catalogue(e->rhost, in, *e->drb);
+    else retain_catalogue(e->rhost, in, *e->hrb);
+    e->rb_serving = true;
+    const int rc = retain_publish(e);
+    e->rbinfo = e->drb ? e->drb->info : e->hrb->info;
+    return rc;
+}
+
+// a bulk load of host strings (bmq_retain_compact, bmq_retain_import into an empty engine) with the configured builder
+int retain_load_items(bmq_engine* e, std::vector<RetainIndexHost::Item>&& items) {
+    if (!e->drb && !e->hrb) return retain_load_host(e, std::move(items), 0);
+    std::vector<uint8_t> tb, pb;
+    std::vector<uint32_t> toff{0}, poff{0}, it_tenant, ex;
+    std::vector<uint64_t> ts;
+    std::unordered_map<std::string, uint32_t> tix;
+    for (const auto& it : items) {
+        auto f = tix.find(it.tenant);
+        if (f == tix.end()) {
+            f = tix.emplace(it.tenant, (uint32_t)tix.size()).first;
+            tb.insert(tb.end(), it.tenant.begin(), it.tenant.end());
+            toff.push_back((uint32_t)tb.size());
+        }
+        it_tenant.push_back(f->second);
+        pb.insert(pb.end(), it.topic.begin(), it.topic.end());
+        if (pb.size() >= 0xFFFFFFF0ull) return set_err(e, BMQ_E_RANGE, "the topics of the load exceed 4 GiB");
+        poff.push_back((uint32_t)pb.size());
+        ts.push_back(it.has_ts ? it.ts : 0ull);
+        ex.push_back(it.has_ts ? it.expiry : 0xFFFFFFFFu);
+    }
+    tb.resize(tb.size() + 16, 0), pb.resize(pb.size() + 16, 0);
+    const RbInput in{tb.data(), toff.data(), (uint32_t)tix.size(), it_tenant.data(), pb.data(), poff.data(), (uint32_t)items.size(), ts.data(), ex.data()};
+    bool too_deep = false;
+    const int rc = retain_load_exec(e, in, &too_deep);
+    if (!too_deep) return rc;
+    return retain_load_host(e, std::move(items), 1);
 }
 
 // a bulk load (rebuild / compact) has produced a new RetainIndexHost: a new generation of topic ids
@@ -298,11 +395,22 @@ int bmq_retain_rebuild_ex(bmq_engine* e, const uint8_t* tenants, const uint32_t*
     if (!e || (n_topics && (!tenants || !tenant_off || !topic_tenant || !topics || !topic_off))) return BMQ_E_INVAL;
     if ((timestamp_hlc == nullptr) != (expiry_seconds == nullptr)) return set_err(e, BMQ_E_INVAL, "timestamps and expiry intervals come together");
     std::lock_guard<std::mutex> g(e->mu);
+    for (uint32_t i = 0; i < n_topics; i++)
+        if (topic_tenant[i] >= n_tenants) return set_err(e, BMQ_E_INVAL, "topic_tenant index out of range");
+    if (e->cur->pending) return set_err(e, BMQ_E_STATE, "a batch is in flight: call bmq_match_finish first");
+    if (e->rcmp.active) return set_err(e, BMQ_E_STATE, "a retain compaction is running: bmq_retain_compact_swap or bmq_retain_compact_abort first");
+    uint32_t fallback = 0;
+    if (e->drb || e->hrb) { // bmq_config.retain_builder = 1: the caller's packed items go to the executor as they are
+        const RbInput in{tenants, tenant_off, n_tenants, topic_tenant, topics, topic_off, n_topics, timestamp_hlc, expiry_seconds};
+        bool too_deep = false;
+        const int rc = retain_load_exec(e, in, &too_deep);
+        if (!too_deep) return rc;
+        fallback = 1;
+    }
     std::vector<RetainIndexHost::Item> items;
     items.reserve(n_topics);
     for (uint32_t i = 0; i < n_topics; i++) {
         const uint32_t ti = topic_tenant[i];
-        if (ti >= n_tenants) return set_err(e, BMQ_E_INVAL, "topic_tenant index out of range");
         RetainIndexHost::Item it;
         it.tenant.assign((const char*)tenants + tenant_off[ti], tenant_off[ti + 1] - tenant_off[ti]);
         it.topic.assign((const char*)topics + topic_off[i], topic_off[i + 1] - topic_off[i]);
@@ -313,10 +421,7 @@ int bmq_retain_rebuild_ex(bmq_engine* e, const uint8_t* tenants, const uint32_t*
         }
         items.push_back(std::move(it));
     }
-    if (e->cur->pending) return set_err(e, BMQ_E_STATE, "a batch is in flight: call bmq_match_finish first");
-    if (e->rcmp.active) return set_err(e, BMQ_E_STATE, "a retain compaction is running: bmq_retain_compact_swap or bmq_retain_compact_abort first");
-    if (!e->rhost.rebuild(std::move(items))) return set_err(e, BMQ_E_INVAL, e->rhost.error);
-    return retain_publish(e);
+    return retain_load_host(e, std::move(items), fallback);
 }
 
 int bmq_retain_rebuild(bmq_engine* e, const uint8_t* tenants, const uint32_t* tenant_off, uint32_t n_tenants,
@@ -342,8 +447,7 @@ static int retain_apply_common(bmq_engine* e, const uint8_t* tenants, const uint
     }
     if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
     if (!e->rbuilt) { // the first retained message of a fresh range: start from an empty bulk load
-        if (!e->rhost.rebuild({})) return set_err(e, BMQ_E_INVAL, e->rhost.error);
-        const int rc = retain_publish(e);
+        const int rc = retain_load_host(e, {}, 0); // (nothing to build: the host builder, whatever bmq_config.retain_builder says)
         if (rc) return rc;
     }
     const bool ok = with_retain(e, [&](auto& rt) {
@@ -429,6 +533,33 @@ int bmq_retain_info_get(const bmq_engine* ce, bmq_retain_info* out) {
     out->added_ids = in.overlay_ids;
     out->overlay_nodes = in.overlay_nodes;
     out->n_tenants = e->rhost.n_tenants();
+    return BMQ_OK;
+}
+
+int bmq_retain_build_info_get(const bmq_engine* ce, bmq_retain_build_info* out) {
+    bmq_engine* e = const_cast<bmq_engine*>(ce);
+    std::unique_lock<std::recursive_mutex> api_lock;
+    if (e) api_lock = std::unique_lock<std::recursive_mutex>(e->api);
+    if (!e || !out) return BMQ_E_INVAL;
+    memset(out, 0, sizeof(*out));
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->rbuilt) return set_err(e, BMQ_E_STATE, "no retained-topic index");
+    const RetainBuildInfo& b = e->rbinfo;
+    out->builder = b.builder;
+    out->fallback = b.fallback;
+    out->n_items = b.n_items;
+    out->n_topics = b.n_topics;
+    out->n_tenants = b.n_tenants;
+    out->n_nodes = b.n_nodes;
+    out->n_edges = b.n_edges;
+    out->n_edge_overflows = b.n_edge_overflows;
+    out->n_posts = b.n_posts;
+    out->n_gp_runs = b.n_gp_runs;
+    out->n_tokens = b.n_tokens;
+    out->max_depth = b.max_depth;
+    out->ms_total = b.ms_total;
+    out->ms_sort = b.ms_sort;
+    out->n_gp_overflows = (uint32_t)b.n_gp_overflows;
     return BMQ_OK;
 }
 
@@ -815,12 +946,15 @@ int bmq_retain_compact_build(bmq_engine* e) {
         if (!c.active) return set_err(e, BMQ_E_STATE, "no retain compaction is running");
         if (c.built) return BMQ_OK;
     }
+    const auto t0 = std::chrono::steady_clock::now();
+    c.n_items = c.items.size();
     if (!c.next.rebuild(std::move(c.items))) {
         std::lock_guard<std::mutex> g(e->mu);
         return set_err(e, BMQ_E_INVAL, c.next.error);
     }
     c.items.clear(), c.items.shrink_to_fit();
     std::lock_guard<std::mutex> g(e->mu);
+    c.ms_build = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c.built = true;
     return BMQ_OK;
 }
@@ -840,6 +974,8 @@ int bmq_retain_compact_swap(bmq_engine* e, uint64_t* out_carried, uint64_t* out_
         if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
         if (out_carried) *out_carried = c.next.n_topics;
         e->rhost = std::move(c.next);
+        e->rb_serving = false; // (bmq_retain_compact_build is the host builder's)
+        e->rbinfo = host_build_info(e->rhost, c.n_items, c.ms_build, 0);
         if (int rc = retain_publish(e)) { // upload + the mutable part starts over: a new generation of topic ids
             e->rcmp = bmq_engine::RetainCompaction{};
             return rc;
@@ -939,8 +1075,7 @@ int bmq_retain_compact(bmq_engine* e) {
         items[i].expiry = ex[ids[i]];
         items[i].has_ts = !(items[i].ts == 0 && items[i].expiry == 0xFFFFFFFFu);
     }
-    if (!e->rhost.rebuild(std::move(items))) return set_err(e, BMQ_E_INVAL, e->rhost.error);
-    return retain_publish(e);
+    return retain_load_items(e, std::move(items));
 }
 
 // ---- the retain store's range by KV boundary: RetainStoreCoProc.reset(Boundary) without the KV scan --------------------------------------
@@ -1014,8 +1149,7 @@ int bmq_retain_import(bmq_engine* dst, bmq_engine* src, uint8_t flags, const uin
         std::lock_guard<std::mutex> g(dst->mu);
         if (dst->device >= 0) HIPCHK(dst, hipSetDevice(dst->device));
         const uint64_t n = items.size();
-        if (!dst->rhost.rebuild(std::move(items))) return set_err(dst, BMQ_E_INVAL, dst->rhost.error);
-        if (int rc = retain_publish(dst)) return rc;
+        if (int rc = retain_load_items(dst, std::move(items))) return rc;
         if (out_imported) *out_imported = n;
         return BMQ_OK;
     }

@@ -185,7 +185,7 @@ class Engine:
 
     def __init__(self, device: int = 0, wave_queue_cap: int = 0, wave_pair_cap: int = 0, slow_scratch_mb: int = 0, kernel_timing: bool = False,
                  dedup_min_topics: int = 0, dedup_sorted: bool = False, region_slack: int = 0,
-                 tail_records: int = 0, child_filters: int = 0):
+                 tail_records: int = 0, child_filters: int = 0, retain_builder: int = 0):
         L = _lib.lib()
         cfg = _lib.Config()
         cfg.struct_size = C.sizeof(_lib.Config)
@@ -199,6 +199,7 @@ class Engine:
         cfg.region_slack = region_slack  # 0: default (6: trie regions at load factor 0.2); 1: 0.4 (less memory, more second probes)
         cfg.tail_records = tail_records  # 0: default (tail records on); 1: off
         cfg.child_filters = child_filters  # 0: default (the walk reads the nodes' child filter words); 1: it ignores them
+        cfg.retain_builder = retain_builder  # 0: default (the host builder bulk-loads the retained-topic index); 1: the executor builder
         h = C.c_void_p()
         rc = L.bmq_engine_create(C.byref(cfg), C.byref(h))
         if rc:
@@ -768,6 +769,12 @@ class Engine:
     def retain_info(self) -> "_lib.RetainInfo":
         st = _lib.RetainInfo()
         self._check(_lib.lib().bmq_retain_info_get(self.h, C.byref(st)))
+        return st
+
+    def retain_build_info(self) -> "_lib.RetainBuildInfo":
+        """the bulk load behind the serving generation of the retained-topic index: which builder ran, what it built, how long it took"""
+        st = _lib.RetainBuildInfo()
+        self._check(_lib.lib().bmq_retain_build_info_get(self.h, C.byref(st)))
         return st
 
     def retain_live_ids(self, tenant=None) -> List[int]:

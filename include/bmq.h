@@ -92,7 +92,13 @@ typedef struct bmq_config {
                                /* empty route ranges, 32 more filter bits over its literal children that the index builder maintains --      */
                                /* before it probes for a literal child: fewer probes for children that do not exist.  1 = the walk ignores    */
                                /* the words (the builder keeps them all the same).  Results are the same either way    */
-    uint32_t reserved[2];
+    uint32_t retain_builder;   /* who BULK-LOADS the retained-topic index (bmq_retain_rebuild*, bmq_retain_compact, bmq_retain_import into an empty   */
+                               /* engine): 0 = default = the host builder (host threads, parallel over tenants; the image is uploaded); 1 = the      */
+                               /* executor builder (bmq_retain_build_core.h): sorts, scans and CAS inserts as gfx950 kernels on a device engine, the  */
+                               /* same functions on host threads on a device = -1 engine; the arrays are built where the walk reads them.  Topic ids, */
+                               /* results and every other call are the same either way; bmq_retain_build_info_get says which one built the serving    */
+                               /* generation.  Any other value: BMQ_E_INVAL                                                                          */
+    uint32_t reserved[1];
 } bmq_config;
 
 /* Counters of the last completed match batch (for roofline accounting). */
@@ -849,7 +855,10 @@ int bmq_retain_compact(bmq_engine* e);
  *                              *out_carried = topics of the new bulk load, *out_replayed = logged ops replayed.  BMQ_E_NOSPACE: the log outgrew
  *                              1 GiB (abort and begin again; no mutation is ever refused).
  *   bmq_retain_compact_abort   drops the half-built generation.
- * One compaction call at a time; bmq_retain_rebuild* / bmq_retain_compact are refused (BMQ_E_STATE) between begin and swap / abort. */
+ * One compaction call at a time; bmq_retain_rebuild* / bmq_retain_compact are refused (BMQ_E_STATE) between begin and swap / abort.
+ * bmq_retain_compact_build always runs the HOST builder, whatever bmq_config.retain_builder says: the snapshot it loads is host strings and
+ * the serving generation owns the executor's buffers.  (A device-side snapshot and a second buffer set are what the executor builder makes
+ * possible next.) */
 int bmq_retain_compact_begin(bmq_engine* e);
 int bmq_retain_compact_build(bmq_engine* e);
 int bmq_retain_compact_swap(bmq_engine* e, uint64_t* out_carried /* may be NULL */, uint64_t* out_replayed /* may be NULL */);
@@ -877,7 +886,8 @@ int bmq_retain_compact_abort(bmq_engine* e);
  *                                and '#', a new generation; *out_imported = topics.  Otherwise chunks of at most 65 536 add ops go through the
  *                                ordinary apply path (a compaction running on dst logs them): a topic dst holds already has its stamps
  *                                replaced and counts in *out_replaced, the others in *out_imported.  dst == src: BMQ_E_INVAL.  Host-only and
- *                                device engines may be paired, and two devices (the strings cross the host: the bulk builder is a host builder).
+ *                                device engines may be paired, and two devices (the strings cross the host; dst bulk-loads with the builder its
+ *                                bmq_config.retain_builder names).
  * A split of range A at key s:  bmq_retain_import(B, A, start = s)  then  bmq_retain_compact_begin_in(A, end = s), _build, _swap.
  * A merge of B into A:          bmq_retain_import(A, B, flags = 0). */
 int bmq_retain_count_in(const bmq_engine* e, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len,
@@ -899,6 +909,26 @@ typedef struct bmq_retain_info {
     uint64_t generation;      /* +1 per bulk load (rebuild / compact): ids of different generations are unrelated */
 } bmq_retain_info;
 int bmq_retain_info_get(const bmq_engine* e, bmq_retain_info* out);
+/* The BULK LOAD behind the serving generation (bmq_retain_rebuild*, bmq_retain_compact, bmq_retain_compact_swap, bmq_retain_import into an
+ * empty engine, the empty load the first bmq_retain_apply* of a fresh engine starts from).  BMQ_E_STATE: nothing is loaded. */
+typedef struct bmq_retain_build_info {
+    uint32_t builder;          /* 0 = the host builder, 1 = the executor builder (bmq_config.retain_builder) built this generation           */
+    uint32_t fallback;         /* 0, or why a retain_builder = 1 engine ran the host builder: 1 = a topic of more than 128 levels            */
+    uint64_t n_items;          /* items handed in ...                                                                                       */
+    uint64_t n_topics;         /* ... distinct (tenant, topic) pairs among them = topic ids of the load                                      */
+    uint64_t n_tenants;
+    uint64_t n_nodes;          /* trie nodes, the tenants' roots included                                                                    */
+    uint64_t n_edges;          /* entries in use of the edge regions (= nodes - tenants)                                                     */
+    uint64_t n_edge_overflows; /* edges that lie behind their home bucket (counted by the executor builder; the host builder reports 0)       */
+    uint64_t n_posts;          /* grandchild postings                                                                                        */
+    uint64_t n_gp_runs;        /* (grandparent, token) runs of them = entries in use of the RGp tables                                       */
+    uint64_t n_tokens;         /* distinct level strings and tenant ids in the dictionary                                                    */
+    uint32_t max_depth;        /* levels of the deepest topic                                                                                */
+    float ms_total;            /* host clock around the build, the last synchronise included (without the snapshot of bmq_retain_compact)    */
+    float ms_sort;             /* ... of which the ordering of the items (executor builder; 0 for the host builder)                          */
+    uint32_t n_gp_overflows;   /* RGp runs that lie behind their home bucket (executor builder; 0 for the host builder)                       */
+} bmq_retain_build_info;
+int bmq_retain_build_info_get(const bmq_engine* e, bmq_retain_build_info* out);
 /* id -> the topic the id denotes in this generation (whether or not it is retained right now: bmq_retain_topic_info tells): out
  * receives the tenant id followed by the topic (no separator), *out_tenant_len bytes of tenant, *out_len bytes in total.
  * bmq_retain_topics: many ids at once (bulk-loaded ids from the host's copy of the load, added ones with ONE device gather):
