@@ -21,7 +21,7 @@ ABI_SYMBOLS = [
     "bmq_match_finish", "bmq_set_kernel_timing", "bmq_match_submit", "bmq_match_wait", "bmq_match_submit_fmt", "bmq_match_submit_dev", "bmq_match_wait_dev", "bmq_match_wait_counts", "bmq_match_wait_ranges", "bmq_match_wait_grouped", "bmq_host_alloc", "bmq_host_free", "bmq_sync", "bmq_stats_get", "bmq_stream", "bmq_match_all", "bmq_route_key_encode",
     "bmq_route_key_decode", "bmq_java_string_hash", "bmq_range_lookup", "bmq_comm_unique_id", "bmq_comm_init", "bmq_comm_destroy", "bmq_exchange_fanout",
     "bmq_exchange_csr", "bmq_exchange_wait", "bmq_partition_batch_dev", "bmq_retain_message_key", "bmq_retain_filter_route", "bmq_retain_rebuild", "bmq_retain_rebuild_ex", "bmq_retain_apply", "bmq_retain_apply_ex", "bmq_retain_topic",
-    "bmq_retain_topic_info", "bmq_retain_find_all", "bmq_retain_expired", "bmq_retain_apply_batch", "bmq_retain_compact", "bmq_retain_compact_begin", "bmq_retain_compact_build", "bmq_retain_compact_swap", "bmq_retain_compact_abort", "bmq_retain_info_get", "bmq_retain_build_info_get",
+    "bmq_retain_topic_info", "bmq_retain_find_all", "bmq_retain_expired", "bmq_retain_apply_batch", "bmq_retain_compact", "bmq_retain_compact_begin", "bmq_retain_compact_build", "bmq_retain_compact_swap", "bmq_retain_compact_abort", "bmq_retain_compact_info_get", "bmq_retain_info_get", "bmq_retain_build_info_get",
     "bmq_retain_live_ids", "bmq_retain_topics", "bmq_retain_tenant_counts", "bmq_retain_message_keys", "bmq_retain_remove_ids", "bmq_retain_keys_prepare", "bmq_retain_keys_by_id", "bmq_retain_keys_match",
     "bmq_retain_count_in", "bmq_retain_ids_in", "bmq_retain_compact_begin_in", "bmq_retain_import",
     "bmq_retain_match_batch", "bmq_retain_match_batch_dev", "bmq_retain_match_limited", "bmq_batcher_create", "bmq_batcher_destroy",
@@ -102,6 +102,12 @@ class RetainBuildInfo(C.Structure):
                 ("n_tokens", C.c_uint64), ("max_depth", C.c_uint32), ("ms_total", C.c_float), ("ms_sort", C.c_float), ("n_gp_overflows", C.c_uint32)]
 
 
+class RetainCompactInfo(C.Structure):
+    _fields_ = [("state", C.c_uint32), ("builder", C.c_uint32), ("fallback", C.c_uint32), ("reserved0", C.c_uint32), ("n_items", C.c_uint64),
+                ("snapshot_bytes", C.c_uint64), ("replayed", C.c_uint64), ("locked_copy_bytes", C.c_uint64), ("begin_ms", C.c_float), ("build_ms", C.c_float),
+                ("swap_ms", C.c_float), ("reserved1", C.c_uint32)]
+
+
 class ShareInfo(C.Structure):
     _fields_ = [("n_tables", C.c_uint64), ("n_members", C.c_uint64), ("n_deliverers", C.c_uint64), ("device_bytes", C.c_uint64),
                 ("generation", C.c_uint64), ("ms_count", C.c_float), ("ms_rows", C.c_float), ("ms_resolve", C.c_float), ("ms_sort", C.c_float),
@@ -149,6 +155,7 @@ def lib() -> C.CDLL:
             "bmq_retain_compact_build": (C.c_int, [vp]),
             "bmq_retain_compact_swap": (C.c_int, [vp, P(u64), P(u64)]),
             "bmq_retain_compact_abort": (C.c_int, [vp]),
+            "bmq_retain_compact_info_get": (C.c_int, [vp, P(RetainCompactInfo)]),
             "bmq_compact_begin": (C.c_int, [vp]),
             "bmq_compact_begin_in": (C.c_int, [vp, C.c_uint8, C.c_char_p, u32, C.c_char_p, u32]),
             "bmq_routes_count_in": (C.c_int, [vp, C.c_uint8, C.c_char_p, u32, C.c_char_p, u32, P(u64), P(u64)]),

@@ -181,14 +181,15 @@ struct bmq_engine {
     // bmq_config.retain_builder = 1: the bulk load runs on the executor (bmq_retain_build.h) and the serving generation's arrays lie in its buffers
     std::unique_ptr<RetainBuild<DevExec>> drb;
     std::unique_ptr<RetainBuild<HostExec>> hrb;
+    bool rb_generation = false;   // bmq_config.retain_builder = 3: bmq_retain_compact_begin[_in] / _build / _swap run there too (under 1 they stay the host builder's)
     bool rb_serving = false;      // the serving generation was built there (rhost holds the catalogue only, its image vectors are empty)
     RetainBuildInfo rbinfo{};     // the serving generation's bulk load (bmq_retain_build_info_get)
     // bmq_retain_compact_begin / _build / _swap: the next generation of the retained-topic index, built beside the serving one (round 6)
     struct RetainCompaction {
-        bool active = false;  // (guarded by mu, like the log; `next` and `items` belong to the one thread that drives the compaction)
+        bool active = false;  // (guarded by mu, like the log and `ci`; `next`, `items` and the exec-resident parts belong to the one thread that drives the compaction)
         bool built = false;
-        std::vector<RetainIndexHost::Item> items; // the live topics at begin, with their stamps
-        RetainIndexHost next;                     // ... loaded into an index of their own, outside the engine lock
+        std::vector<RetainIndexHost::Item> items; // the live topics at begin, with their stamps (retain_builder = 0 or 1)
+        RetainIndexHost next;                     // ... loaded into an index of their own, outside the engine lock (retain_builder = 3: the next catalogue)
         struct Op {
             std::string tenant, topic;
             uint8_t op;
@@ -202,7 +203,23 @@ struct bmq_engine {
         bool log_overflow = false;
         uint64_t n_items = 0; // what bmq_retain_build_info tells of the generation once it serves
         float ms_build = 0;
+        // bmq_config.retain_builder = 3: the snapshot stays in exec memory and the next generation is built there, on an executor of its own
+        // (rbx on the build stream / rhx), outside the engine lock -- image, key store and mutable part ready for the swap to take over
+        std::unique_ptr<RetainSnapshot<DevExec>> dsnap;
+        std::unique_ptr<RetainSnapshot<HostExec>> hsnap;
+        std::unique_ptr<RetainBuild<DevExec>> ndrb;
+        std::unique_ptr<RetainBuild<HostExec>> nhrb;
+        std::unique_ptr<RetainDyn<DevExec>> ndrt;
+        std::unique_ptr<RetainDyn<HostExec>> nhrt;
+        bool exec_snapshot = false; // begin took the snapshot in exec memory (`items` stays empty)
+        bool exec_built = false;    // build left the next generation in exec memory (false after a fallback: `next` holds a host-built one)
+        uint32_t fallback = 0;
+        bmq_retain_compact_info ci{}; // bmq_retain_compact_info_get of this compaction
     } rcmp;
+    bmq_retain_compact_info rcinfo{}; // ... of the last compaction that ended in a swap
+    DevExec rbx;                      // the executor the next retain generation is built on (stream: s_build)
+    HostExec rhx;                     // ... of a host-only engine
+    uint64_t r_up_bytes = 0;          // bytes upload_retain has copied to the device so far (bmq_retain_compact_info.locked_copy_bytes)
     uint64_t repoch = 0;      // +1 per retain rebuild / apply / compact
     uint64_t rgeneration = 0; // +1 per retain rebuild / compact: topic ids of different generations are unrelated
     RetainLimit rlim;
@@ -1020,13 +1037,14 @@ int bmq_engine_create(const bmq_config* cfg, bmq_engine** out) {
     if (const char* v = bmq_env("BMQ_QCAP")) c.wave_queue_cap = (uint32_t)atoi(v); // profiling experiments
     if (const char* v = bmq_env("BMQ_PCAP")) c.wave_pair_cap = (uint32_t)atoi(v);
     if ((c.wave_queue_cap != 0 && c.wave_queue_cap != 128) || (c.wave_pair_cap != 0 && c.wave_pair_cap != 128)) return BMQ_E_INVAL;
-    if (c.region_slack > 64 || c.tail_records > 1 || c.child_filters > 1 || c.retain_builder > 1) return BMQ_E_INVAL;
+    if (c.region_slack > 64 || c.tail_records > 1 || c.child_filters > 1 || c.retain_builder > 3 || c.retain_builder == 2) return BMQ_E_INVAL;
     const bool smallest = c.wave_queue_cap == 128 || c.wave_pair_cap == 128;
     c.wave_queue_cap = smallest ? WALK_QC_SMALLEST : WALK_QC_DEFAULT; // (what bmq_config reports back / BatchArgs carries: the geometry in use)
     c.wave_pair_cap = smallest ? WALK_PC_SMALLEST : WALK_PC_DEFAULT;
     auto e = std::make_unique<bmq_engine>();
     e->cfg = c;
     e->device = c.device;
+    e->rb_generation = c.retain_builder == 3;
     e->walk_geom = smallest ? 2 : 0;
     if (c.dedup_min_topics) e->dedup_min = c.dedup_min_topics;
     if (const char* v = bmq_env("BMQ_DEDUP_MIN")) e->dedup_min = (uint32_t)strtoul(v, nullptr, 10); // profiling experiments (4294967295: never)
@@ -1058,7 +1076,7 @@ int bmq_engine_create(const bmq_config* cfg, bmq_engine** out) {
             if (hipHostMalloc((void**)&sl.h_fsums, 4 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) return BMQ_E_NOMEM;
             memset(sl.h_fsums, 0, 4 * sizeof(unsigned long long));
         }
-        e->dx.device = e->dxi[0].device = e->dxi[1].device = c.device;
+        e->dx.device = e->dxi[0].device = e->dxi[1].device = e->rbx.device = c.device;
         e->dx.stream = e->dxi[0].stream = e->stream;
         e->dix = std::make_unique<DistIndex<DevExec>>(e->dxi[0]);
         if (c.region_slack) e->dix->slack_num = c.region_slack;
@@ -1111,6 +1129,9 @@ void bmq_engine_destroy(bmq_engine* e) {
         if (e->s_side) (void)hipStreamDestroy(e->s_side);
         if (e->s_build) (void)hipStreamSynchronize(e->s_build);
         e->cmp = bmq_engine::Compaction{}; // (a generation left half-built)
+        e->rcmp = bmq_engine::RetainCompaction{}; // (its buffers go through rbx: while the device is still this thread's)
+        e->rbx.release(e->rbx.tmp);
+        e->rbx.tmp = nullptr;
         if (e->s_build) (void)hipStreamDestroy(e->s_build);
         if (e->ev_serving) (void)hipEventDestroy(e->ev_serving);
         if (e->ev_lend) (void)hipEventDestroy(e->ev_lend);
@@ -1126,6 +1147,7 @@ void bmq_engine_destroy(bmq_engine* e) {
         if (e->stream) (void)hipStreamDestroy(e->stream);
     }
     e->hfo.reset(); // (before the index it refers to)
+    e->rcmp = bmq_engine::RetainCompaction{}; // (a host-only engine's half-built retain generation: before the executor it refers to)
     delete e;
 }
 

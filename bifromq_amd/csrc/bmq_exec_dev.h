@@ -18,6 +18,7 @@
 #include "bmq_fanout_kernels.h"
 #include "bmq_retain_build_kernels.h"
 #include "bmq_retain_core.h"
+#include "bmq_retain_snap_kernels.h"
 #include "bmq_share_kernels.h"
 
 namespace bmq {
@@ -799,6 +800,57 @@ struct DevExec {
     }
     bool r_key_write(const RetainMut& m, const RetainKeyStore& ks, const uint32_t* ids, uint32_t n, const unsigned long long* offs, uint8_t* out) {
         hipLaunchKernelGGL(k_r_key_write, grid(n, 256), dim3(256), 0, stream, m, ks, ids, n, offs, out);
+        return launched();
+    }
+    // ---- snapshot of the retained-topic index and the next generation's per-id arrays (bmq_retain_snap_kernels.h) ----
+    bool rs_lens(const RetainMut& m, const RetainKeyStore& ks, const RsArgs& A) { // A.totals[0] += topic bytes, [1] += bulk-loaded ids
+        if (A.S.n == 0) return true;
+        hipLaunchKernelGGL(k_rs_lens, grid(A.S.n, RSK), dim3(RSK), 0, stream, m, ks, A);
+        return launched();
+    }
+    bool rs_tenant_lens(const RetainMut& m, const RsArgs& A) {
+        if (A.ov_nodes == 0) return true;
+        hipLaunchKernelGGL(k_rs_tenant_lens, grid(A.ov_nodes, RSK), dim3(RSK), 0, stream, m, A);
+        return launched();
+    }
+    bool rs_totals(const RsArgs& A) {
+        hipLaunchKernelGGL(k_rs_totals, dim3(1), dim3(64), 0, stream, A);
+        return launched();
+    }
+    bool rs_tenants(const RetainMut& m, const RsArgs& A) {
+        if (A.ov_nodes == 0) return true;
+        hipLaunchKernelGGL(k_rs_tenants, grid(A.ov_nodes, RSK), dim3(RSK), 0, stream, m, A);
+        return launched();
+    }
+    bool rs_items(const RetainMut& m, const RsArgs& A) { // the overlay items [A.n_bulk, A.S.n)
+        if (A.S.n <= A.n_bulk) return true;
+        hipLaunchKernelGGL(k_rs_items, grid(A.S.n - A.n_bulk, 64), dim3(64), 0, stream, m, A);
+        return launched();
+    }
+    template <class SO> bool rs_gather(const RsGather<SO>& G) {
+        if (G.n == 0 || G.bytes == 0) return true;
+        const unsigned long long waves = (G.bytes + RS_WAVE_BYTES - 1) / RS_WAVE_BYTES;
+        hipLaunchKernelGGL(k_rs_gather<SO>, grid(waves, RSK / 64), dim3(RSK), 0, stream, G);
+        return launched();
+    }
+    bool rs_used(const uint32_t* item_tenant, uint32_t n, uint32_t* used) {
+        if (n == 0) return true;
+        hipLaunchKernelGGL(k_rs_used, grid(n, RSK), dim3(RSK), 0, stream, item_tenant, used, n);
+        return launched();
+    }
+    bool rs_remap(const uint32_t* item_tenant, const uint32_t* rank_of, uint32_t* out, uint32_t n) {
+        if (n == 0) return true;
+        hipLaunchKernelGGL(k_rs_remap, grid(n, RSK), dim3(RSK), 0, stream, item_tenant, rank_of, out, n);
+        return launched();
+    }
+    bool rs_perm_lens(const RsNext& N) {
+        if (N.n_topics == 0) return true;
+        hipLaunchKernelGGL(k_rs_perm_lens, grid(N.n_topics, RSK), dim3(RSK), 0, stream, N);
+        return launched();
+    }
+    bool rs_next(const RsNext& N) {
+        if (N.n_topics == 0) return true;
+        hipLaunchKernelGGL(k_rs_next, grid(N.n_topics, RSK), dim3(RSK), 0, stream, N);
         return launched();
     }
 #undef BMQ_X

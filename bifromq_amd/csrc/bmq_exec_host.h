@@ -16,6 +16,7 @@
 #include "bmq_fanout_core.h"
 #include "bmq_retain_build_core.h"
 #include "bmq_retain_core.h"
+#include "bmq_retain_snap_core.h"
 #include "bmq_share_core.h"
 
 namespace bmq {
@@ -461,6 +462,55 @@ struct HostExec {
         lv.start = 0;
         scan_level_bytes<0u>(name, pos, len, lv.h, lv.inl, lv.len);
         out[0] = ov_find(m.onodes, m.oedges, m.oedge_mask, m.opool, 0u, lv.h.h1, lv.h.h2, lv.len, name, 0);
+        return true;
+    }
+    // ---- snapshot of the retained-topic index and the next generation's per-id arrays (bmq_retain_snap_core.h) ----
+    bool rs_lens(const RetainMut& m, const RetainKeyStore& ks, const RsArgs& A) { // A.totals[0] += topic bytes, [1] += bulk-loaded ids
+        std::atomic<unsigned long long> bytes{0}, n_bulk{0};
+        par(A.S.n, [&](size_t i) {
+            bool bulk = false;
+            bytes.fetch_add(rs_len_one(m, ks, A, (uint32_t)i, &bulk), std::memory_order_relaxed);
+            if (bulk) n_bulk.fetch_add(1, std::memory_order_relaxed);
+        });
+        A.totals[0] += bytes.load();
+        A.totals[1] += n_bulk.load();
+        return true;
+    }
+    bool rs_tenant_lens(const RetainMut& m, const RsArgs& A) {
+        par(A.ov_nodes, [&](size_t i) { rs_tenant_len_one(m, A, (uint32_t)i); });
+        return true;
+    }
+    bool rs_totals(const RsArgs& A) {
+        rs_totals_one(A);
+        return true;
+    }
+    bool rs_tenants(const RetainMut& m, const RsArgs& A) {
+        par(A.ov_nodes, [&](size_t i) { rs_tenant_write_one(m, A, (uint32_t)i); });
+        return true;
+    }
+    bool rs_items(const RetainMut& m, const RsArgs& A) { // the overlay items [A.n_bulk, A.S.n)
+        if (A.S.n > A.n_bulk) par(A.S.n - A.n_bulk, [&](size_t i) { rs_item_write_one(m, A, A.n_bulk + (uint32_t)i); });
+        return true;
+    }
+    template <class SO> bool rs_gather(const RsGather<SO>& G) {
+        if (G.n == 0 || G.bytes == 0) return true;
+        par((size_t)((G.bytes + 15) / 16), [&](size_t c) { rs_gather_chunk(G, c, 0u, G.n); });
+        return true;
+    }
+    bool rs_used(const uint32_t* item_tenant, uint32_t n, uint32_t* used) {
+        par(n, [&](size_t i) { rs_used_one(item_tenant, used, (uint32_t)i); });
+        return true;
+    }
+    bool rs_remap(const uint32_t* item_tenant, const uint32_t* rank_of, uint32_t* out, uint32_t n) {
+        par(n, [&](size_t i) { rs_remap_one(item_tenant, rank_of, out, (uint32_t)i); });
+        return true;
+    }
+    bool rs_perm_lens(const RsNext& N) {
+        par(N.n_topics, [&](size_t r) { rs_perm_len_one(N, (uint32_t)r); });
+        return true;
+    }
+    bool rs_next(const RsNext& N) {
+        par(N.n_topics, [&](size_t r) { rs_next_one(N, (uint32_t)r); });
         return true;
     }
 };

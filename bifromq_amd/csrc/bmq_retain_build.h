@@ -16,7 +16,7 @@
 
 namespace bmq {
 
-struct RbInput { // the caller's items (host memory)
+struct RbInput { // the caller's items: host memory, or (in_exec) a snapshot that lies in exec memory already -- the tenant table is host memory always
     const uint8_t* tenants;
     const uint32_t* tenant_off;
     uint32_t n_tenants;
@@ -26,6 +26,8 @@ struct RbInput { // the caller's items (host memory)
     uint32_t n;
     const uint64_t* ts;        // [n] or null: no stamps (ts 0, expiry 0xFFFFFFFF: never expires)
     const uint32_t* expiry;    // [n] or null (together with ts)
+    bool in_exec = false;      // item_tenant, topics (zero-filled 16 bytes past the end) and topic_off are exec memory: used where they lie (ts / expiry are not read)
+    uint64_t topic_bytes = 0;  // in_exec: topic_off[n]
 };
 
 struct RetainBuildInfo {
@@ -43,7 +45,10 @@ struct RbImage { // what RetainIndexView points at
 template <class Exec> class RetainBuild {
 public:
     explicit RetainBuild(Exec& exec) : x(exec) {}
-    ~RetainBuild() { drop(img); }
+    ~RetainBuild() {
+        drop(img);
+        drop_perm();
+    }
     RetainBuild(const RetainBuild&) = delete;
     RetainBuild& operator=(const RetainBuild&) = delete;
 
@@ -57,6 +62,21 @@ public:
     std::vector<uint32_t> perm;     // rank (= topic id) -> input item
     std::vector<uint32_t> t_begin;  // [tenants + 1] first rank of every tenant
     std::vector<RbTenant> plan;
+    // keep_perm: the permutation also stays in exec memory after a build (d_perm[info.n_topics]) until drop_perm / the next build: what lays the
+    // next generation's per-id arrays out in rank order reads it there (RetainDyn::reset_exec)
+    bool keep_perm = false;
+    uint32_t* d_perm = nullptr;
+    void drop_perm() {
+        x.release(d_perm);
+        d_perm = nullptr;
+    }
+    // the image `o` built becomes this one's (exec memory is the executors' common ground: alloc / release do not depend on the instance)
+    void take_image(RetainBuild& o) {
+        drop(img);
+        img = o.img;
+        o.img = RbImage{};
+        info = o.info;
+    }
 
     void view(RetainIndexView& v) const {
         v = RetainIndexView{};
@@ -78,15 +98,18 @@ public:
         const auto t0 = clk::now();
         error.clear();
         too_deep = false;
+        drop_perm();
         Scratch sc{x, {}};
         RbImage ni;
         const bool ok = run(in, sc, ni);
         if (!x.sync()) { // (transient arrays are released behind everything that reads them)
             drop(ni);
+            drop_perm();
             return xfail();
         }
         if (!ok) {
             drop(ni);
+            drop_perm();
             return false;
         }
         drop(img);
@@ -151,10 +174,17 @@ private:
         if ((uint64_t)n >= 0x7FFFFFF0ull) return fail("too many retained topics");
         if (n == 0) return empty_image(ni);
         // ---- the tenant table: small, so the host de-duplicates and byte-sorts it and hands every item its tenant's rank ----
-        std::vector<uint32_t> rank_of(in.n_tenants, NONE), item_rank(n);
+        std::vector<uint32_t> rank_of(in.n_tenants, NONE), item_rank(in.in_exec ? 0 : n);
+        uint32_t* d_rank_of = nullptr; // in_exec: which table entries the items use, then the entries' ranks
         {
-            std::vector<uint8_t> used(in.n_tenants, 0);
-            for (uint32_t i = 0; i < n; i++) used[in.item_tenant[i]] = 1;
+            std::vector<uint32_t> used(in.n_tenants, 0);
+            if (in.in_exec) {
+                d_rank_of = get<uint32_t>(sc, in.n_tenants);
+                if (!d_rank_of) return false;
+                if (!x.zero(d_rank_of, sizeof(uint32_t) * in.n_tenants) || !x.rs_used(in.item_tenant, n, d_rank_of) || !x.copy_out(used.data(), d_rank_of, sizeof(uint32_t) * in.n_tenants))
+                    return xfail();
+            } else
+                for (uint32_t i = 0; i < n; i++) used[in.item_tenant[i]] = 1;
             std::vector<uint32_t> ord;
             for (uint32_t t = 0; t < in.n_tenants; t++)
                 if (used[t]) ord.push_back(t);
@@ -164,7 +194,8 @@ private:
                 if (k == 0 || name(ord[k]) != name(ord[k - 1])) names.emplace_back(name(ord[k]));
                 rank_of[ord[k]] = (uint32_t)names.size() - 1;
             }
-            for (uint32_t i = 0; i < n; i++) item_rank[i] = rank_of[in.item_tenant[i]];
+            if (!in.in_exec)
+                for (uint32_t i = 0; i < n; i++) item_rank[i] = rank_of[in.item_tenant[i]];
         }
         const uint32_t nt = (uint32_t)names.size();
         std::vector<uint8_t> tbytes;
@@ -174,23 +205,25 @@ private:
             toff.push_back((uint32_t)tbytes.size());
         }
         tbytes.resize(tbytes.size() + 16, 0);
-        const size_t topic_bytes = in.topic_off[n];
+        const size_t topic_bytes = in.in_exec ? (size_t)in.topic_bytes : in.topic_off[n];
 
         RbArgs B{};
         uint8_t* d_tenants = get<uint8_t>(sc, tbytes.size());
         uint32_t* d_toff = get<uint32_t>(sc, nt + 1);
-        uint8_t* d_topics = get<uint8_t>(sc, topic_bytes + 16);
-        uint32_t* d_poff = get<uint32_t>(sc, (size_t)n + 1);
+        const uint8_t* d_topics = in.in_exec ? in.topics : get<uint8_t>(sc, topic_bytes + 16);
+        const uint32_t* d_poff = in.in_exec ? in.topic_off : get<uint32_t>(sc, (size_t)n + 1);
         uint32_t* d_item = get<uint32_t>(sc, n);
         B.idx = get<uint32_t>(sc, n);
         B.flag = get<uint32_t>(sc, n);
         B.scan = get<uint32_t>(sc, n);
         B.ctr = get<RbCounters>(sc, 1);
         if (!d_tenants || !d_toff || !d_topics || !d_poff || !d_item || !B.idx || !B.flag || !B.scan || !B.ctr) return false;
-        if (!x.copy_in_async(d_tenants, tbytes.data(), tbytes.size()) || !x.copy_in_async(d_toff, toff.data(), sizeof(uint32_t) * (nt + 1)) ||
-            !x.copy_in_async(d_topics, in.topics, topic_bytes) || !x.zero(d_topics + topic_bytes, 16) ||
-            !x.copy_in_async(d_poff, in.topic_off, sizeof(uint32_t) * ((size_t)n + 1)) || !x.copy_in_async(d_item, item_rank.data(), sizeof(uint32_t) * n) ||
-            !x.zero(B.ctr, sizeof(RbCounters)))
+        if (!x.copy_in_async(d_tenants, tbytes.data(), tbytes.size()) || !x.copy_in_async(d_toff, toff.data(), sizeof(uint32_t) * (nt + 1)) || !x.zero(B.ctr, sizeof(RbCounters)))
+            return xfail();
+        if (in.in_exec) {
+            if (!x.copy_in_async(d_rank_of, rank_of.data(), sizeof(uint32_t) * in.n_tenants) || !x.rs_remap(in.item_tenant, d_rank_of, d_item, n)) return xfail();
+        } else if (!x.copy_in_async((uint8_t*)d_topics, in.topics, topic_bytes) || !x.zero((uint8_t*)d_topics + topic_bytes, 16) ||
+                   !x.copy_in_async((uint32_t*)d_poff, in.topic_off, sizeof(uint32_t) * ((size_t)n + 1)) || !x.copy_in_async(d_item, item_rank.data(), sizeof(uint32_t) * n))
             return xfail();
         B.tenants = d_tenants, B.ten_off = d_toff, B.n_tenants = nt;
         B.topics = d_topics, B.topic_off = d_poff, B.item_tenant = d_item, B.n_items = n;
@@ -203,7 +236,11 @@ private:
         uint32_t n_topics = 0;
         if (!x.rb_keep(B) || !x.scan_flags(B.flag, B.scan, n) || !last_of(B.scan, n, n_topics)) return xfail();
         B.n_topics = n_topics;
-        B.perm = get<uint32_t>(sc, n_topics);
+        if (keep_perm) {
+            d_perm = (uint32_t*)x.alloc(sizeof(uint32_t) * std::max<size_t>(n_topics, 1) + 16);
+            if (!d_perm) error = "out of memory (retain bulk load)";
+        }
+        B.perm = keep_perm ? d_perm : get<uint32_t>(sc, n_topics);
         B.L = get<uint32_t>(sc, n_topics);
         B.lcp = get<uint32_t>(sc, n_topics);
         B.ten = get<uint32_t>(sc, n_topics);

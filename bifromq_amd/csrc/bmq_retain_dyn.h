@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "bmq_retain_core.h"
+#include "bmq_retain_snap_core.h"
 
 namespace bmq {
 
@@ -21,6 +22,22 @@ struct RetainDynInfo {
     uint64_t overlay_ids = 0; // ids handed out to topics added since the bulk load
     uint64_t overlay_nodes = 0;
     uint64_t batches = 0;
+};
+
+// A snapshot of the live retained topics in exec memory (RetainDyn::snapshot): owns the arrays of RsSnap
+template <class Exec> struct RetainSnapshot {
+    explicit RetainSnapshot(Exec& exec) : x(exec) {}
+    ~RetainSnapshot() { drop(); }
+    RetainSnapshot(const RetainSnapshot&) = delete;
+    RetainSnapshot& operator=(const RetainSnapshot&) = delete;
+    Exec& x;
+    RsSnap s{};
+    uint64_t topic_bytes = 0, bytes = 0; // bytes: everything the snapshot holds in exec memory
+    void drop() {
+        for (void* p : {(void*)s.tenants, (void*)s.tenant_off, (void*)s.item_tenant, (void*)s.topics, (void*)s.topic_off, (void*)s.ts, (void*)s.expiry}) x.release(p);
+        s = RsSnap{};
+        topic_bytes = bytes = 0;
+    }
 };
 
 template <class Exec> class RetainDyn {
@@ -35,6 +52,7 @@ public:
     bool tiny = false; // test knob: minimal capacities, every growth path runs all the time
     RetainDynInfo info;
     bool ready = false;
+    uint64_t copied = 0; // bytes of host <-> exec copies issued so far, whatever the executor (what bmq_retain_compact_info.locked_copy_bytes is the difference of)
 
     // ---- after a bulk load: ids 0 .. n-1 are live ranks; everything dynamic starts empty ----
     bool reset(const RetainIndexView& base_view, const RetainIndexHost& h) {
@@ -53,22 +71,22 @@ public:
                 ex[t->id_base + i] = t->expiry[i];
                 ex_at[t->id_base + i] = h.expire_at[t->id_base + i];
             }
-        if (!x.copy_in_async(d_ts, ts.data(), sizeof(unsigned long long) * base_n) || !x.copy_in_async(d_expiry, ex.data(), sizeof(uint32_t) * base_n) ||
-            !x.copy_in_async(d_expire_at, ex_at.data(), sizeof(unsigned long long) * base_n))
+        if (!cin(d_ts, ts.data(), sizeof(unsigned long long) * base_n) || !cin(d_expiry, ex.data(), sizeof(uint32_t) * base_n) ||
+            !cin(d_expire_at, ex_at.data(), sizeof(unsigned long long) * base_n))
             return xfail();
         // dead bits: bulk-loaded ids live, everything behind them "not retained" until an add hands the id out
         {
             std::vector<unsigned long long> bits(n_words() + 1, ~0ull);
             for (uint32_t w = 0; w < base_n / 64; w++) bits[w] = 0ull;
             if (base_n & 63u) bits[base_n / 64] = ~0ull << (base_n & 63u);
-            if (!x.copy_in_async(d_dead, bits.data(), sizeof(unsigned long long) * (n_words() + 1))) return xfail();
+            if (!cin(d_dead, bits.data(), sizeof(unsigned long long) * (n_words() + 1))) return xfail();
         }
         if (!alloc_overlay(tiny ? 4u : 4096u, tiny ? 16u : 1u << 16)) return false;
         RetainCounters c{};
         c.ov_nodes = 1; // the root
         c.next_id = base_n;
         ONode root{NONE, 0, 0, 0, 0, NONE, NONE, NONE};
-        if (!x.copy_in_async(d_nodes, &root, sizeof(root)) || !x.copy_in_async(d_ctr, &c, sizeof(c))) return xfail();
+        if (!cin(d_nodes, &root, sizeof(root)) || !cin(d_ctr, &c, sizeof(c))) return xfail();
         hc = c;
         if (!x.r_rank(mut(), n_words()) || !x.sync()) return xfail();
         info = RetainDynInfo{};
@@ -124,10 +142,10 @@ public:
             stage_cap = d_stage ? total + total / 4 : 0;
             if (!d_stage) return fail("out of memory (retain op staging)");
         }
-        if (!x.copy_in_async(d_stage + off_t, tenants, tb) || !x.copy_in_async(d_stage + off_to, tenant_off, 4 * ((size_t)n_tenants + 1)) ||
-            (op_tenant && !x.copy_in_async(d_stage + off_ot, op_tenant, 4 * (size_t)n)) || !x.copy_in_async(d_stage + off_p, topics, pb) ||
-            !x.copy_in_async(d_stage + off_po, topic_off, 4 * ((size_t)n + 1)) || !x.copy_in_async(d_stage + off_op, op, n) ||
-            (ts && (!x.copy_in_async(d_stage + off_ts, ts, 8 * (size_t)n) || !x.copy_in_async(d_stage + off_ex, expiry, 4 * (size_t)n))))
+        if (!cin(d_stage + off_t, tenants, tb) || !cin(d_stage + off_to, tenant_off, 4 * ((size_t)n_tenants + 1)) ||
+            (op_tenant && !cin(d_stage + off_ot, op_tenant, 4 * (size_t)n)) || !cin(d_stage + off_p, topics, pb) ||
+            !cin(d_stage + off_po, topic_off, 4 * ((size_t)n + 1)) || !cin(d_stage + off_op, op, n) ||
+            (ts && (!cin(d_stage + off_ts, ts, 8 * (size_t)n) || !cin(d_stage + off_ex, expiry, 4 * (size_t)n))))
             return xfail();
         RetainOps ob{};
         ob.tenants = d_stage + off_t;
@@ -147,8 +165,8 @@ public:
         if (!x.zero((uint8_t*)d_ctr + offsetof(RetainCounters, went_live), sizeof(RetainCounters) - offsetof(RetainCounters, went_live))) return xfail();
         const RetainMut m = mut();
         if (!x.r_locate(m, ob) || !x.r_commit(m, ob) || !x.r_rank(m, n_words())) return xfail();
-        if (!x.copy_out(&hc, d_ctr, sizeof(hc))) return xfail(); // waits for the batch
-        if (out_ids && !x.copy_out(out_ids, ob.out_ids, 4 * (size_t)n)) return xfail();
+        if (!cout(&hc, d_ctr, sizeof(hc))) return xfail(); // waits for the batch
+        if (out_ids && !cout(out_ids, ob.out_ids, 4 * (size_t)n)) return xfail();
         if (hc.err) {
             const uint32_t err = hc.err;
             uint32_t zero32 = 0;
@@ -178,11 +196,11 @@ public:
         if (!ready) return fail("the retained-topic index has not been built");
         if (n == 0) return true;
         if (!ensure(q_buf, q_cap, 4 * (size_t)n)) return false;
-        if (!x.copy_in_async(q_buf, ids, 4 * (size_t)n)) return xfail();
+        if (!cin(q_buf, ids, 4 * (size_t)n)) return xfail();
         if (!x.zero((uint8_t*)d_ctr + offsetof(RetainCounters, went_live), sizeof(RetainCounters) - offsetof(RetainCounters, went_live))) return xfail();
         const RetainMut m = mut();
         if (!x.r_remove_ids(m, (const uint32_t*)q_buf, n, (uint32_t)info.id_bound) || !x.r_rank(m, n_words())) return xfail();
-        if (!x.copy_out(&hc, d_ctr, sizeof(hc))) return xfail(); // waits for the kernels
+        if (!cout(&hc, d_ctr, sizeof(hc))) return xfail(); // waits for the kernels
         uint64_t dead = 0, bdead = 0;
         for (uint32_t k = 0; k < N_CTR_LANES; k++) dead += hc.went_dead[k], bdead += hc.base_went_dead[k];
         info.n_live -= dead;
@@ -197,7 +215,7 @@ public:
         w.assign((size_t)(info.id_bound + 63) / 64 + 1, ~0ull);
         if (!ready) return fail("the retained-topic index has not been built");
         const size_t n = (size_t)(info.id_bound + 63) / 64;
-        return (n == 0 || x.copy_out(w.data(), d_dead, 8 * n)) ? true : xfail();
+        return (n == 0 || cout(w.data(), d_dead, 8 * n)) ? true : xfail();
     }
 
     // ---- retained topics per tenant.  bulk: the (id_base, id_base + topics) rank range of every bulk-loaded tenant, in the order of
@@ -212,8 +230,8 @@ public:
         if (nt) {
             const size_t off_out = align16(8 * (size_t)nt);
             if (!ensure(q_buf, q_cap, off_out + 4 * (size_t)nt)) return false;
-            if (!x.copy_in_async(q_buf, bulk_ranges.data(), 8 * (size_t)nt) || !x.r_census_bulk(m, (const uint32_t*)q_buf, nt, (uint32_t*)(q_buf + off_out)) ||
-                !x.copy_out(bulk_live.data(), q_buf + off_out, 4 * (size_t)nt))
+            if (!cin(q_buf, bulk_ranges.data(), 8 * (size_t)nt) || !x.r_census_bulk(m, (const uint32_t*)q_buf, nt, (uint32_t*)(q_buf + off_out)) ||
+                !cout(bulk_live.data(), q_buf + off_out, 4 * (size_t)nt))
                 return xfail();
         }
         if (info.overlay_ids == 0) return true;
@@ -227,11 +245,11 @@ public:
         uint32_t* d_cnt = (uint32_t*)(q_buf + off_cnt);
         uint32_t n = 0;
         if (!x.zero(d_table, off_list) || !x.zero(d_cnt, 16) || !x.r_census(m, (uint32_t)info.id_bound, d_table) || !x.r_census_pick(d_table, n_nodes, d_list, d_cnt) ||
-            !x.copy_out(&n, d_cnt, 4))
+            !cout(&n, d_cnt, 4))
             return xfail();
         if (n == 0) return true;
         std::vector<unsigned long long> picked(n);
-        if (!x.copy_out(picked.data(), d_list, 8 * (size_t)n)) return xfail();
+        if (!cout(picked.data(), d_list, 8 * (size_t)n)) return xfail();
         std::sort(picked.begin(), picked.end());
         std::vector<uint32_t> nodes(n);
         std::vector<unsigned long long> table_of(n);
@@ -240,16 +258,16 @@ public:
         const size_t off_len = align16(4 * (size_t)n), off_off = align16(off_len + 4 * (size_t)n);
         if (!ensure(q_buf, q_cap, off_off + 8 * ((size_t)n + 1))) return false;
         std::vector<uint32_t> lens(n);
-        if (!x.copy_in_async(q_buf, nodes.data(), 4 * (size_t)n) || !x.r_node_lens(m, (const uint32_t*)q_buf, n, (uint32_t*)(q_buf + off_len)) ||
-            !x.copy_out(lens.data(), q_buf + off_len, 4 * (size_t)n))
+        if (!cin(q_buf, nodes.data(), 4 * (size_t)n) || !x.r_node_lens(m, (const uint32_t*)q_buf, n, (uint32_t*)(q_buf + off_len)) ||
+            !cout(lens.data(), q_buf + off_len, 4 * (size_t)n))
             return xfail();
         std::vector<unsigned long long> offs((size_t)n + 1, 0);
         for (uint32_t i = 0; i < n; i++) offs[i + 1] = offs[i] + lens[i];
         std::vector<uint8_t> bytes(offs[n] + 1);
         if (offs[n]) {
             if (!ensure(o_buf, o_cap, offs[n] + 16)) return false;
-            if (!x.copy_in_async(q_buf + off_off, offs.data(), 8 * ((size_t)n + 1)) ||
-                !x.r_node_write(m, (const uint32_t*)q_buf, n, (const unsigned long long*)(q_buf + off_off), o_buf) || !x.copy_out(bytes.data(), o_buf, offs[n]))
+            if (!cin(q_buf + off_off, offs.data(), 8 * ((size_t)n + 1)) ||
+                !x.r_node_write(m, (const uint32_t*)q_buf, n, (const unsigned long long*)(q_buf + off_off), o_buf) || !cout(bytes.data(), o_buf, offs[n]))
                 return xfail();
         }
         for (uint32_t i = 0; i < n; i++) ov.emplace_back(std::string((const char*)bytes.data() + offs[i], lens[i]), table_of[i]);
@@ -269,13 +287,13 @@ public:
         uint32_t* d_lens = (uint32_t*)(q_buf + off_len);
         unsigned long long* d_offs = (unsigned long long*)(q_buf + off_off);
         const RetainMut m = mut();
-        if (!x.copy_in_async(d_ids, ids, 4 * (size_t)n) || !x.r_topic_lens(m, d_ids, n, d_lens) || !x.copy_out(lens.data(), d_lens, 8 * (size_t)n)) return xfail();
+        if (!cin(d_ids, ids, 4 * (size_t)n) || !x.r_topic_lens(m, d_ids, n, d_lens) || !cout(lens.data(), d_lens, 8 * (size_t)n)) return xfail();
         std::vector<unsigned long long> offs((size_t)n + 1, 0);
         for (uint32_t i = 0; i < n; i++) offs[i + 1] = offs[i] + lens[2 * i + 1];
         bytes.resize(offs[n]);
         if (offs[n] == 0) return true;
         if (!ensure(o_buf, o_cap, offs[n] + 16)) return false;
-        if (!x.copy_in_async(d_offs, offs.data(), 8 * ((size_t)n + 1)) || !x.r_topic_write(m, d_ids, n, d_offs, o_buf) || !x.copy_out(bytes.data(), o_buf, offs[n]))
+        if (!cin(d_offs, offs.data(), 8 * ((size_t)n + 1)) || !x.r_topic_write(m, d_ids, n, d_offs, o_buf) || !cout(bytes.data(), o_buf, offs[n]))
             return xfail();
         return true;
     }
@@ -315,9 +333,9 @@ public:
                 drop_key_store();
                 return fail("out of memory (retain key store)");
             }
-            if (!x.copy_in_async(ks_topics, topics.data(), topics.size()) || !x.copy_in_async(ks_tenants, tenants.data(), tenants.size()) ||
-                !x.copy_in_async(ks_topic_off, toff.data(), 8 * toff.size()) || !x.copy_in_async(ks_tenant_lo, lo.data(), 4 * lo.size()) ||
-                !x.copy_in_async(ks_tenant_off, tnoff.data(), 4 * tnoff.size()) || !x.sync()) {
+            if (!cin(ks_topics, topics.data(), topics.size()) || !cin(ks_tenants, tenants.data(), tenants.size()) ||
+                !cin(ks_topic_off, toff.data(), 8 * toff.size()) || !cin(ks_tenant_lo, lo.data(), 4 * lo.size()) ||
+                !cin(ks_tenant_off, tnoff.data(), 4 * tnoff.size()) || !x.sync()) {
                 drop_key_store();
                 return xfail();
             }
@@ -340,7 +358,7 @@ public:
         const RetainMut m = mut();
         const RetainKeyStore ks = key_store();
         unsigned long long t = 0;
-        if (!x.r_key_offsets(m, ks, ids, n, lens, o) || !x.copy_out(&t, o + n, 8)) return xfail();
+        if (!x.r_key_offsets(m, ks, ids, n, lens, o) || !cout(&t, o + n, 8)) return xfail();
         if (!ensure(k_out, k_out_cap, (size_t)t + 16)) return false;
         if (t && !x.r_key_write(m, ks, ids, n, o, k_out)) return xfail();
         offs = o;
@@ -352,21 +370,21 @@ public:
     bool keys_by_id(const RetainIndexHost& h, const uint32_t* ids, uint32_t n, uint8_t* out, uint64_t cap, unsigned long long* out_off, bool& nospace) {
         nospace = false;
         if (!ensure(k_ids, k_ids_cap, 4 * (size_t)n + 16)) return false;
-        if (!x.copy_in_async(k_ids, ids, 4 * (size_t)n)) return xfail();
+        if (!cin(k_ids, ids, 4 * (size_t)n)) return xfail();
         const unsigned long long* offs = nullptr;
         const uint8_t* bytes = nullptr;
         uint64_t total = 0;
         if (!keys_compose(h, (const uint32_t*)k_ids, n, offs, bytes, total)) return false;
-        if (!x.copy_out(out_off, offs, 8 * ((size_t)n + 1))) return xfail();
+        if (!cout(out_off, offs, 8 * ((size_t)n + 1))) return xfail();
         nospace = total > cap || (total && !out);
-        if (!nospace && total && !x.copy_out(out, bytes, total)) return xfail();
+        if (!nospace && total && !cout(out, bytes, total)) return xfail();
         return true;
     }
 
     bool topic_info(uint32_t id, unsigned long long& ts, uint32_t& expiry, unsigned long long& expire_at_ms, bool& live) {
         if (!ready || id >= info.id_bound) return fail("no such retained topic");
         unsigned long long w = 0;
-        if (!x.copy_out(&ts, d_ts + id, 8) || !x.copy_out(&expiry, d_expiry + id, 4) || !x.copy_out(&expire_at_ms, d_expire_at + id, 8) || !x.copy_out(&w, d_dead + (id >> 6), 8))
+        if (!cout(&ts, d_ts + id, 8) || !cout(&expiry, d_expiry + id, 4) || !cout(&expire_at_ms, d_expire_at + id, 8) || !cout(&w, d_dead + (id >> 6), 8))
             return xfail();
         live = !((w >> (id & 63u)) & 1ull);
         return true;
@@ -374,6 +392,17 @@ public:
     // ids (ascending) the query accepts (GC scan / findAll); tenant_name: resolves GcQuery.t_node when q.has_tenant
     bool select(GcQuery q, const uint8_t* tenant_name, uint32_t tenant_len, std::vector<uint32_t>& out) {
         out.clear();
+        const uint32_t* d_ids = nullptr;
+        uint32_t cnt = 0;
+        if (!select_exec(q, tenant_name, tenant_len, d_ids, cnt)) return false;
+        out.resize(cnt);
+        if (cnt && !cout(out.data(), d_ids, 4 * (size_t)cnt)) return xfail();
+        return true;
+    }
+    // ... the ids stay in exec memory (q_buf: valid until the next call that uses it), only their number comes back
+    bool select_exec(GcQuery q, const uint8_t* tenant_name, uint32_t tenant_len, const uint32_t*& d_ids, uint32_t& cnt) {
+        d_ids = nullptr;
+        cnt = 0;
         if (!ready) return fail("the retained-topic index has not been built");
         q.n_ids = (uint32_t)info.id_bound;
         if (q.n_ids == 0) return true;
@@ -384,14 +413,12 @@ public:
         if (q.has_tenant) {
             std::vector<uint8_t> padded((size_t)tenant_len + 16, 0);
             if (tenant_len) memcpy(padded.data(), tenant_name, tenant_len);
-            if (!x.copy_in_async(q_buf + off_name, padded.data(), padded.size()) || !x.r_find_tenant(m, q_buf + off_name, tenant_len, d_cnt + 1) ||
-                !x.copy_out(&q.t_node, d_cnt + 1, 4))
+            if (!cin(q_buf + off_name, padded.data(), padded.size()) || !x.r_find_tenant(m, q_buf + off_name, tenant_len, d_cnt + 1) ||
+                !cout(&q.t_node, d_cnt + 1, 4))
                 return xfail();
         }
-        uint32_t cnt = 0;
-        if (!x.r_gc_select(m, q, q_buf, (uint32_t*)(q_buf + off_ids), d_cnt) || !x.copy_out(&cnt, d_cnt, 4)) return xfail();
-        out.resize(cnt);
-        if (cnt && !x.copy_out(out.data(), q_buf + off_ids, 4 * (size_t)cnt)) return xfail();
+        if (!x.r_gc_select(m, q, q_buf, (uint32_t*)(q_buf + off_ids), d_cnt) || !cout(&cnt, d_cnt, 4)) return xfail();
+        d_ids = (const uint32_t*)(q_buf + off_ids);
         return true;
     }
 
@@ -402,9 +429,23 @@ public:
     // has none, as keys_compose does.
     bool boundary_select(const RetainIndexHost& h, uint32_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len, uint64_t& topics,
                          uint64_t* key_bytes, std::vector<uint32_t>* ids) {
+        if (ids) ids->clear();
+        const uint32_t* d_ids = nullptr;
+        uint32_t cnt = 0;
+        if (!boundary_select_exec(h, flags, start, start_len, end, end_len, topics, key_bytes, ids != nullptr, d_ids, cnt)) return false;
+        if (ids) {
+            ids->resize(cnt);
+            if (cnt && !cout(ids->data(), d_ids, 4 * (size_t)cnt)) return xfail();
+        }
+        return true;
+    }
+    // ... want_ids: the ids stay in exec memory (q_buf), their number comes back
+    bool boundary_select_exec(const RetainIndexHost& h, uint32_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len, uint64_t& topics,
+                              uint64_t* key_bytes, bool want_ids, const uint32_t*& d_ids, uint32_t& cnt) {
         topics = 0;
         if (key_bytes) *key_bytes = 0;
-        if (ids) ids->clear();
+        d_ids = nullptr;
+        cnt = 0;
         if (!keys_prepare(h, nullptr)) return false;
         const uint32_t n = (uint32_t)info.id_bound;
         if (n == 0) return true;
@@ -412,7 +453,7 @@ public:
         if (!(flags & 2u)) end_len = 0;
         const size_t off_ctr = align16((size_t)n), off_cnt = off_ctr + 16, off_start = off_cnt + 16, off_end = align16(off_start + start_len + 16),
                      off_ids = align16(off_end + end_len + 16);
-        if (!ensure(q_buf, q_cap, off_ids + (ids ? 4 * (size_t)n : 0))) return false;
+        if (!ensure(q_buf, q_cap, off_ids + (want_ids ? 4 * (size_t)n : 0))) return false;
         unsigned long long* d_sums = (unsigned long long*)(q_buf + off_ctr);
         uint32_t* d_cnt = (uint32_t*)(q_buf + off_cnt);
         KeyBoundary kb{};
@@ -421,18 +462,16 @@ public:
         kb.start_len = start_len;
         kb.end_len = end_len;
         kb.flags = flags & 3u;
-        if (!x.zero(q_buf + off_ctr, 32) || !x.copy_in_async(q_buf + off_start, start, start_len) || !x.copy_in_async(q_buf + off_end, end, end_len)) return xfail();
+        if (!x.zero(q_buf + off_ctr, 32) || !cin(q_buf + off_start, start, start_len) || !cin(q_buf + off_end, end, end_len)) return xfail();
         unsigned long long sums[2] = {0, 0};
-        if (!x.r_boundary(mut(), key_store(), n, kb, ids ? q_buf : nullptr, key_bytes != nullptr, d_sums)) return xfail();
-        if (ids && !x.r_flagged_ids(q_buf, n, (uint32_t*)(q_buf + off_ids), d_cnt)) return xfail();
-        if (!x.copy_out(sums, d_sums, 16)) return xfail(); // waits for the pass
+        if (!x.r_boundary(mut(), key_store(), n, kb, want_ids ? q_buf : nullptr, key_bytes != nullptr, d_sums)) return xfail();
+        if (want_ids && !x.r_flagged_ids(q_buf, n, (uint32_t*)(q_buf + off_ids), d_cnt)) return xfail();
+        if (!cout(sums, d_sums, 16)) return xfail(); // waits for the pass
         topics = sums[0];
         if (key_bytes) *key_bytes = sums[1];
-        if (ids) {
-            uint32_t cnt = 0;
-            if (!x.copy_out(&cnt, d_cnt, 4)) return xfail();
-            ids->resize(cnt);
-            if (cnt && !x.copy_out(ids->data(), q_buf + off_ids, 4 * (size_t)cnt)) return xfail();
+        if (want_ids) {
+            if (!cout(&cnt, d_cnt, 4)) return xfail();
+            d_ids = (const uint32_t*)(q_buf + off_ids);
         }
         return true;
     }
@@ -442,8 +481,188 @@ public:
         ts.assign(info.id_bound ? info.id_bound : 1, 0);
         expiry.assign(info.id_bound ? info.id_bound : 1, 0);
         if (!ready) return fail("the retained-topic index has not been built");
-        if (!x.copy_out(ts.data(), d_ts, 8 * (size_t)info.id_bound) || !x.copy_out(expiry.data(), d_expiry, 4 * (size_t)info.id_bound)) return xfail();
+        if (!cout(ts.data(), d_ts, 8 * (size_t)info.id_bound) || !cout(expiry.data(), d_expiry, 4 * (size_t)info.id_bound)) return xfail();
         return true;
+    }
+
+    // ---- the live topics (bflags = 0), or those whose retainMessageKey lies inside the boundary, as a private snapshot in exec memory, in the
+    // layout the executor builder reads (bmq_retain_snap_core.h).  Runs on the executor's stream behind whatever is in flight and ends in a
+    // synchronise; nothing of this generation is referenced by `out` afterwards.  What crosses to the host: the number of ids and four totals.
+    // The strings of the bulk-loaded ids come from the key store, which is built here from the host's copy of the load if the generation has
+    // none (keys_prepare ahead of the call takes that out of it).
+    bool snapshot(const RetainIndexHost& h, uint32_t bflags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len, RetainSnapshot<Exec>& out) {
+        error.clear();
+        out.drop();
+        if (!keys_prepare(h, nullptr)) return false;
+        const uint32_t* d_ids = nullptr;
+        uint32_t n = 0;
+        if (bflags & 3u) {
+            uint64_t topics = 0;
+            if (!boundary_select_exec(h, bflags, start, start_len, end, end_len, topics, nullptr, true, d_ids, n)) return false;
+        } else {
+            GcQuery q{};
+            q.live_only = 1;
+            q.override_expiry = -1;
+            if (!select_exec(q, nullptr, 0, d_ids, n)) return false;
+        }
+        std::vector<void*> tmp; // transient arrays: released behind the last synchronise
+        struct Free {
+            Exec& x;
+            std::vector<void*>& v;
+            ~Free() {
+                (void)x.sync();
+                for (void* p : v) x.release(p);
+            }
+        } free_tmp{x, tmp};
+        auto get = [&](size_t bytes) {
+            void* p = x.alloc(bytes + 16);
+            if (p) tmp.push_back(p);
+            return p;
+        };
+        const uint32_t nodes = hc.ov_nodes;
+        RsArgs A{};
+        RsSnap& S = out.s;
+        S.n = n;
+        S.item_tenant = take<uint32_t>((size_t)n + 4);
+        S.topic_off = take<uint32_t>((size_t)n + 4);
+        S.ts = take<unsigned long long>((size_t)n + 2);
+        S.expiry = take<uint32_t>((size_t)n + 4);
+        A.ids = d_ids;
+        A.len = (uint32_t*)get(4 * ((size_t)n + 1));
+        A.tn_flag = (uint32_t*)get(4 * (size_t)nodes);
+        A.tn_len = (uint32_t*)get(4 * (size_t)nodes);
+        A.tn_rank = (uint32_t*)get(4 * (size_t)nodes);
+        A.tn_end = (uint32_t*)get(4 * (size_t)nodes);
+        A.totals = (unsigned long long*)get(32);
+        A.ov_nodes = nodes;
+        if (!S.item_tenant || !S.topic_off || !S.ts || !S.expiry || !A.len || !A.tn_flag || !A.tn_len || !A.tn_rank || !A.tn_end || !A.totals)
+            return fail("out of memory (retain snapshot)");
+        A.S = S;
+        const RetainMut m = mut();
+        const RetainKeyStore ks = key_store();
+        uint32_t ks_tb = 0; // bytes of the key store's tenant ids: its last offset (4 bytes, once per snapshot)
+        if (ks.n_tenants && !cout(&ks_tb, ks.tenant_off + ks.n_tenants, 4)) return xfail();
+        A.ks_tenants = ks.n_tenants;
+        A.ks_tenant_bytes = ks_tb;
+        // lengths and tenants per id, their sums; the overlay tenants that own one
+        unsigned long long totals[4] = {0, 0, 0, 0};
+        if (!x.zero(A.totals, 32) || !x.zero(A.tn_flag, 4 * (size_t)nodes) || !x.zero(S.topic_off, 4) || !x.rs_lens(m, ks, A) || (n && !x.scan_flags(A.len, S.topic_off + 1, n)) ||
+            !x.rs_tenant_lens(m, A) || (nodes && (!x.scan_flags(A.tn_flag, A.tn_rank, nodes) || !x.scan_flags(A.tn_len, A.tn_end, nodes))) || !x.rs_totals(A) ||
+            !cout(totals, A.totals, 32))
+            return xfail();
+        if (totals[0] >= 0xFFFFFFF0ull) return fail("the topics of the snapshot exceed 4 GiB");
+        const uint32_t n_ov_t = (uint32_t)totals[2], ov_tb = (uint32_t)totals[3];
+        A.n_bulk = (uint32_t)totals[1];
+        out.topic_bytes = totals[0];
+        S.n_tenants = ks.n_tenants + n_ov_t;
+        S.topics = (uint8_t*)x.alloc((size_t)totals[0] + 32);
+        S.tenants = (uint8_t*)x.alloc((size_t)ks_tb + ov_tb + 32);
+        S.tenant_off = take<uint32_t>((size_t)S.n_tenants + 4);
+        if (!S.topics || !S.tenants || !S.tenant_off) return fail("out of memory (retain snapshot)");
+        A.S = S;
+        // the tenant table: the key store's entries, then the overlay's; the topics: the bulk-loaded ids' runs of the key store, then the overlay chains
+        RsGather<unsigned long long> G{S.topics, S.topic_off, A.n_bulk, ks.topics, ks.topic_off, d_ids, 0ull};
+        uint32_t bulk_bytes = 0;
+        if (A.n_bulk && !cout(&bulk_bytes, S.topic_off + A.n_bulk, 4)) return xfail();
+        G.bytes = bulk_bytes;
+        if (!x.zero(S.tenant_off, 4) || (ks.n_tenants && (!x.copy(S.tenant_off, ks.tenant_off, 4 * ((size_t)ks.n_tenants + 1)) || !x.copy(S.tenants, ks.tenants, ks_tb))) ||
+            !x.zero(S.tenants + ks_tb + ov_tb, 16) || !x.rs_tenants(m, A) || !x.zero(S.topics + totals[0], 16) || !x.rs_gather(G) || !x.rs_items(m, A) || !x.sync())
+            return xfail();
+        out.bytes = totals[0] + ks_tb + ov_tb + 4 * ((size_t)S.n_tenants + 1) + 24 * (size_t)n + 4;
+        return true;
+    }
+
+    // ---- the mutable part of a generation that RetainBuild<Exec> has just built from a snapshot, made ready AHEAD of the swap on this
+    // instance's executor (the build stream): per-id payload and key store through the builder's permutation (d_perm: exec memory, rank ->
+    // item of `s`), dead bitmap and empty overlay by fills.  No host loop over the topics.  adopt() of the serving instance takes it over.
+    bool reset_exec(const RsSnap& s, const uint32_t* d_perm, uint32_t n_topics, const std::vector<std::string>& names, const std::vector<uint32_t>& t_begin) {
+        error.clear();
+        drop();
+        base = RetainIndexView{};
+        base_n = n_topics;
+        const uint32_t want_ids = base_n + (tiny ? 4u : std::max<uint32_t>(1024u, base_n / 8));
+        if (!alloc_ids(want_ids)) return false;
+        const uint32_t live_words = base_n / 64;
+        unsigned long long edge_word = ~0ull << (base_n & 63u); // the word the bulk-loaded ids end in
+        if (!x.zero(d_dead, 8 * (size_t)live_words) || !x.fill_bytes(d_dead + live_words, 0xFF, 8 * ((size_t)n_words() + 1 - live_words)) ||
+            ((base_n & 63u) && !cin(d_dead + live_words, &edge_word, 8)))
+            return xfail();
+        if (!alloc_overlay(tiny ? 4u : 4096u, tiny ? 16u : 1u << 16)) return false;
+        RetainCounters c{};
+        c.ov_nodes = 1; // the root
+        c.next_id = base_n;
+        ONode root{NONE, 0, 0, 0, 0, NONE, NONE, NONE};
+        if (!cin(d_nodes, &root, sizeof(root)) || !cin(d_ctr, &c, sizeof(c)) || !x.sync()) return xfail();
+        hc = c;
+        // the key store: the builder's tenants are the ranges t_begin[t] .. t_begin[t + 1] of the ranks, every one with topics
+        std::vector<uint8_t> tbytes;
+        std::vector<uint32_t> tnoff{0};
+        for (const std::string& nm : names) {
+            tbytes.insert(tbytes.end(), nm.begin(), nm.end());
+            tnoff.push_back((uint32_t)tbytes.size());
+        }
+        std::vector<uint32_t> lo(t_begin.begin(), t_begin.end());
+        if (lo.empty()) lo.push_back(0u);
+        lo.back() = base_n;
+        ks_n_tenants = (uint32_t)lo.size() - 1;
+        uint32_t* klen = take<uint32_t>((size_t)base_n + 4);
+        uint32_t* koff = take<uint32_t>((size_t)base_n + 4);
+        ks_topic_off = take<unsigned long long>((size_t)base_n + 2);
+        ks_tenants = (uint8_t*)x.alloc(tbytes.size() + 16);
+        ks_tenant_lo = take<uint32_t>(lo.size());
+        ks_tenant_off = take<uint32_t>(tnoff.size());
+        bool ok = klen && koff && ks_topic_off && ks_tenants && ks_tenant_lo && ks_tenant_off;
+        uint32_t key_bytes = 0;
+        RsNext N{d_perm, base_n, s.topic_off, s.ts, s.expiry, klen, koff, d_ts, d_expire_at, d_expiry, ks_topic_off};
+        if (ok)
+            ok = x.zero(koff, 4) && x.zero(ks_topic_off, 8) && x.rs_perm_lens(N) && (base_n == 0 || x.scan_flags(klen, koff + 1, base_n)) && x.rs_next(N) &&
+                 cout(&key_bytes, koff + base_n, 4);
+        if (ok) ks_topics = (uint8_t*)x.alloc((size_t)key_bytes + 32);
+        ok = ok && ks_topics;
+        if (ok) {
+            const RsGather<uint32_t> G{ks_topics, koff, base_n, s.topics, s.topic_off, d_perm, key_bytes};
+            ok = x.rs_gather(G) && x.zero(ks_topics + key_bytes, 16) && cin(ks_tenants, tbytes.data(), tbytes.size()) && cin(ks_tenant_lo, lo.data(), 4 * lo.size()) &&
+                 cin(ks_tenant_off, tnoff.data(), 4 * tnoff.size()) && x.r_rank(mut(), n_words());
+        }
+        ok = x.sync() && ok;
+        x.release(klen);
+        x.release(koff);
+        if (!ok) {
+            const std::string why = x.err.empty() ? std::string("out of memory (next retain generation)") : x.err;
+            drop();
+            return fail(why);
+        }
+        ks_bytes = (uint64_t)key_bytes + tbytes.size() + 8 * ((size_t)base_n + 1) + 4 * lo.size() + 4 * tnoff.size();
+        ks_ready = true;
+        info = RetainDynInfo{};
+        info.n_live = base_n;
+        info.id_bound = base_n;
+        info.base_n = base_n;
+        seq = 0;
+        ready = true;
+        return true;
+    }
+    // the arrays `o` prepared (reset_exec) become this instance's: pointers change hands, nothing is copied; `o` is left empty
+    void adopt(RetainDyn& o, const RetainIndexView& base_view) {
+        drop();
+        base = base_view;
+        base_n = o.base_n;
+        d_expire_at = o.d_expire_at, d_ts = o.d_ts, d_expiry = o.d_expiry, d_id_node = o.d_id_node, d_id_tnode = o.d_id_tnode;
+        d_dead = o.d_dead, d_rank = o.d_rank, d_last = o.d_last, d_nodes = o.d_nodes, d_edges = o.d_edges, d_pool = o.d_pool, d_ctr = o.d_ctr;
+        hc = o.hc;
+        id_cap = o.id_cap, ov_cap = o.ov_cap, pool_cap = o.pool_cap, edge_slots = o.edge_slots;
+        ks_topics = o.ks_topics, ks_tenants = o.ks_tenants, ks_topic_off = o.ks_topic_off, ks_tenant_lo = o.ks_tenant_lo, ks_tenant_off = o.ks_tenant_off;
+        ks_n_tenants = o.ks_n_tenants, ks_bytes = o.ks_bytes, ks_ready = o.ks_ready;
+        info = o.info;
+        seq = 0;
+        ready = o.ready;
+        o.d_expire_at = o.d_ts = nullptr;
+        o.d_expiry = o.d_id_node = o.d_id_tnode = nullptr;
+        o.d_dead = nullptr, o.d_rank = nullptr, o.d_last = nullptr, o.d_nodes = nullptr, o.d_edges = nullptr, o.d_pool = nullptr, o.d_ctr = nullptr;
+        o.ks_topics = o.ks_tenants = nullptr;
+        o.ks_topic_off = nullptr;
+        o.ks_tenant_lo = o.ks_tenant_off = nullptr;
+        o.drop();
     }
 
     void drop() {
@@ -517,6 +736,15 @@ private:
     }
 
     static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+    // every host <-> exec copy of this class is issued here and counted (`copied`)
+    bool cin(void* d, const void* s, size_t n) {
+        copied += n;
+        return x.copy_in_async(d, s, n);
+    }
+    bool cout(void* d, const void* s, size_t n) {
+        copied += n;
+        return x.copy_out(d, s, n);
+    }
     uint32_t n_words() const { return (id_cap + 63) / 64; }
     bool fail(const std::string& m) {
         error = m;

@@ -47,6 +47,7 @@ int upload_retain(bmq_engine* e) {
     if ((rc = upload(e, d.dict, h.dict.data(), h.dict.size() * sizeof(DictSlot)))) return rc;
     if ((rc = upload(e, d.pool, h.pool.data(), h.pool.size()))) return rc;
     HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->r_up_bytes += nb + eb + h.posts.size() * sizeof(REdge) + h.gps.size() * sizeof(RGp) + h.tenants.size() * sizeof(RTenantSlot) + h.dict.size() * sizeof(DictSlot) + h.pool.size();
     h.full_upload = false;
     h.dict_changed = false;
     h.dirty.clear();
@@ -917,7 +918,13 @@ static int retain_live_items_locked(bmq_engine* e, std::vector<RetainIndexHost::
 // both back into a fresh bulk load, but under the engine lock: 2 s for 1 M topics (the host-side load).  The three calls below take the
 // load out of the lock:  begin = snapshot of the live topics (tens of ms under the lock); build = the load into an index of its own, no
 // lock held, matching and bmq_retain_apply* go on (what they change is logged); swap = upload + replay of the log under the lock.
+// With bmq_config.retain_builder = 3 (under 1 the three calls stay as they are) the snapshot is gathered where the index lives and stays there (RetainDyn::snapshot), build runs the
+// executor builder on an executor of its own and makes the next mutable part ready (retain_build_next), swap exchanges pointers: what the
+// two holds of the lock copy between host and executor is a handful of words (bmq_retain_compact_info.locked_copy_bytes).
 int bmq_retain_compact_begin(bmq_engine* e) { return bmq_retain_compact_begin_in(e, 0, nullptr, 0, nullptr, 0); }
+// bytes of host <-> exec copies the retain direction has issued so far (RetainDyn::copied + the image uploads): under e->mu
+static uint64_t retain_copy_meter(bmq_engine* e) { return (e->drt ? e->drt->copied : e->hrt->copied) + e->r_up_bytes; }
+static float ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 // ... for a range that SHRINKS (RetainStoreCoProc.reset(Boundary) after a split): the snapshot takes only the topics whose key lies inside
 // the boundary, and the swap replays only the logged ops whose key does.  The serving generation matches and mutates over all its topics
 // until the swap.
@@ -931,31 +938,152 @@ int bmq_retain_compact_begin_in(bmq_engine* e, uint8_t flags, const uint8_t* sta
     if (e->rcmp.active) return set_err(e, BMQ_E_STATE, "a retain compaction is running: bmq_retain_compact_swap or bmq_retain_compact_abort first");
     if (!e->rbuilt) return set_err(e, BMQ_E_STATE, "no retained-topic index");
     if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t meter0 = retain_copy_meter(e);
     e->rcmp = bmq_engine::RetainCompaction{};
-    e->rcmp.bound = bound;
-    if (int rc = retain_live_items_locked(e, e->rcmp.items, bound)) return rc;
-    e->rcmp.active = true;
+    bmq_engine::RetainCompaction& c = e->rcmp;
+    c.bound = bound;
+    if (e->rb_generation) { // bmq_config.retain_builder = 3: ids, strings and stamps are gathered where the index lives and stay there
+        if (e->drb && !e->s_build) {
+            int least = 0, greatest = 0;
+            HIPCHK(e, hipDeviceGetStreamPriorityRange(&least, &greatest));
+            HIPCHK(e, hipStreamCreateWithPriority(&e->s_build, hipStreamNonBlocking, least)); // a match batch's waves go first
+            HIPCHK(e, hipEventCreateWithFlags(&e->ev_serving, hipEventDisableTiming));
+        }
+        e->rbx.stream = e->s_build;
+        bool ok;
+        if (e->drb) {
+            c.dsnap = std::make_unique<RetainSnapshot<DevExec>>(e->dx);
+            ok = e->drt->snapshot(e->rhost, bound.flags, (const uint8_t*)bound.start.data(), (uint32_t)bound.start.size(), (const uint8_t*)bound.end.data(), (uint32_t)bound.end.size(), *c.dsnap);
+            if (!ok) e->err = e->drt->error;
+        } else {
+            c.hsnap = std::make_unique<RetainSnapshot<HostExec>>(e->hx);
+            ok = e->hrt->snapshot(e->rhost, bound.flags, (const uint8_t*)bound.start.data(), (uint32_t)bound.start.size(), (const uint8_t*)bound.end.data(), (uint32_t)bound.end.size(), *c.hsnap);
+            if (!ok) e->err = e->hrt->error;
+        }
+        if (!ok) {
+            const std::string msg = e->err;
+            e->rcmp = bmq_engine::RetainCompaction{};
+            return set_err(e, msg.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : (msg.find("exceed") != std::string::npos ? BMQ_E_RANGE : BMQ_E_HIP), msg);
+        }
+        c.exec_snapshot = true;
+        c.ci.n_items = c.dsnap ? c.dsnap->s.n : c.hsnap->s.n;
+        c.ci.snapshot_bytes = c.dsnap ? c.dsnap->bytes : c.hsnap->bytes;
+        c.ci.builder = 1;
+    } else {
+        if (int rc = retain_live_items_locked(e, c.items, bound)) return rc;
+        c.ci.n_items = c.items.size();
+        for (const auto& it : c.items) c.ci.snapshot_bytes += it.tenant.size() + it.topic.size() + 12;
+    }
+    c.active = true;
+    c.ci.state = 1;
+    c.ci.locked_copy_bytes = retain_copy_meter(e) - meter0;
+    c.ci.begin_ms = ms_since(t0);
     return BMQ_OK;
 }
+
+// bmq_retain_compact_build with the executor builder: the next image from the snapshot, the next catalogue from ONE copy of the snapshot to the
+// host, the next mutable part ready in exec memory.  Runs on bx (its own stream); no engine lock.  *msg: why it failed (rc != BMQ_OK).
+extern "C++" {
+template <class Exec>
+static int retain_build_next(bmq_engine::RetainCompaction& c, Exec& bx, RetainSnapshot<Exec>& snap, std::unique_ptr<RetainBuild<Exec>>& nrb, std::unique_ptr<RetainDyn<Exec>>& nrt, bool tiny,
+                             std::string& msg) {
+    const RsSnap& S = snap.s;
+    // the tenant table is small: the builder de-duplicates and byte-sorts it on the host
+    std::vector<uint8_t> tb;
+    std::vector<uint32_t> toff((size_t)S.n_tenants + 1, 0);
+    if (!bx.copy_out(toff.data(), S.tenant_off, 4 * toff.size())) return msg = bx.err, BMQ_E_HIP;
+    tb.resize((size_t)toff[S.n_tenants] + 16, 0);
+    if (!bx.copy_out(tb.data(), S.tenants, toff[S.n_tenants])) return msg = bx.err, BMQ_E_HIP;
+    RbInput in{tb.data(), toff.data(), S.n_tenants, S.item_tenant, S.topics, S.topic_off, S.n, nullptr, nullptr};
+    in.in_exec = true;
+    in.topic_bytes = snap.topic_bytes;
+    nrb = std::make_unique<RetainBuild<Exec>>(bx);
+    nrb->keep_perm = true;
+    const bool built = nrb->build(in);
+    if (!built && !nrb->too_deep) {
+        msg = nrb->error;
+        return msg.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : (msg.find("too many") != std::string::npos ? BMQ_E_INVAL : BMQ_E_HIP);
+    }
+    // the packed snapshot on the host, once: what the catalogue's strings and stamps are cut from (or what the host builder loads)
+    std::vector<uint8_t> pb((size_t)snap.topic_bytes + 16, 0);
+    std::vector<uint32_t> poff((size_t)S.n + 1, 0), it_tenant(S.n), ex(S.n);
+    std::vector<uint64_t> ts(S.n);
+    if (!bx.copy_out(pb.data(), S.topics, snap.topic_bytes) || !bx.copy_out(poff.data(), S.topic_off, 4 * poff.size()) || !bx.copy_out(ts.data(), S.ts, 8 * (size_t)S.n) ||
+        !bx.copy_out(ex.data(), S.expiry, 4 * (size_t)S.n) || (!built && !bx.copy_out(it_tenant.data(), S.item_tenant, 4 * (size_t)S.n)))
+        return msg = bx.err, BMQ_E_HIP;
+    if (!built) { // declined: a topic of more than RB_MAX_DEPTH levels.  The host builder over the same items; the swap is then an upload
+        nrb.reset();
+        std::vector<RetainIndexHost::Item> items(S.n);
+        for (uint32_t i = 0; i < S.n; i++) {
+            const uint32_t t = it_tenant[i];
+            items[i].tenant.assign((const char*)tb.data() + toff[t], toff[t + 1] - toff[t]);
+            items[i].topic.assign((const char*)pb.data() + poff[i], poff[i + 1] - poff[i]);
+            items[i].ts = ts[i];
+            items[i].expiry = ex[i];
+            items[i].has_ts = !(ts[i] == 0 && ex[i] == 0xFFFFFFFFu);
+        }
+        if (!c.next.rebuild(std::move(items))) return msg = c.next.error, BMQ_E_INVAL;
+        c.fallback = 1;
+        c.exec_built = false;
+        return BMQ_OK;
+    }
+    in.in_exec = false;
+    in.item_tenant = nullptr; // (retain_catalogue reads topics, offsets and stamps)
+    in.topics = pb.data(), in.topic_off = poff.data(), in.ts = ts.data(), in.expiry = ex.data();
+    retain_catalogue(c.next, in, *nrb);
+    nrt = std::make_unique<RetainDyn<Exec>>(bx);
+    nrt->tiny = tiny;
+    if (!nrt->reset_exec(S, nrb->d_perm, (uint32_t)nrb->info.n_topics, nrb->names, nrb->t_begin)) {
+        msg = nrt->error;
+        return msg.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : BMQ_E_HIP;
+    }
+    nrb->drop_perm();
+    c.exec_built = true;
+    return BMQ_OK;
+}
+} // extern "C++"
+
 int bmq_retain_compact_build(bmq_engine* e) {
     if (!e) return BMQ_E_INVAL;
     std::lock_guard<std::mutex> gc(e->cmp_mu); // (one compaction call at a time; the engine lock is NOT held: this is the long part)
     bmq_engine::RetainCompaction& c = e->rcmp;
+    bool tiny = false;
     {
         std::lock_guard<std::mutex> g(e->mu);
         if (!c.active) return set_err(e, BMQ_E_STATE, "no retain compaction is running");
         if (c.built) return BMQ_OK;
+        tiny = e->drt ? e->drt->tiny : e->hrt->tiny;
     }
     const auto t0 = std::chrono::steady_clock::now();
-    c.n_items = c.items.size();
-    if (!c.next.rebuild(std::move(c.items))) {
-        std::lock_guard<std::mutex> g(e->mu);
-        return set_err(e, BMQ_E_INVAL, c.next.error);
+    if (c.exec_snapshot) {
+        std::string msg;
+        int rc;
+        if (c.dsnap) {
+            if (hipSetDevice(e->device) != hipSuccess) rc = BMQ_E_HIP, msg = "hipSetDevice failed";
+            else rc = retain_build_next(c, e->rbx, *c.dsnap, c.ndrb, c.ndrt, tiny, msg);
+        } else rc = retain_build_next(c, e->rhx, *c.hsnap, c.nhrb, c.nhrt, tiny, msg);
+        if (rc) {
+            std::lock_guard<std::mutex> g(e->mu);
+            return set_err(e, rc, msg);
+        }
+        c.n_items = c.dsnap ? c.dsnap->s.n : c.hsnap->s.n;
+        c.dsnap.reset(), c.hsnap.reset(); // (the next generation holds everything it needs)
+    } else {
+        c.n_items = c.items.size();
+        if (!c.next.rebuild(std::move(c.items))) {
+            std::lock_guard<std::mutex> g(e->mu);
+            return set_err(e, BMQ_E_INVAL, c.next.error);
+        }
+        c.items.clear(), c.items.shrink_to_fit();
     }
-    c.items.clear(), c.items.shrink_to_fit();
     std::lock_guard<std::mutex> g(e->mu);
-    c.ms_build = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c.ms_build = ms_since(t0);
     c.built = true;
+    c.ci.state = 2;
+    c.ci.builder = c.exec_built ? 1 : 0;
+    c.ci.fallback = c.fallback;
+    c.ci.build_ms = c.ms_build;
     return BMQ_OK;
 }
 int bmq_retain_compact_swap(bmq_engine* e, uint64_t* out_carried, uint64_t* out_replayed) {
@@ -963,6 +1091,7 @@ int bmq_retain_compact_swap(bmq_engine* e, uint64_t* out_carried, uint64_t* out_
     std::lock_guard<std::recursive_mutex> api_lock(e->api);
     std::lock_guard<std::mutex> gc(e->cmp_mu);
     uint64_t n_log = 0;
+    bmq_retain_compact_info ci{};
     {
         std::lock_guard<std::mutex> g(e->mu);
         bmq_engine::RetainCompaction& c = e->rcmp;
@@ -972,15 +1101,39 @@ int bmq_retain_compact_swap(bmq_engine* e, uint64_t* out_carried, uint64_t* out_
         for (auto& sl : e->slots)
             if (sl.pending) return set_err(e, BMQ_E_STATE, "a batch is in flight: finish / wait for it first");
         if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
+        const auto t0 = std::chrono::steady_clock::now();
+        const uint64_t meter0 = retain_copy_meter(e);
         if (out_carried) *out_carried = c.next.n_topics;
         e->rhost = std::move(c.next);
-        e->rb_serving = false; // (bmq_retain_compact_build is the host builder's)
-        e->rbinfo = host_build_info(e->rhost, c.n_items, c.ms_build, 0);
-        if (int rc = retain_publish(e)) { // upload + the mutable part starts over: a new generation of topic ids
-            e->rcmp = bmq_engine::RetainCompaction{};
-            return rc;
+        if (c.exec_built) { // image, key store and mutable part change hands: no upload, no host loop over the topics
+            e->rb_serving = true;
+            if (e->drb) {
+                e->drb->take_image(*c.ndrb);
+                e->drb->view(e->rdev.view);
+                for (DevBuf* b : {&e->rdev.nodes, &e->rdev.edges, &e->rdev.posts, &e->rdev.gps, &e->rdev.tenants, &e->rdev.dict, &e->rdev.pool}) b->release(); // (a host-built generation's)
+                e->drt->adopt(*c.ndrt, e->rdev.view);
+                e->rbinfo = e->drb->info;
+            } else {
+                e->hrb->take_image(*c.nhrb);
+                e->hrb->view(e->rhview);
+                e->hrt->adopt(*c.nhrt, e->rhview);
+                e->rbinfo = e->hrb->info;
+            }
+            e->rbuilt = true;
+            e->repoch++;
+            e->rgeneration++;
+        } else {
+            e->rb_serving = false; // (the host builder's: retain_builder = 0 or 1, or the executor builder declined)
+            e->rbinfo = host_build_info(e->rhost, c.n_items, c.ms_build, c.fallback);
+            if (int rc = retain_publish(e)) { // upload + the mutable part starts over: a new generation of topic ids
+                e->rcmp = bmq_engine::RetainCompaction{};
+                return rc;
+            }
         }
         n_log = c.log.size();
+        ci = c.ci;
+        ci.locked_copy_bytes += retain_copy_meter(e) - meter0;
+        ci.swap_ms = ms_since(t0);
     }
     // what was added / removed meanwhile, in order (the ordinary apply path; nothing is logged any more: the compaction is over)
     std::vector<bmq_engine::RetainCompaction::Op> log;
@@ -999,6 +1152,9 @@ int bmq_retain_compact_swap(bmq_engine* e, uint64_t* out_carried, uint64_t* out_
             log.resize(kept);
             n_log = kept;
         }
+        ci.state = 3;
+        ci.replayed = n_log;
+        e->rcinfo = ci;
     }
     for (size_t lo = 0; lo < log.size();) {
         const size_t hi = std::min(log.size(), lo + 65536);
@@ -1037,7 +1193,15 @@ int bmq_retain_compact_abort(bmq_engine* e) {
     std::lock_guard<std::recursive_mutex> api_lock(e->api);
     std::lock_guard<std::mutex> gc(e->cmp_mu);
     std::lock_guard<std::mutex> g(e->mu);
-    e->rcmp = bmq_engine::RetainCompaction{};
+    if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
+    e->rcmp = bmq_engine::RetainCompaction{}; // (the snapshot and the next generation's buffers go with it; bmq_retain_compact_info tells of the last swap again)
+    return BMQ_OK;
+}
+int bmq_retain_compact_info_get(const bmq_engine* ce, bmq_retain_compact_info* out) {
+    bmq_engine* e = const_cast<bmq_engine*>(ce);
+    if (!e || !out) return BMQ_E_INVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    *out = e->rcmp.active ? e->rcmp.ci : e->rcinfo;
     return BMQ_OK;
 }
 

@@ -199,7 +199,7 @@ class Engine:
         cfg.region_slack = region_slack  # 0: default (6: trie regions at load factor 0.2); 1: 0.4 (less memory, more second probes)
         cfg.tail_records = tail_records  # 0: default (tail records on); 1: off
         cfg.child_filters = child_filters  # 0: default (the walk reads the nodes' child filter words); 1: it ignores them
-        cfg.retain_builder = retain_builder  # 0: default (the host builder bulk-loads the retained-topic index); 1: the executor builder
+        cfg.retain_builder = retain_builder  # 0: default (the host builder bulk-loads the retained-topic index); 1: the executor builder; 3: it also serves retain_compact_begin / _build / _swap
         h = C.c_void_p()
         rc = L.bmq_engine_create(C.byref(cfg), C.byref(h))
         if rc:
@@ -712,13 +712,22 @@ class Engine:
         self._check(_lib.lib().bmq_retain_import(self.h, src.h, *self._boundary(start, end), C.byref(imported), C.byref(replaced)))
         return int(imported.value), int(replaced.value)
 
+    def retain_compact_info(self) -> "_lib.RetainCompactInfo":
+        """bmq_retain_compact_info_get: the running begin / build / swap compaction, or the last one that ended in a swap -- state, who built, sizes,
+        the host clock around each call, and the bytes copied between host and executor while the engine lock was held"""
+        st = _lib.RetainCompactInfo()
+        self._check(_lib.lib().bmq_retain_compact_info_get(self.h, C.byref(st)))
+        return st
+
     def retain_compact_build(self):
-        """bmq_retain_compact_build: loads the snapshot into an index of its own; no engine lock held (matching / add / remove go on)"""
+        """bmq_retain_compact_build: loads the snapshot into an index of its own; no engine lock held (matching / add / remove go on).  With
+        retain_builder = 3 the snapshot lies in executor memory and the executor builder loads it there, on a stream of its own"""
         self._check(_lib.lib().bmq_retain_compact_build(self.h))
         return self
 
     def retain_compact_swap(self) -> Tuple[int, int]:
-        """bmq_retain_compact_swap: upload, replay of what was added / removed meanwhile, swap -> (topics carried over, ops replayed)"""
+        """bmq_retain_compact_swap: upload (retain_builder = 3: an exchange of pointers), replay of what was added / removed meanwhile, swap ->
+        (topics carried over, ops replayed)"""
         carried, replayed = C.c_uint64(), C.c_uint64()
         self._check(_lib.lib().bmq_retain_compact_swap(self.h, C.byref(carried), C.byref(replayed)))
         return int(carried.value), int(replayed.value)

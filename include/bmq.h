@@ -97,7 +97,9 @@ typedef struct bmq_config {
                                /* executor builder (bmq_retain_build_core.h): sorts, scans and CAS inserts as gfx950 kernels on a device engine, the  */
                                /* same functions on host threads on a device = -1 engine; the arrays are built where the walk reads them.  Topic ids, */
                                /* results and every other call are the same either way; bmq_retain_build_info_get says which one built the serving    */
-                               /* generation.  Any other value: BMQ_E_INVAL                                                                          */
+                               /* generation.  3 = 1, and the executor builder also serves the generation change that does not stop the world,       */
+                               /* bmq_retain_compact_begin[_in] / _build / _swap (see there); under 0 and 1 those three stay the host builder's.      */
+                               /* Any other value (2 included: the generation change needs the bulk loader): BMQ_E_INVAL                              */
     uint32_t reserved[1];
 } bmq_config;
 
@@ -856,13 +858,43 @@ int bmq_retain_compact(bmq_engine* e);
  *                              1 GiB (abort and begin again; no mutation is ever refused).
  *   bmq_retain_compact_abort   drops the half-built generation.
  * One compaction call at a time; bmq_retain_rebuild* / bmq_retain_compact are refused (BMQ_E_STATE) between begin and swap / abort.
- * bmq_retain_compact_build always runs the HOST builder, whatever bmq_config.retain_builder says: the snapshot it loads is host strings and
- * the serving generation owns the executor's buffers.  (A device-side snapshot and a second buffer set are what the executor builder makes
- * possible next.) */
+ * Which builder serves them is bmq_config.retain_builder's choice:
+ *   0 (default)  the HOST builder.  _begin copies the live topics to host strings under the lock, _build loads them into a host index, _swap
+ *                uploads its image and re-creates the per-id arrays from host loops under the lock.
+ *   1            as 0: the value moves the bulk loads to the executor, not these three calls (bmq_retain_build_info.builder = 0 after _swap).
+ *   3            the EXECUTOR builder, and the snapshot never leaves the executor.  _begin selects the live ids where the index lives and
+ *                gathers their strings and stamps into a private snapshot in executor memory, on the engine's stream (what crosses to the host
+ *                under the lock is a handful of words); the strings of bulk-loaded ids come from the generation's key store, which _begin
+ *                builds from the host's copy of the load, under the lock, if the generation has none -- a caller that minds calls
+ *                bmq_retain_keys_prepare ahead; a generation made by _swap brings its store along, so only the first round after a
+ *                bmq_retain_rebuild* pays.  _build runs the builder on an executor and stream of its own, reads the snapshot only, copies it
+ *                to the host once for the next catalogue (outside the lock) and lays out the next key store, per-id stamps, dead bitmap and
+ *                empty overlay in executor memory.  _swap exchanges pointers -- no upload, no host loop over the topics, no copy whose size
+ *                grows with the number of topics -- and replays the log.  A live topic of more than 128 levels makes the builder decline:
+ *                _build then runs the host builder over the host copy of the snapshot and _swap is the upload of retain_builder = 0
+ *                (bmq_retain_build_info.builder = 0, fallback = 1); results are the same.
+ * bmq_retain_compact_info_get tells of the running compaction, or of the last one that ended in a swap. */
 int bmq_retain_compact_begin(bmq_engine* e);
 int bmq_retain_compact_build(bmq_engine* e);
 int bmq_retain_compact_swap(bmq_engine* e, uint64_t* out_carried /* may be NULL */, uint64_t* out_replayed /* may be NULL */);
 int bmq_retain_compact_abort(bmq_engine* e);
+typedef struct bmq_retain_compact_info {
+    uint32_t state;             /* 0 = none yet, 1 = begun, 2 = built, 3 = swapped (an abort leaves the last swapped one, or none)              */
+    uint32_t builder;           /* who builds / built the next generation: 0 = host builder, 1 = executor builder (known after _build; until    */
+                                /* then what bmq_config.retain_builder asks for)                                                              */
+    uint32_t fallback;          /* 1 = the executor builder declined (a topic of more than 128 levels) and the host builder ran                  */
+    uint32_t reserved0;
+    uint64_t n_items;           /* topics in the snapshot                                                                                      */
+    uint64_t snapshot_bytes;    /* what the snapshot holds: executor memory (builder 1), or the bytes of its host strings (builder 0)            */
+    uint64_t replayed;          /* logged ops replayed by the swap                                                                             */
+    uint64_t locked_copy_bytes; /* bytes of all host <-> executor copies issued while the engine lock was held in _begin and in _swap before     */
+                                /* the replay (device engines: host <-> device; host-only engines: the same call sites, a memcpy each)          */
+    float begin_ms;             /* host clock around _begin's own work ...                                                                     */
+    float build_ms;             /* ... _build's ...                                                                                            */
+    float swap_ms;              /* ... and _swap's, up to the start of the replay                                                              */
+    uint32_t reserved1;
+} bmq_retain_compact_info;
+int bmq_retain_compact_info_get(const bmq_engine* e, bmq_retain_compact_info* out);
 /* Split and merge of the retain store's base-kv range WITHOUT a KV scan: IKVRangeCoProc.reset(Boundary) fires on every split and merge, and
  * RetainStoreCoProc answers it with load(), a scan of the whole range (RS/RetainStoreCoProc.java:133-137,279-296).  The retained-topic index
  * holds no KV keys, and no id range is a key range (tenants are ranked in byte order, keys sort by tenant length first), so "is
@@ -913,7 +945,7 @@ int bmq_retain_info_get(const bmq_engine* e, bmq_retain_info* out);
  * empty engine, the empty load the first bmq_retain_apply* of a fresh engine starts from).  BMQ_E_STATE: nothing is loaded. */
 typedef struct bmq_retain_build_info {
     uint32_t builder;          /* 0 = the host builder, 1 = the executor builder (bmq_config.retain_builder) built this generation           */
-    uint32_t fallback;         /* 0, or why a retain_builder = 1 engine ran the host builder: 1 = a topic of more than 128 levels            */
+    uint32_t fallback;         /* 0, or why a retain_builder = 1 / 3 engine ran the host builder: 1 = a topic of more than 128 levels        */
     uint64_t n_items;          /* items handed in ...                                                                                       */
     uint64_t n_topics;         /* ... distinct (tenant, topic) pairs among them = topic ids of the load                                      */
     uint64_t n_tenants;
