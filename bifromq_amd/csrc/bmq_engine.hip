@@ -36,6 +36,7 @@
 #include "bmq_retain_build.h"
 #include "bmq_retain_dyn.h"
 #include "bmq_retain_kernels.h"
+#include "bmq_retain_next.h"
 #include "bmq_share.h"
 
 using namespace bmq;
@@ -201,19 +202,13 @@ struct bmq_engine {
         Boundary bound;                           // bmq_retain_compact_begin_in: the next generation keeps the topics whose key lies inside (flags 0: all)
         uint64_t log_bytes = 0;
         bool log_overflow = false;
-        uint64_t n_items = 0; // what bmq_retain_build_info tells of the generation once it serves
         float ms_build = 0;
         // bmq_config.retain_builder = 3: the snapshot stays in exec memory and the next generation is built there, on an executor of its own
         // (rbx on the build stream / rhx), outside the engine lock -- image, key store and mutable part ready for the swap to take over
-        std::unique_ptr<RetainSnapshot<DevExec>> dsnap;
-        std::unique_ptr<RetainSnapshot<HostExec>> hsnap;
-        std::unique_ptr<RetainBuild<DevExec>> ndrb;
-        std::unique_ptr<RetainBuild<HostExec>> nhrb;
-        std::unique_ptr<RetainDyn<DevExec>> ndrt;
-        std::unique_ptr<RetainDyn<HostExec>> nhrt;
+        // (bmq_retain_next.h).  The one of the engine's executor type is in use: with_retain_next; its n_items / fallback tell of a host build too
+        RetainNext<DevExec> on_dev;
+        RetainNext<HostExec> on_host;
         bool exec_snapshot = false; // begin took the snapshot in exec memory (`items` stays empty)
-        bool exec_built = false;    // build left the next generation in exec memory (false after a fallback: `next` holds a host-built one)
-        uint32_t fallback = 0;
         bmq_retain_compact_info ci{}; // bmq_retain_compact_info_get of this compaction
     } rcmp;
     bmq_retain_compact_info rcinfo{}; // ... of the last compaction that ended in a swap
@@ -1271,14 +1266,15 @@ static int replay_log(bmq_engine* e, size_t from) {
     }
     return BMQ_OK;
 }
-// flags / start / end of the boundary arguments -> b; false: a present key without bytes behind it, unknown flag bits, or start >= end
-static bool parse_boundary(uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len, Boundary& b) {
-    if ((flags & ~3u) || ((flags & 1u) && start_len && !start) || ((flags & 2u) && end_len && !end)) return false;
+// flags / start / end of the boundary arguments -> b; refused: a present key without bytes behind it, unknown flag bits, or start >= end
+static int parse_boundary(bmq_engine* e, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len, Boundary& b) {
     b = Boundary{};
     b.flags = flags;
-    if ((flags & 1u) && start_len) b.start.assign((const char*)start, start_len);
-    if ((flags & 2u) && end_len) b.end.assign((const char*)end, end_len);
-    return b.valid();
+    if ((flags & 1u) && start_len && start) b.start.assign((const char*)start, start_len);
+    if ((flags & 2u) && end_len && end) b.end.assign((const char*)end, end_len);
+    if ((flags & ~3u) || ((flags & 1u) && start_len && !start) || ((flags & 2u) && end_len && !end) || !b.valid())
+        return set_err(e, BMQ_E_INVAL, "malformed boundary (start >= end, or a present key without bytes)");
+    return BMQ_OK;
 }
 int bmq_compact_begin(bmq_engine* e) { return bmq_compact_begin_in(e, 0, nullptr, 0, nullptr, 0); }
 int bmq_compact_begin_in(bmq_engine* e, uint8_t flags, const uint8_t* start, uint32_t start_len, const uint8_t* end, uint32_t end_len) {
@@ -1287,7 +1283,7 @@ int bmq_compact_begin_in(bmq_engine* e, uint8_t flags, const uint8_t* start, uin
     std::lock_guard<std::mutex> gc(e->cmp_mu);
     std::lock_guard<std::mutex> g(e->mu);
     Boundary bound;
-    if (!parse_boundary(flags, start, start_len, end, end_len, bound)) return set_err(e, BMQ_E_INVAL, "malformed boundary (start >= end, or a present key without bytes)");
+    if (int rc = parse_boundary(e, flags, start, start_len, end, end_len, bound)) return rc;
     if (int rc = complete_apply(e)) return rc;
     if (e->cmp.active) return set_err(e, BMQ_E_STATE, "a compaction is running: bmq_compact_swap or bmq_compact_abort first");
     if (e->lending) return set_err(e, BMQ_E_STATE, "a bmq_routes_import reads this engine's keys: wait for it to return");
@@ -1459,7 +1455,7 @@ int bmq_routes_count_in(const bmq_engine* ce, uint8_t flags, const uint8_t* star
     if (!e) return BMQ_E_INVAL;
     std::lock_guard<std::mutex> g(e->mu);
     Boundary bound;
-    if (!parse_boundary(flags, start, start_len, end, end_len, bound)) return set_err(e, BMQ_E_INVAL, "malformed boundary (start >= end, or a present key without bytes)");
+    if (int rc = parse_boundary(e, flags, start, start_len, end, end_len, bound)) return rc;
     if (int rc_open = complete_apply(e)) return rc_open; // (a batch handed over with bmq_routes_apply_async first)
     if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
     uint64_t routes = 0, bytes = 0;
@@ -1505,7 +1501,7 @@ int bmq_routes_tenant_stats(const bmq_engine* ce, uint8_t flags, const uint8_t* 
     if (!e) return BMQ_E_INVAL;
     std::lock_guard<std::mutex> g(e->mu);
     Boundary bound;
-    if (!parse_boundary(flags, start, start_len, end, end_len, bound)) return set_err(e, BMQ_E_INVAL, "malformed boundary (start >= end, or a present key without bytes)");
+    if (int rc = parse_boundary(e, flags, start, start_len, end, end_len, bound)) return rc;
     if (int rc_open = complete_apply(e)) return rc_open; // (a batch handed over with bmq_routes_apply_async first)
     if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
     std::vector<std::pair<std::string, std::array<uint64_t, 4>>> rows;
@@ -1644,7 +1640,7 @@ int bmq_routes_import(bmq_engine* dst, bmq_engine* src, uint8_t flags, const uin
     Boundary bound;
     std::unique_lock<std::mutex> g(dst->mu); // (for the error string; released before the import takes its locks one by one)
     if (dst == src) return set_err(dst, BMQ_E_INVAL, "bmq_routes_import: source and destination are the same engine");
-    if (!parse_boundary(flags, start, start_len, end, end_len, bound)) return set_err(dst, BMQ_E_INVAL, "malformed boundary (start >= end, or a present key without bytes)");
+    if (int rc = parse_boundary(dst, flags, start, start_len, end, end_len, bound)) return rc;
     if ((dst->device >= 0) != (src->device >= 0)) return set_err(dst, BMQ_E_INVAL, "bmq_routes_import: a host-executor engine and a device engine");
     if (dst->device != src->device) return set_err(dst, BMQ_E_INVAL, "bmq_routes_import: the engines live on different devices");
     g.unlock();

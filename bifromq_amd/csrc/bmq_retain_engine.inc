@@ -1,21 +1,59 @@
 // bmq_retain_engine.inc -- retain-direction entry points of include/bmq.h (included at the end of bmq_engine.hip).
 namespace {
 
-template <class F> static auto with_retain(bmq_engine* e, F&& f) { return e->drt ? f(*e->drt) : f(*e->hrt); }
+// the engine runs on ONE executor type: f gets the serving mutable part ...
+template <class F> static decltype(auto) with_retain(bmq_engine* e, F&& f) {
+    if (e->drt) return f(*e->drt);
+    return f(*e->hrt);
+}
+// f on the serving mutable part; false: its message is the engine's
+template <class F> static bool retain_try(bmq_engine* e, F&& f) {
+    return with_retain(e, [&](auto& rt) {
+        const bool ok = f(rt);
+        if (!ok) e->err = rt.error;
+        return ok;
+    });
+}
+// ... and, for the generation change: the serving builder (null under bmq_config.retain_builder = 0), the executor the next generation is
+// built on, and what the compaction holds of it
+template <class F> static decltype(auto) with_retain_next(bmq_engine* e, F&& f) {
+    if (e->drt) return f(*e->drt, e->drb.get(), e->rbx, e->rcmp.on_dev);
+    return f(*e->hrt, e->hrb.get(), e->rhx, e->rcmp.on_host);
+}
+static const RetainDynInfo& retain_dyn_info(bmq_engine* e) {
+    return with_retain(e, [](auto& rt) -> const RetainDynInfo& { return rt.info; });
+}
+
+// An image the executor builder left in rb serves from now on: the view the walk reads (the arrays lie where it reads them already); a device
+// engine lets a host-built generation's buffers go
+static RetainIndexView& adopt_exec_image(bmq_engine* e, const RetainBuild<HostExec>& rb) { return rb.view(e->rhview), e->rhview; }
+static RetainIndexView& adopt_exec_image(bmq_engine* e, const RetainBuild<DevExec>& rb) {
+    rb.view(e->rdev.view);
+    for (DevBuf* b : {&e->rdev.nodes, &e->rdev.edges, &e->rdev.posts, &e->rdev.gps, &e->rdev.tenants, &e->rdev.dict, &e->rdev.pool}) b->release();
+    return e->rdev.view;
+}
+
+// the stream the next generation is built on (HostExec has none)
+static int retain_build_stream(bmq_engine*, HostExec&) { return BMQ_OK; }
+static int retain_build_stream(bmq_engine* e, DevExec& bx) {
+    if (!e->s_build) {
+        int least = 0, greatest = 0;
+        HIPCHK(e, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIPCHK(e, hipStreamCreateWithPriority(&e->s_build, hipStreamNonBlocking, least)); // a match batch's waves go first
+        HIPCHK(e, hipEventCreateWithFlags(&e->ev_serving, hipEventDisableTiming));
+    }
+    bx.stream = e->s_build;
+    return BMQ_OK;
+}
 
 int upload_retain(bmq_engine* e) {
     RetainIndexHost& h = e->rhost;
-    if (e->rb_serving) { // built by the executor builder (bmq_retain_build.h): the arrays lie where the walk reads them already, rhost is the catalogue
-        if (e->device < 0) {
-            e->hrb->view(e->rhview);
-            if (!e->hrt->reset(e->rhview, h)) return set_err(e, BMQ_E_NOMEM, e->hrt->error);
-            return BMQ_OK;
-        }
-        HIPCHK(e, hipSetDevice(e->device));
-        e->drb->view(e->rdev.view);
-        for (DevBuf* b : {&e->rdev.nodes, &e->rdev.edges, &e->rdev.posts, &e->rdev.gps, &e->rdev.tenants, &e->rdev.dict, &e->rdev.pool}) b->release(); // (a host-built generation's)
-        if (!e->drt->reset(e->rdev.view, h)) return set_err(e, e->dx.err.empty() ? BMQ_E_NOMEM : BMQ_E_HIP, e->drt->error);
-        return BMQ_OK;
+    if (e->rb_serving) { // built by the executor builder (bmq_retain_build.h): rhost is the catalogue
+        if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
+        return with_retain_next(e, [&](auto& rt, auto* rb, auto&, auto&) {
+            if (!rt.reset(adopt_exec_image(e, *rb), h)) return set_err(e, e->device < 0 || e->dx.err.empty() ? BMQ_E_NOMEM : BMQ_E_HIP, rt.error);
+            return (int)BMQ_OK;
+        });
     }
     if (e->device < 0) { // host-only engine: the bulk-loaded arrays stay where the host builder keeps them
         RetainIndexView& v = e->rhview;
@@ -104,48 +142,29 @@ int retain_load_host(bmq_engine* e, std::vector<RetainIndexHost::Item>&& items, 
 int retain_load_exec(bmq_engine* e, const RbInput& in, bool* too_deep) {
     *too_deep = false;
     if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
-    const bool ok = e->drb ? e->drb->build(in) : e->hrb->build(in);
-    if (!ok) {
-        if (e->drb ? e->drb->too_deep : e->hrb->too_deep) {
+    return with_retain_next(e, [&](auto&, auto* rb, auto&, auto&) {
+        if (!rb->build(in)) {
+            if (!rb->too_deep) return set_err(e, retain_rc(rb->error), rb->error);
             *too_deep = true;
-            return BMQ_OK;
+            return (int)BMQ_OK;
         }
-        const std::string& msg = e->drb ? e->drb->error : e->hrb->error;
-        return set_err(e, msg.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : (msg.find("too many") != std::string::npos ? BMQ_E_INVAL : BMQ_E_HIP), msg);
-    }
-    if (e->drb) retain_catalogue(e->rhost, in, *e->drb);
-    else retain_catalogue(e->rhost, in, *e->hrb);
-    e->rb_serving = true;
-    const int rc = retain_publish(e);
-    e->rbinfo = e->drb ? e->drb->info : e->hrb->info;
-    return rc;
+        retain_catalogue(e->rhost, in, *rb);
+        e->rb_serving = true;
+        const int rc = retain_publish(e);
+        e->rbinfo = rb->info;
+        return rc;
+    });
 }
 
 // a bulk load of host strings (bmq_retain_compact, bmq_retain_import into an empty engine) with the configured builder
 int retain_load_items(bmq_engine* e, std::vector<RetainIndexHost::Item>&& items) {
     if (!e->drb && !e->hrb) return retain_load_host(e, std::move(items), 0);
-    std::vector<uint8_t> tb, pb;
-    std::vector<uint32_t> toff{0}, poff{0}, it_tenant, ex;
-    std::vector<uint64_t> ts;
-    std::unordered_map<std::string, uint32_t> tix;
-    for (const auto& it : items) {
-        auto f = tix.find(it.tenant);
-        if (f == tix.end()) {
-            f = tix.emplace(it.tenant, (uint32_t)tix.size()).first;
-            tb.insert(tb.end(), it.tenant.begin(), it.tenant.end());
-            toff.push_back((uint32_t)tb.size());
-        }
-        it_tenant.push_back(f->second);
-        pb.insert(pb.end(), it.topic.begin(), it.topic.end());
-        if (pb.size() >= 0xFFFFFFF0ull) return set_err(e, BMQ_E_RANGE, "the topics of the load exceed 4 GiB");
-        poff.push_back((uint32_t)pb.size());
-        ts.push_back(it.has_ts ? it.ts : 0ull);
-        ex.push_back(it.has_ts ? it.expiry : 0xFFFFFFFFu);
-    }
-    tb.resize(tb.size() + 16, 0), pb.resize(pb.size() + 16, 0);
-    const RbInput in{tb.data(), toff.data(), (uint32_t)tix.size(), it_tenant.data(), pb.data(), poff.data(), (uint32_t)items.size(), ts.data(), ex.data()};
+    PackedTopics P;
+    for (const auto& it : items)
+        if (!P.add(it.tenant, it.topic, it.has_ts, it.ts, it.expiry)) return set_err(e, BMQ_E_RANGE, "the topics of the load exceed 4 GiB");
+    P.pad();
     bool too_deep = false;
-    const int rc = retain_load_exec(e, in, &too_deep);
+    const int rc = retain_load_exec(e, P.rb_input(), &too_deep);
     if (!too_deep) return rc;
     return retain_load_host(e, std::move(items), 1);
 }
@@ -408,21 +427,7 @@ int bmq_retain_rebuild_ex(bmq_engine* e, const uint8_t* tenants, const uint32_t*
         if (!too_deep) return rc;
         fallback = 1;
     }
-    std::vector<RetainIndexHost::Item> items;
-    items.reserve(n_topics);
-    for (uint32_t i = 0; i < n_topics; i++) {
-        const uint32_t ti = topic_tenant[i];
-        RetainIndexHost::Item it;
-        it.tenant.assign((const char*)tenants + tenant_off[ti], tenant_off[ti + 1] - tenant_off[ti]);
-        it.topic.assign((const char*)topics + topic_off[i], topic_off[i + 1] - topic_off[i]);
-        if (timestamp_hlc) {
-            it.has_ts = true;
-            it.ts = timestamp_hlc[i];
-            it.expiry = expiry_seconds[i];
-        }
-        items.push_back(std::move(it));
-    }
-    return retain_load_host(e, std::move(items), fallback);
+    return retain_load_host(e, PackedTopics::items(n_topics, PackedTopics::by_table(tenants, tenant_off, topic_tenant, topics, topic_off), timestamp_hlc, expiry_seconds), fallback);
 }
 
 int bmq_retain_rebuild(bmq_engine* e, const uint8_t* tenants, const uint32_t* tenant_off, uint32_t n_tenants,
@@ -430,6 +435,17 @@ int bmq_retain_rebuild(bmq_engine* e, const uint8_t* tenants, const uint32_t* te
     return bmq_retain_rebuild_ex(e, tenants, tenant_off, n_tenants, topic_tenant, topics, topic_off, n_topics, nullptr, nullptr);
 }
 
+// ops the serving generation has taken enter the log of the compaction that runs beside it (under e->mu)
+static void retain_log(bmq_engine::RetainCompaction& c, std::vector<bmq_engine::RetainCompaction::Op>& ops) {
+    for (auto& o : ops) {
+        c.log_bytes += o.tenant.size() + o.topic.size() + 48;
+        c.log.push_back(std::move(o));
+    }
+    if (c.log_bytes > (1ull << 30)) { // (what gives way is the compaction, never the mutation)
+        c.log_overflow = true;
+        c.log.clear(), c.log.shrink_to_fit();
+    }
+}
 // IRetainTopicIndex.add / remove for a batch of (tenant, topic) pairs: three kernels on the engine stream (locate, commit, rank:
 // bmq_retain_core.h), behind whatever match batch is in flight and in front of every later one.  Ids are stable: a removed topic's id
 // goes dead, a re-added one gets its id back, a new topic gets the next unused id.
@@ -451,30 +467,16 @@ static int retain_apply_common(bmq_engine* e, const uint8_t* tenants, const uint
         const int rc = retain_load_host(e, {}, 0); // (nothing to build: the host builder, whatever bmq_config.retain_builder says)
         if (rc) return rc;
     }
-    const bool ok = with_retain(e, [&](auto& rt) {
-        const bool r = rt.apply(tenants, tenant_off, n_tenants, op_tenant, topics, topic_off, op, (const unsigned long long*)timestamp_hlc, expiry_seconds, n, out_ids);
-        if (!r) e->err = rt.error;
-        return r;
-    });
-    if (!ok) return set_err(e, e->err.find("malformed") != std::string::npos ? BMQ_E_INVAL : (e->err.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : BMQ_E_HIP), e->err);
+    const bool ok = retain_try(e, [&](auto& rt) { return rt.apply(tenants, tenant_off, n_tenants, op_tenant, topics, topic_off, op, (const unsigned long long*)timestamp_hlc, expiry_seconds, n, out_ids); });
+    if (!ok) return set_err(e, retain_rc(e->err), e->err);
     if (e->rcmp.active && !e->rcmp.log_overflow) { // a generation is being built beside this one: it gets the ops too, before the swap
-        bmq_engine::RetainCompaction& c = e->rcmp;
+        std::vector<bmq_engine::RetainCompaction::Op> ops(n);
         for (uint32_t i = 0; i < n; i++) {
             const uint32_t ti = op_tenant ? op_tenant[i] : 0u;
-            bmq_engine::RetainCompaction::Op o;
-            o.tenant.assign((const char*)tenants + tenant_off[ti], tenant_off[ti + 1] - tenant_off[ti]);
-            o.topic.assign((const char*)topics + topic_off[i], topic_off[i + 1] - topic_off[i]);
-            o.op = op[i];
-            o.has_ts = timestamp_hlc != nullptr;
-            o.ts = timestamp_hlc ? timestamp_hlc[i] : 0ull;
-            o.expiry = expiry_seconds ? expiry_seconds[i] : 0xFFFFFFFFu;
-            c.log_bytes += o.tenant.size() + o.topic.size() + 48;
-            c.log.push_back(std::move(o));
+            ops[i] = {std::string((const char*)tenants + tenant_off[ti], tenant_off[ti + 1] - tenant_off[ti]), std::string((const char*)topics + topic_off[i], topic_off[i + 1] - topic_off[i]),
+                      op[i], timestamp_hlc != nullptr, timestamp_hlc ? timestamp_hlc[i] : 0ull, expiry_seconds ? expiry_seconds[i] : 0xFFFFFFFFu};
         }
-        if (c.log_bytes > (1ull << 30)) { // (what gives way is the compaction, never the mutation)
-            c.log_overflow = true;
-            c.log.clear(), c.log.shrink_to_fit();
-        }
+        retain_log(e->rcmp, ops);
     }
     e->repoch++;
     return BMQ_OK;
@@ -526,7 +528,7 @@ int bmq_retain_info_get(const bmq_engine* ce, bmq_retain_info* out) {
     out->epoch = e->repoch;
     out->generation = e->rgeneration;
     if (!e->rbuilt) return BMQ_OK;
-    const RetainDynInfo& in = e->drt ? e->drt->info : e->hrt->info;
+    const RetainDynInfo& in = retain_dyn_info(e);
     out->n_topics = in.n_live;
     out->id_bound = in.id_bound;
     out->loaded_topics = in.base_n;
@@ -570,7 +572,7 @@ int bmq_retain_find_all(const bmq_engine* ce, uint64_t* out_n_topics, uint64_t* 
     std::unique_lock<std::recursive_mutex> api_lock;
     if (e) api_lock = std::unique_lock<std::recursive_mutex>(e->api);
     if (!e || !out_n_topics) return BMQ_E_INVAL;
-    *out_n_topics = e->rbuilt ? (e->drt ? e->drt->info.n_live : e->hrt->info.n_live) : 0;
+    *out_n_topics = e->rbuilt ? retain_dyn_info(e).n_live : 0;
     if (out_epoch) *out_epoch = e->repoch;
     return BMQ_OK;
 }
@@ -593,11 +595,7 @@ static int retain_select(bmq_engine* e, const uint8_t* tenant, uint32_t tenant_l
         q.t_node = NONE;
     }
     std::vector<uint32_t> ids;
-    const bool ok = with_retain(e, [&](auto& rt) {
-        const bool r = rt.select(q, tenant, tenant_len, ids);
-        if (!r) e->err = rt.error;
-        return r;
-    });
+    const bool ok = retain_try(e, [&](auto& rt) { return rt.select(q, tenant, tenant_len, ids); });
     if (!ok) return set_err(e, BMQ_E_HIP, e->err);
     *out_n = (uint32_t)ids.size();
     for (size_t i = 0; i < ids.size() && i < cap && out_ids; i++) out_ids[i] = ids[i];
@@ -640,7 +638,7 @@ static int retain_topics_locked(bmq_engine* e, const uint32_t* ids, uint32_t n, 
     bytes.clear();
     if (!e->rbuilt) return BMQ_OK;
     if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
-    const uint64_t base_n = e->drt ? e->drt->info.base_n : e->hrt->info.base_n;
+    const uint64_t base_n = retain_dyn_info(e).base_n;
     std::vector<uint32_t> ov_ids, ov_pos;
     for (uint32_t i = 0; i < n; i++)
         if (ids[i] >= base_n) {
@@ -650,11 +648,7 @@ static int retain_topics_locked(bmq_engine* e, const uint32_t* ids, uint32_t n, 
     std::vector<uint32_t> lens;
     std::vector<uint8_t> ov_bytes;
     if (!ov_ids.empty()) {
-        const bool ok = with_retain(e, [&](auto& rt) {
-            const bool r = rt.overlay_topics(ov_ids.data(), (uint32_t)ov_ids.size(), lens, ov_bytes);
-            if (!r) e->err = rt.error;
-            return r;
-        });
+        const bool ok = retain_try(e, [&](auto& rt) { return rt.overlay_topics(ov_ids.data(), (uint32_t)ov_ids.size(), lens, ov_bytes); });
         if (!ok) return set_err(e, BMQ_E_HIP, e->err);
     }
     size_t k = 0, ov_off = 0;
@@ -718,11 +712,7 @@ int bmq_retain_topic(const bmq_engine* ce, uint32_t topic_id, uint8_t* out, uint
 
 // liveness of ids: the dead bitmap over the ids handed out (a bit per id: 128 KB per million ids), one copy
 static int retain_dead_words_locked(bmq_engine* e, std::vector<unsigned long long>& words) {
-    const bool ok = with_retain(e, [&](auto& rt) {
-        const bool r = rt.dead_words(words);
-        if (!r) e->err = rt.error;
-        return r;
-    });
+    const bool ok = retain_try(e, [&](auto& rt) { return rt.dead_words(words); });
     return ok ? BMQ_OK : set_err(e, BMQ_E_HIP, e->err);
 }
 
@@ -737,7 +727,7 @@ int bmq_retain_message_keys(const bmq_engine* ce, const uint32_t* topic_ids, uin
     if (e->rbuilt && n) {
         std::vector<unsigned long long> dead;
         if (int rc = retain_dead_words_locked(e, dead)) return rc;
-        const uint64_t bound = e->drt ? e->drt->info.id_bound : e->hrt->info.id_bound;
+        const uint64_t bound = retain_dyn_info(e).id_bound;
         std::vector<uint32_t> live; // (positions keep their order: the keys are composed id for id below)
         for (uint32_t i = 0; i < n; i++)
             if (topic_ids[i] < bound && !((dead[topic_ids[i] >> 6] >> (topic_ids[i] & 63u)) & 1ull)) live.push_back(topic_ids[i]);
@@ -771,7 +761,7 @@ int bmq_retain_remove_ids(bmq_engine* e, const uint32_t* topic_ids, uint32_t n, 
     std::lock_guard<std::mutex> g(e->mu);
     if (out_removed) *out_removed = 0;
     if (!e->rbuilt || generation != e->rgeneration) return set_err(e, BMQ_E_STATE, "the topic ids belong to another generation of the retained-topic index");
-    const uint64_t bound = e->drt ? e->drt->info.id_bound : e->hrt->info.id_bound;
+    const uint64_t bound = retain_dyn_info(e).id_bound;
     for (uint32_t i = 0; i < n; i++) // nothing is changed by a call that holds an id nobody handed out
         if (topic_ids[i] >= bound) return set_err(e, BMQ_E_INVAL, "topic id out of range (>= bmq_retain_info.id_bound)");
     if (n == 0) return BMQ_OK;
@@ -779,7 +769,6 @@ int bmq_retain_remove_ids(bmq_engine* e, const uint32_t* topic_ids, uint32_t n, 
     // a generation is being built beside this one: it gets the removals as remove ops of the topics.  The ops are made ready here (the ids
     // that are live now, once each, with their strings) and enter the log only after the removal has succeeded, as in retain_apply_common
     std::vector<bmq_engine::RetainCompaction::Op> log_ops;
-    uint64_t log_ops_bytes = 0;
     if (e->rcmp.active && !e->rcmp.log_overflow) {
         std::vector<unsigned long long> dead;
         if (int rc = retain_dead_words_locked(e, dead)) return rc;
@@ -794,34 +783,14 @@ int bmq_retain_remove_ids(bmq_engine* e, const uint32_t* topic_ids, uint32_t n, 
         std::vector<uint64_t> off;
         std::vector<uint32_t> tlen;
         if (int rc = retain_topics_locked(e, live.data(), (uint32_t)live.size(), bytes, off, tlen)) return rc;
-        for (size_t i = 0; i < live.size(); i++) {
-            bmq_engine::RetainCompaction::Op o;
-            o.tenant.assign((const char*)bytes.data() + off[i], tlen[i]);
-            o.topic.assign((const char*)bytes.data() + off[i] + tlen[i], (size_t)(off[i + 1] - off[i]) - tlen[i]);
-            o.op = 1;
-            o.has_ts = false;
-            o.ts = 0ull;
-            o.expiry = 0xFFFFFFFFu;
-            log_ops_bytes += o.tenant.size() + o.topic.size() + 48;
-            log_ops.push_back(std::move(o));
-        }
+        for (size_t i = 0; i < live.size(); i++)
+            log_ops.push_back({std::string((const char*)bytes.data() + off[i], tlen[i]), std::string((const char*)bytes.data() + off[i] + tlen[i], (size_t)(off[i + 1] - off[i]) - tlen[i]), 1, false, 0ull,
+                               0xFFFFFFFFu});
     }
     uint64_t removed = 0;
-    const bool ok = with_retain(e, [&](auto& rt) {
-        const bool r = rt.remove_ids(topic_ids, n, removed);
-        if (!r) e->err = rt.error;
-        return r;
-    });
-    if (!ok) return set_err(e, e->err.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : BMQ_E_HIP, e->err);
-    if (e->rcmp.active && !e->rcmp.log_overflow) {
-        bmq_engine::RetainCompaction& c = e->rcmp;
-        c.log_bytes += log_ops_bytes;
-        for (auto& o : log_ops) c.log.push_back(std::move(o));
-        if (c.log_bytes > (1ull << 30)) { // (what gives way is the compaction, never the mutation)
-            c.log_overflow = true;
-            c.log.clear(), c.log.shrink_to_fit();
-        }
-    }
+    const bool ok = retain_try(e, [&](auto& rt) { return rt.remove_ids(topic_ids, n, removed); });
+    if (!ok) return set_err(e, retain_rc(e->err), e->err);
+    if (e->rcmp.active && !e->rcmp.log_overflow) retain_log(e->rcmp, log_ops);
     if (out_removed) *out_removed = removed;
     e->repoch++;
     return BMQ_OK;
@@ -843,11 +812,7 @@ int bmq_retain_tenant_counts(const bmq_engine* ce, uint8_t* out_tenants, uint64_
             ranges.push_back(t->id_base + (uint32_t)t->topics.size());
         }
         std::vector<std::pair<std::string, uint64_t>> ov;
-        const bool ok = with_retain(e, [&](auto& rt) {
-            const bool r = rt.tenant_counts(ranges, bulk_live, ov);
-            if (!r) e->err = rt.error;
-            return r;
-        });
+        const bool ok = retain_try(e, [&](auto& rt) { return rt.tenant_counts(ranges, bulk_live, ov); });
         if (!ok) return set_err(e, BMQ_E_HIP, e->err);
         for (size_t i = 0; i < e->rhost.order.size(); i++)
             if (bulk_live[i]) merged[e->rhost.order[i]->name] += bulk_live[i];
@@ -869,13 +834,11 @@ static int retain_boundary_locked(bmq_engine* e, const Boundary& b, uint64_t& to
     if (ids) ids->clear();
     if (!e->rbuilt) return BMQ_OK;
     if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
-    const bool ok = with_retain(e, [&](auto& rt) {
-        const bool r = rt.boundary_select(e->rhost, b.flags, (const uint8_t*)b.start.data(), (uint32_t)b.start.size(), (const uint8_t*)b.end.data(), (uint32_t)b.end.size(),
-                                          topics, key_bytes, ids);
-        if (!r) e->err = rt.error;
-        return r;
+    const bool ok = retain_try(e, [&](auto& rt) {
+        return rt.boundary_select(e->rhost, b.flags, (const uint8_t*)b.start.data(), (uint32_t)b.start.size(), (const uint8_t*)b.end.data(), (uint32_t)b.end.size(),
+                                  topics, key_bytes, ids);
     });
-    if (!ok) return set_err(e, e->err.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : BMQ_E_HIP, e->err);
+    if (!ok) return set_err(e, retain_rc(e->err), e->err);
     return BMQ_OK;
 }
 
@@ -890,25 +853,14 @@ static int retain_live_items_locked(bmq_engine* e, std::vector<RetainIndexHost::
     GcQuery q{};
     q.live_only = 1;
     q.override_expiry = -1;
-    const bool ok = with_retain(e, [&](auto& rt) {
-        const bool r = (bound.bounded() || rt.select(q, nullptr, 0, ids)) && rt.payload(ts, ex);
-        if (!r) e->err = rt.error;
-        return r;
-    });
+    const bool ok = retain_try(e, [&](auto& rt) { return (bound.bounded() || rt.select(q, nullptr, 0, ids)) && rt.payload(ts, ex); });
     if (!ok) return set_err(e, BMQ_E_HIP, e->err);
     std::vector<uint8_t> bytes;
     std::vector<uint64_t> off;
     std::vector<uint32_t> tlen;
     int rc = retain_topics_locked(e, ids.data(), (uint32_t)ids.size(), bytes, off, tlen);
     if (rc) return rc;
-    items.assign(ids.size(), RetainIndexHost::Item{});
-    for (size_t i = 0; i < ids.size(); i++) {
-        items[i].tenant.assign((const char*)bytes.data() + off[i], tlen[i]);
-        items[i].topic.assign((const char*)bytes.data() + off[i] + tlen[i], (size_t)(off[i + 1] - off[i]) - tlen[i]);
-        items[i].ts = ts[ids[i]];
-        items[i].expiry = ex[ids[i]];
-        items[i].has_ts = !(items[i].ts == 0 && items[i].expiry == 0xFFFFFFFFu);
-    }
+    items = PackedTopics::items(ids.size(), PackedTopics::by_prefix(bytes.data(), off.data(), tlen.data()), (const uint64_t*)ts.data(), ex.data(), ids.data());
     return BMQ_OK;
 }
 
@@ -919,11 +871,12 @@ static int retain_live_items_locked(bmq_engine* e, std::vector<RetainIndexHost::
 // load out of the lock:  begin = snapshot of the live topics (tens of ms under the lock); build = the load into an index of its own, no
 // lock held, matching and bmq_retain_apply* go on (what they change is logged); swap = upload + replay of the log under the lock.
 // With bmq_config.retain_builder = 3 (under 1 the three calls stay as they are) the snapshot is gathered where the index lives and stays there (RetainDyn::snapshot), build runs the
-// executor builder on an executor of its own and makes the next mutable part ready (retain_build_next), swap exchanges pointers: what the
-// two holds of the lock copy between host and executor is a handful of words (bmq_retain_compact_info.locked_copy_bytes).
+// executor builder on an executor of its own and makes the next mutable part ready (retain_build_next in bmq_retain_next.h, which knows no engine: tools/retain_snapshot_check.cpp runs that very
+// function under the sanitizers), swap exchanges pointers: what the two holds of the lock copy between host and executor is a handful of words
+// (bmq_retain_compact_info.locked_copy_bytes).  One body per call: the executor type comes in through with_retain_next.
 int bmq_retain_compact_begin(bmq_engine* e) { return bmq_retain_compact_begin_in(e, 0, nullptr, 0, nullptr, 0); }
 // bytes of host <-> exec copies the retain direction has issued so far (RetainDyn::copied + the image uploads): under e->mu
-static uint64_t retain_copy_meter(bmq_engine* e) { return (e->drt ? e->drt->copied : e->hrt->copied) + e->r_up_bytes; }
+static uint64_t retain_copy_meter(bmq_engine* e) { return with_retain(e, [](auto& rt) { return rt.copied; }) + e->r_up_bytes; }
 static float ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 // ... for a range that SHRINKS (RetainStoreCoProc.reset(Boundary) after a split): the snapshot takes only the topics whose key lies inside
 // the boundary, and the swap replays only the logged ops whose key does.  The serving generation matches and mutates over all its topics
@@ -934,7 +887,7 @@ int bmq_retain_compact_begin_in(bmq_engine* e, uint8_t flags, const uint8_t* sta
     std::lock_guard<std::mutex> gc(e->cmp_mu);
     std::lock_guard<std::mutex> g(e->mu);
     Boundary bound;
-    if (!parse_boundary(flags, start, start_len, end, end_len, bound)) return set_err(e, BMQ_E_INVAL, "malformed boundary (start >= end, or a present key without bytes)");
+    if (int rc = parse_boundary(e, flags, start, start_len, end, end_len, bound)) return rc;
     if (e->rcmp.active) return set_err(e, BMQ_E_STATE, "a retain compaction is running: bmq_retain_compact_swap or bmq_retain_compact_abort first");
     if (!e->rbuilt) return set_err(e, BMQ_E_STATE, "no retained-topic index");
     if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
@@ -944,31 +897,20 @@ int bmq_retain_compact_begin_in(bmq_engine* e, uint8_t flags, const uint8_t* sta
     bmq_engine::RetainCompaction& c = e->rcmp;
     c.bound = bound;
     if (e->rb_generation) { // bmq_config.retain_builder = 3: ids, strings and stamps are gathered where the index lives and stay there
-        if (e->drb && !e->s_build) {
-            int least = 0, greatest = 0;
-            HIPCHK(e, hipDeviceGetStreamPriorityRange(&least, &greatest));
-            HIPCHK(e, hipStreamCreateWithPriority(&e->s_build, hipStreamNonBlocking, least)); // a match batch's waves go first
-            HIPCHK(e, hipEventCreateWithFlags(&e->ev_serving, hipEventDisableTiming));
-        }
-        e->rbx.stream = e->s_build;
-        bool ok;
-        if (e->drb) {
-            c.dsnap = std::make_unique<RetainSnapshot<DevExec>>(e->dx);
-            ok = e->drt->snapshot(e->rhost, bound.flags, (const uint8_t*)bound.start.data(), (uint32_t)bound.start.size(), (const uint8_t*)bound.end.data(), (uint32_t)bound.end.size(), *c.dsnap);
-            if (!ok) e->err = e->drt->error;
-        } else {
-            c.hsnap = std::make_unique<RetainSnapshot<HostExec>>(e->hx);
-            ok = e->hrt->snapshot(e->rhost, bound.flags, (const uint8_t*)bound.start.data(), (uint32_t)bound.start.size(), (const uint8_t*)bound.end.data(), (uint32_t)bound.end.size(), *c.hsnap);
-            if (!ok) e->err = e->hrt->error;
-        }
-        if (!ok) {
-            const std::string msg = e->err;
-            e->rcmp = bmq_engine::RetainCompaction{};
-            return set_err(e, msg.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : (msg.find("exceed") != std::string::npos ? BMQ_E_RANGE : BMQ_E_HIP), msg);
-        }
+        const int rc = with_retain_next(e, [&](auto& rt, auto*, auto& bx, auto& nx) {
+            if (int rc = retain_build_stream(e, bx)) return rc;
+            nx.snap = std::make_unique<std::decay_t<decltype(*nx.snap)>>(rt.x);
+            if (!rt.snapshot(e->rhost, bound.flags, (const uint8_t*)bound.start.data(), (uint32_t)bound.start.size(), (const uint8_t*)bound.end.data(), (uint32_t)bound.end.size(), *nx.snap)) {
+                const std::string msg = rt.error;
+                e->rcmp = bmq_engine::RetainCompaction{};
+                return set_err(e, retain_rc(msg), msg);
+            }
+            c.ci.n_items = nx.snap->s.n;
+            c.ci.snapshot_bytes = nx.snap->bytes;
+            return (int)BMQ_OK;
+        });
+        if (rc) return rc;
         c.exec_snapshot = true;
-        c.ci.n_items = c.dsnap ? c.dsnap->s.n : c.hsnap->s.n;
-        c.ci.snapshot_bytes = c.dsnap ? c.dsnap->bytes : c.hsnap->bytes;
         c.ci.builder = 1;
     } else {
         if (int rc = retain_live_items_locked(e, c.items, bound)) return rc;
@@ -982,68 +924,32 @@ int bmq_retain_compact_begin_in(bmq_engine* e, uint8_t flags, const uint8_t* sta
     return BMQ_OK;
 }
 
-// bmq_retain_compact_build with the executor builder: the next image from the snapshot, the next catalogue from ONE copy of the snapshot to the
-// host, the next mutable part ready in exec memory.  Runs on bx (its own stream); no engine lock.  *msg: why it failed (rc != BMQ_OK).
 extern "C++" {
-template <class Exec>
-static int retain_build_next(bmq_engine::RetainCompaction& c, Exec& bx, RetainSnapshot<Exec>& snap, std::unique_ptr<RetainBuild<Exec>>& nrb, std::unique_ptr<RetainDyn<Exec>>& nrt, bool tiny,
-                             std::string& msg) {
-    const RsSnap& S = snap.s;
-    // the tenant table is small: the builder de-duplicates and byte-sorts it on the host
-    std::vector<uint8_t> tb;
-    std::vector<uint32_t> toff((size_t)S.n_tenants + 1, 0);
-    if (!bx.copy_out(toff.data(), S.tenant_off, 4 * toff.size())) return msg = bx.err, BMQ_E_HIP;
-    tb.resize((size_t)toff[S.n_tenants] + 16, 0);
-    if (!bx.copy_out(tb.data(), S.tenants, toff[S.n_tenants])) return msg = bx.err, BMQ_E_HIP;
-    RbInput in{tb.data(), toff.data(), S.n_tenants, S.item_tenant, S.topics, S.topic_off, S.n, nullptr, nullptr};
-    in.in_exec = true;
-    in.topic_bytes = snap.topic_bytes;
-    nrb = std::make_unique<RetainBuild<Exec>>(bx);
-    nrb->keep_perm = true;
-    const bool built = nrb->build(in);
-    if (!built && !nrb->too_deep) {
-        msg = nrb->error;
-        return msg.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : (msg.find("too many") != std::string::npos ? BMQ_E_INVAL : BMQ_E_HIP);
+static uint8_t retain_op_of(const bmq_engine::RetainCompaction::Op& o) { return o.op; }
+static uint8_t retain_op_of(const RetainIndexHost::Item&) { return 0; } // (an item is an add)
+// Logged ops / items through the ordinary apply path, 65 536 at a time.  around(n, apply) runs each chunk of n: it calls apply() and hands its
+// result on.  Stamps go with a chunk if one of its entries has some, or with every chunk (always_stamps).
+template <class T, class Around> static int retain_apply_chunked(bmq_engine* e, const std::vector<T>& v, bool always_stamps, Around&& around) {
+    for (size_t lo = 0; lo < v.size();) {
+        const size_t hi = std::min(v.size(), lo + 65536);
+        PackedTopics P;
+        for (size_t i = lo; i < hi; i++)
+            if (!P.add(v[i].tenant, v[i].topic, v[i].has_ts, v[i].ts, v[i].expiry, retain_op_of(v[i]))) return set_err(e, BMQ_E_RANGE, "the topics of the batch exceed 4 GiB");
+        P.pad();
+        const bool stamps = always_stamps || P.any_ts;
+        const int rc = around((uint32_t)(hi - lo), [&] {
+            return retain_apply_common(e, P.tenants.data(), P.tenant_off.data(), P.n_tenants(), P.item_tenant.data(), P.topics.data(), P.topic_off.data(), P.op.data(),
+                                       stamps ? P.ts.data() : nullptr, stamps ? P.expiry.data() : nullptr, P.n(), nullptr);
+        });
+        if (rc) return rc;
+        lo = hi;
     }
-    // the packed snapshot on the host, once: what the catalogue's strings and stamps are cut from (or what the host builder loads)
-    std::vector<uint8_t> pb((size_t)snap.topic_bytes + 16, 0);
-    std::vector<uint32_t> poff((size_t)S.n + 1, 0), it_tenant(S.n), ex(S.n);
-    std::vector<uint64_t> ts(S.n);
-    if (!bx.copy_out(pb.data(), S.topics, snap.topic_bytes) || !bx.copy_out(poff.data(), S.topic_off, 4 * poff.size()) || !bx.copy_out(ts.data(), S.ts, 8 * (size_t)S.n) ||
-        !bx.copy_out(ex.data(), S.expiry, 4 * (size_t)S.n) || (!built && !bx.copy_out(it_tenant.data(), S.item_tenant, 4 * (size_t)S.n)))
-        return msg = bx.err, BMQ_E_HIP;
-    if (!built) { // declined: a topic of more than RB_MAX_DEPTH levels.  The host builder over the same items; the swap is then an upload
-        nrb.reset();
-        std::vector<RetainIndexHost::Item> items(S.n);
-        for (uint32_t i = 0; i < S.n; i++) {
-            const uint32_t t = it_tenant[i];
-            items[i].tenant.assign((const char*)tb.data() + toff[t], toff[t + 1] - toff[t]);
-            items[i].topic.assign((const char*)pb.data() + poff[i], poff[i + 1] - poff[i]);
-            items[i].ts = ts[i];
-            items[i].expiry = ex[i];
-            items[i].has_ts = !(ts[i] == 0 && ex[i] == 0xFFFFFFFFu);
-        }
-        if (!c.next.rebuild(std::move(items))) return msg = c.next.error, BMQ_E_INVAL;
-        c.fallback = 1;
-        c.exec_built = false;
-        return BMQ_OK;
-    }
-    in.in_exec = false;
-    in.item_tenant = nullptr; // (retain_catalogue reads topics, offsets and stamps)
-    in.topics = pb.data(), in.topic_off = poff.data(), in.ts = ts.data(), in.expiry = ex.data();
-    retain_catalogue(c.next, in, *nrb);
-    nrt = std::make_unique<RetainDyn<Exec>>(bx);
-    nrt->tiny = tiny;
-    if (!nrt->reset_exec(S, nrb->d_perm, (uint32_t)nrb->info.n_topics, nrb->names, nrb->t_begin)) {
-        msg = nrt->error;
-        return msg.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : BMQ_E_HIP;
-    }
-    nrb->drop_perm();
-    c.exec_built = true;
     return BMQ_OK;
 }
 } // extern "C++"
 
+// bmq_retain_compact_build under bmq_config.retain_builder = 3 is retain_build_next (bmq_retain_next.h) on rbx (its own stream) / rhx: no engine
+// lock.  tools/retain_snapshot_check.cpp runs the same function under the sanitizers.
 int bmq_retain_compact_build(bmq_engine* e) {
     if (!e) return BMQ_E_INVAL;
     std::lock_guard<std::mutex> gc(e->cmp_mu); // (one compaction call at a time; the engine lock is NOT held: this is the long part)
@@ -1053,36 +959,29 @@ int bmq_retain_compact_build(bmq_engine* e) {
         std::lock_guard<std::mutex> g(e->mu);
         if (!c.active) return set_err(e, BMQ_E_STATE, "no retain compaction is running");
         if (c.built) return BMQ_OK;
-        tiny = e->drt ? e->drt->tiny : e->hrt->tiny;
+        tiny = with_retain(e, [](auto& rt) { return rt.tiny; });
     }
     const auto t0 = std::chrono::steady_clock::now();
-    if (c.exec_snapshot) {
-        std::string msg;
-        int rc;
-        if (c.dsnap) {
-            if (hipSetDevice(e->device) != hipSuccess) rc = BMQ_E_HIP, msg = "hipSetDevice failed";
-            else rc = retain_build_next(c, e->rbx, *c.dsnap, c.ndrb, c.ndrt, tiny, msg);
-        } else rc = retain_build_next(c, e->rhx, *c.hsnap, c.nhrb, c.nhrt, tiny, msg);
-        if (rc) {
-            std::lock_guard<std::mutex> g(e->mu);
-            return set_err(e, rc, msg);
+    std::string msg;
+    const int rc = with_retain_next(e, [&](auto&, auto*, auto& bx, auto& nx) {
+        if (!c.exec_snapshot) {
+            nx.n_items = c.items.size();
+            if (!c.next.rebuild(std::move(c.items))) return msg = c.next.error, (int)BMQ_E_INVAL;
+            c.items.clear(), c.items.shrink_to_fit();
+            return (int)BMQ_OK;
         }
-        c.n_items = c.dsnap ? c.dsnap->s.n : c.hsnap->s.n;
-        c.dsnap.reset(), c.hsnap.reset(); // (the next generation holds everything it needs)
-    } else {
-        c.n_items = c.items.size();
-        if (!c.next.rebuild(std::move(c.items))) {
-            std::lock_guard<std::mutex> g(e->mu);
-            return set_err(e, BMQ_E_INVAL, c.next.error);
-        }
-        c.items.clear(), c.items.shrink_to_fit();
-    }
+        if constexpr (std::is_same_v<std::decay_t<decltype(bx)>, DevExec>)
+            if (hipSetDevice(e->device) != hipSuccess) return msg = "hipSetDevice failed", (int)BMQ_E_HIP;
+        if (const int rc = retain_build_next(nx, bx, c.next, tiny, msg)) return rc;
+        nx.snap.reset(); // (the next generation holds everything it needs)
+        return (int)BMQ_OK;
+    });
     std::lock_guard<std::mutex> g(e->mu);
+    if (rc) return set_err(e, rc, msg);
     c.ms_build = ms_since(t0);
     c.built = true;
     c.ci.state = 2;
-    c.ci.builder = c.exec_built ? 1 : 0;
-    c.ci.fallback = c.fallback;
+    with_retain_next(e, [&](auto&, auto*, auto&, auto& nx) { c.ci.builder = nx.exec_built ? 1 : 0, c.ci.fallback = nx.fallback; });
     c.ci.build_ms = c.ms_build;
     return BMQ_OK;
 }
@@ -1105,30 +1004,24 @@ int bmq_retain_compact_swap(bmq_engine* e, uint64_t* out_carried, uint64_t* out_
         const uint64_t meter0 = retain_copy_meter(e);
         if (out_carried) *out_carried = c.next.n_topics;
         e->rhost = std::move(c.next);
-        if (c.exec_built) { // image, key store and mutable part change hands: no upload, no host loop over the topics
-            e->rb_serving = true;
-            if (e->drb) {
-                e->drb->take_image(*c.ndrb);
-                e->drb->view(e->rdev.view);
-                for (DevBuf* b : {&e->rdev.nodes, &e->rdev.edges, &e->rdev.posts, &e->rdev.gps, &e->rdev.tenants, &e->rdev.dict, &e->rdev.pool}) b->release(); // (a host-built generation's)
-                e->drt->adopt(*c.ndrt, e->rdev.view);
-                e->rbinfo = e->drb->info;
-            } else {
-                e->hrb->take_image(*c.nhrb);
-                e->hrb->view(e->rhview);
-                e->hrt->adopt(*c.nhrt, e->rhview);
-                e->rbinfo = e->hrb->info;
+        const int rc = with_retain_next(e, [&](auto& rt, auto* rb, auto&, auto& nx) {
+            if (nx.exec_built) { // image, key store and mutable part change hands: no upload, no host loop over the topics
+                e->rb_serving = true;
+                rb->take_image(*nx.rb);
+                rt.adopt(*nx.rt, adopt_exec_image(e, *rb));
+                e->rbinfo = rb->info;
+                e->rbuilt = true;
+                e->repoch++;
+                e->rgeneration++;
+                return (int)BMQ_OK;
             }
-            e->rbuilt = true;
-            e->repoch++;
-            e->rgeneration++;
-        } else {
             e->rb_serving = false; // (the host builder's: retain_builder = 0 or 1, or the executor builder declined)
-            e->rbinfo = host_build_info(e->rhost, c.n_items, c.ms_build, c.fallback);
-            if (int rc = retain_publish(e)) { // upload + the mutable part starts over: a new generation of topic ids
-                e->rcmp = bmq_engine::RetainCompaction{};
-                return rc;
-            }
+            e->rbinfo = host_build_info(e->rhost, nx.n_items, c.ms_build, nx.fallback);
+            return retain_publish(e); // upload + the mutable part starts over: a new generation of topic ids
+        });
+        if (rc) {
+            e->rcmp = bmq_engine::RetainCompaction{};
+            return rc;
         }
         n_log = c.log.size();
         ci = c.ci;
@@ -1156,35 +1049,7 @@ int bmq_retain_compact_swap(bmq_engine* e, uint64_t* out_carried, uint64_t* out_
         ci.replayed = n_log;
         e->rcinfo = ci;
     }
-    for (size_t lo = 0; lo < log.size();) {
-        const size_t hi = std::min(log.size(), lo + 65536);
-        std::vector<uint8_t> tb, pb, ops;
-        std::vector<uint32_t> toff{0}, poff{0}, ot, ex;
-        std::vector<uint64_t> ts;
-        std::unordered_map<std::string, uint32_t> tix;
-        bool any_ts = false;
-        for (size_t i = lo; i < hi; i++) any_ts = any_ts || log[i].has_ts;
-        for (size_t i = lo; i < hi; i++) {
-            const auto& o = log[i];
-            auto f = tix.find(o.tenant);
-            if (f == tix.end()) {
-                f = tix.emplace(o.tenant, (uint32_t)tix.size()).first;
-                tb.insert(tb.end(), o.tenant.begin(), o.tenant.end());
-                toff.push_back((uint32_t)tb.size());
-            }
-            ot.push_back(f->second);
-            pb.insert(pb.end(), o.topic.begin(), o.topic.end());
-            poff.push_back((uint32_t)pb.size());
-            ops.push_back(o.op);
-            ts.push_back(o.has_ts ? o.ts : 0ull);
-            ex.push_back(o.has_ts ? o.expiry : 0xFFFFFFFFu);
-        }
-        tb.resize(tb.size() + 16, 0), pb.resize(pb.size() + 16, 0);
-        const int rc = retain_apply_common(e, tb.data(), toff.data(), (uint32_t)tix.size(), ot.data(), pb.data(), poff.data(), ops.data(), any_ts ? ts.data() : nullptr,
-                                           any_ts ? ex.data() : nullptr, (uint32_t)(hi - lo), nullptr);
-        if (rc) return rc;
-        lo = hi;
-    }
+    if (int rc = retain_apply_chunked(e, log, false, [](uint32_t, auto&& apply) { return apply(); })) return rc;
     if (out_replayed) *out_replayed = n_log;
     return BMQ_OK;
 }
@@ -1214,31 +1079,8 @@ int bmq_retain_compact(bmq_engine* e) {
     if (e->rcmp.active) return set_err(e, BMQ_E_STATE, "a retain compaction is running: bmq_retain_compact_swap or bmq_retain_compact_abort first");
     if (e->cur->pending) return set_err(e, BMQ_E_STATE, "a batch is in flight: call bmq_match_finish first");
     if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
-    std::vector<uint32_t> ids;
-    std::vector<unsigned long long> ts;
-    std::vector<uint32_t> ex;
-    GcQuery q{};
-    q.live_only = 1;
-    q.override_expiry = -1;
-    const bool ok = with_retain(e, [&](auto& rt) {
-        const bool r = rt.select(q, nullptr, 0, ids) && rt.payload(ts, ex);
-        if (!r) e->err = rt.error;
-        return r;
-    });
-    if (!ok) return set_err(e, BMQ_E_HIP, e->err);
-    std::vector<uint8_t> bytes;
-    std::vector<uint64_t> off;
-    std::vector<uint32_t> tlen;
-    int rc = retain_topics_locked(e, ids.data(), (uint32_t)ids.size(), bytes, off, tlen);
-    if (rc) return rc;
-    std::vector<RetainIndexHost::Item> items(ids.size());
-    for (size_t i = 0; i < ids.size(); i++) {
-        items[i].tenant.assign((const char*)bytes.data() + off[i], tlen[i]);
-        items[i].topic.assign((const char*)bytes.data() + off[i] + tlen[i], (size_t)(off[i + 1] - off[i]) - tlen[i]);
-        items[i].ts = ts[ids[i]];
-        items[i].expiry = ex[ids[i]];
-        items[i].has_ts = !(items[i].ts == 0 && items[i].expiry == 0xFFFFFFFFu);
-    }
+    std::vector<RetainIndexHost::Item> items;
+    if (int rc = retain_live_items_locked(e, items)) return rc;
     return retain_load_items(e, std::move(items));
 }
 
@@ -1251,7 +1093,7 @@ int bmq_retain_count_in(const bmq_engine* ce, uint8_t flags, const uint8_t* star
     if (!e) return BMQ_E_INVAL;
     std::lock_guard<std::mutex> g(e->mu);
     Boundary bound;
-    if (!parse_boundary(flags, start, start_len, end, end_len, bound)) return set_err(e, BMQ_E_INVAL, "malformed boundary (start >= end, or a present key without bytes)");
+    if (int rc = parse_boundary(e, flags, start, start_len, end, end_len, bound)) return rc;
     uint64_t topics = 0, bytes = 0;
     if (int rc = retain_boundary_locked(e, bound, topics, out_key_bytes ? &bytes : nullptr, nullptr)) return rc;
     if (out_topics) *out_topics = topics;
@@ -1268,7 +1110,7 @@ int bmq_retain_ids_in(const bmq_engine* ce, uint8_t flags, const uint8_t* start,
     std::lock_guard<std::mutex> g(e->mu);
     *out_n = 0;
     Boundary bound;
-    if (!parse_boundary(flags, start, start_len, end, end_len, bound)) return set_err(e, BMQ_E_INVAL, "malformed boundary (start >= end, or a present key without bytes)");
+    if (int rc = parse_boundary(e, flags, start, start_len, end, end_len, bound)) return rc;
     uint64_t topics = 0;
     std::vector<uint32_t> ids;
     if (int rc = retain_boundary_locked(e, bound, topics, nullptr, &ids)) return rc;
@@ -1288,9 +1130,9 @@ int bmq_retain_import(bmq_engine* dst, bmq_engine* src, uint8_t flags, const uin
     {
         std::lock_guard<std::mutex> g(dst->mu);
         if (dst == src) return set_err(dst, BMQ_E_INVAL, "bmq_retain_import: source and destination are the same engine");
-        if (!parse_boundary(flags, start, start_len, end, end_len, bound)) return set_err(dst, BMQ_E_INVAL, "malformed boundary (start >= end, or a present key without bytes)");
+        if (int rc = parse_boundary(dst, flags, start, start_len, end, end_len, bound)) return rc;
         // the new sibling of a split: nothing to merge with, so the import is a bulk load (ranks, the fast path of '+' and '#')
-        dst_empty = !dst->rbuilt || (!dst->rcmp.active && (dst->drt ? dst->drt->info.n_live : dst->hrt->info.n_live) == 0);
+        dst_empty = !dst->rbuilt || (!dst->rcmp.active && retain_dyn_info(dst).n_live == 0);
         if (dst_empty)
             for (auto& sl : dst->slots)
                 if (sl.pending) return set_err(dst, BMQ_E_STATE, "a batch is in flight: finish / wait for it first");
@@ -1320,36 +1162,15 @@ int bmq_retain_import(bmq_engine* dst, bmq_engine* src, uint8_t flags, const uin
     // a merge: add ops through the ordinary apply path (a compaction running on dst logs them like any apply).  A topic dst holds already
     // has its stamps replaced: counted from dst's live count around every chunk (dst->api keeps other mutators out).
     uint64_t imported = 0, replaced = 0;
-    for (size_t lo = 0; lo < items.size();) {
-        const size_t hi = std::min(items.size(), lo + 65536);
-        std::vector<uint8_t> tb, pb, ops(hi - lo, 0);
-        std::vector<uint32_t> toff{0}, poff{0}, ot, ex;
-        std::vector<uint64_t> ts;
-        std::unordered_map<std::string, uint32_t> tix;
-        for (size_t i = lo; i < hi; i++) {
-            const auto& it = items[i];
-            auto f = tix.find(it.tenant);
-            if (f == tix.end()) {
-                f = tix.emplace(it.tenant, (uint32_t)tix.size()).first;
-                tb.insert(tb.end(), it.tenant.begin(), it.tenant.end());
-                toff.push_back((uint32_t)tb.size());
-            }
-            ot.push_back(f->second);
-            pb.insert(pb.end(), it.topic.begin(), it.topic.end());
-            poff.push_back((uint32_t)pb.size());
-            ts.push_back(it.has_ts ? it.ts : 0ull);
-            ex.push_back(it.has_ts ? it.expiry : 0xFFFFFFFFu);
-        }
-        tb.resize(tb.size() + 16, 0), pb.resize(pb.size() + 16, 0);
-        const uint64_t before = dst->drt ? dst->drt->info.n_live : dst->hrt->info.n_live;
-        const int rc = retain_apply_common(dst, tb.data(), toff.data(), (uint32_t)tix.size(), ot.data(), pb.data(), poff.data(), ops.data(), ts.data(), ex.data(),
-                                           (uint32_t)(hi - lo), nullptr);
-        if (rc) return rc;
-        const uint64_t fresh = (dst->drt ? dst->drt->info.n_live : dst->hrt->info.n_live) - before;
+    const int rc = retain_apply_chunked(dst, items, true, [&](uint32_t n, auto&& apply) {
+        const uint64_t before = retain_dyn_info(dst).n_live;
+        if (int rc = apply()) return rc;
+        const uint64_t fresh = retain_dyn_info(dst).n_live - before;
         imported += fresh;
-        replaced += (hi - lo) - fresh;
-        lo = hi;
-    }
+        replaced += n - fresh;
+        return (int)BMQ_OK;
+    });
+    if (rc) return rc;
     if (out_imported) *out_imported = imported;
     if (out_replaced) *out_replaced = replaced;
     return BMQ_OK;
@@ -1537,12 +1358,8 @@ int bmq_retain_keys_prepare(bmq_engine* e, uint64_t* out_store_bytes) {
     if (!e->rbuilt) return set_err(e, BMQ_E_STATE, "no retained-topic index");
     if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
     uint64_t bytes = 0;
-    const bool ok = with_retain(e, [&](auto& rt) {
-        const bool r = rt.keys_prepare(e->rhost, &bytes);
-        if (!r) e->err = rt.error;
-        return r;
-    });
-    if (!ok) return set_err(e, e->err.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : BMQ_E_HIP, e->err);
+    const bool ok = retain_try(e, [&](auto& rt) { return rt.keys_prepare(e->rhost, &bytes); });
+    if (!ok) return set_err(e, retain_rc(e->err), e->err);
     if (out_store_bytes) *out_store_bytes = bytes;
     return BMQ_OK;
 }
@@ -1557,12 +1374,8 @@ int bmq_retain_keys_by_id(const bmq_engine* ce, const uint32_t* topic_ids, uint3
     if (!e->rbuilt || n == 0) return BMQ_OK;
     if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
     bool nospace = false;
-    const bool ok = with_retain(e, [&](auto& rt) {
-        const bool r = rt.keys_by_id(e->rhost, topic_ids, n, out, cap, (unsigned long long*)out_off, nospace);
-        if (!r) e->err = rt.error;
-        return r;
-    });
-    if (!ok) return set_err(e, e->err.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : BMQ_E_HIP, e->err);
+    const bool ok = retain_try(e, [&](auto& rt) { return rt.keys_by_id(e->rhost, topic_ids, n, out, cap, (unsigned long long*)out_off, nospace); });
+    if (!ok) return set_err(e, retain_rc(e->err), e->err);
     if (nospace) return set_err(e, BMQ_E_NOSPACE, "output buffer too small");
     return BMQ_OK;
 }
@@ -1601,7 +1414,7 @@ int bmq_retain_keys_match(bmq_engine* e, const uint8_t* tenants, const uint32_t*
     const uint8_t* d_keys = nullptr;
     uint64_t key_bytes = 0;
     if (!e->drt->keys_compose(e->rhost, e->cur->s_lim_ids.as<uint32_t>(), (uint32_t)kept, d_koff, d_keys, key_bytes))
-        return set_err(e, e->drt->error.find("out of memory") != std::string::npos ? BMQ_E_NOMEM : BMQ_E_HIP, e->drt->error);
+        return set_err(e, retain_rc(e->drt->error), e->drt->error);
     *out_needed_key_bytes = key_bytes;
     if (kept > out_capacity || !out_topic_ids) { // (out_key_off has out_capacity + 1 entries: nothing of the rows fits)
         HIPCHK(e, hipStreamSynchronize(e->stream));

@@ -201,6 +201,65 @@ def test_the_lock_condition_no_copy_under_the_lock_grows_with_the_number_of_topi
         assert l0[k] - s0[k] > 20000
 
 
+@pytest.fixture(scope="module")
+def long_log():
+    """300 loaded topics over two tenants and 65 537 ops for the time between begin and build -- one more than a chunk of the replay (65 536): adds
+    of distinct short topics, and 300 removes, of loaded topics and of topics added a moment before, in turn.  -> (tenants, loaded, ops as
+    (tenant index, op, topic), the set model after them)"""
+    names = ["s0", "s1"]
+    loaded = [(names[i % 2], "base/%d" % i) for i in range(300)]
+    live, ops, n_adds, n_removes = set(loaded), [], 65537 - 300, 0
+    for i in range(n_adds):
+        ops.append((i % 2, 0, "n/%d" % i))
+        if i % 217 == 216 and n_removes < 300:
+            t, p = loaded[n_removes] if n_removes % 2 == 0 else (names[(i - 5) % 2], "n/%d" % (i - 5))
+            ops.append((names.index(t), 1, p))
+            n_removes += 1
+    assert len(ops) == 65537 and n_removes == 300
+    for t, op, p in ops:
+        (live.add if op == 0 else live.discard)((names[t], p))
+    return names, loaded, ops, live
+
+
+def topics_by_tenant(e, tenants):
+    """per tenant what '#' (and '$'-filters: no topic here starts with '$') would give -- a host-only engine cannot match, so: the tenant's live ids"""
+    return {t: sorted(p for _, p in e.retain_topics(e.retain_live_ids(t))) for t in tenants}
+
+
+def test_a_log_of_65537_ops_is_replayed_in_two_chunks_and_the_result_merges_in_two(long_log, engines):
+    names, loaded, ops, live = long_log
+    got = []
+    for rb in (0, 1):
+        e, dst = engines(rb), engines(rb)
+        e.retain_rebuild(names, [names.index(t) for t, _ in loaded], [p for _, p in loaded])
+        e.retain_compact_begin()
+        for lo in range(0, len(ops), 9000):                                            # (batches of its own size: the chunks are the replay's)
+            part = ops[lo:lo + 9000]
+            e.retain_apply_batch(names, [t for t, _, _ in part], [(op, p) for _, op, p in part])
+        e.retain_compact_build()
+        assert e.retain_compact_swap() == (300, 65537)
+        assert int(e.retain_compact_info().replayed) == 65537
+        by_tenant = topics_by_tenant(e, names)
+        assert int(e.retain_info().n_topics) == len(live) and by_tenant == {t: sorted(p for tt, p in live if tt == t) for t in names}
+        got.append((by_tenant, e.retain_live_ids()))
+        # the merge leg of bmq_retain_import: dst holds topics already, 70 of them src's too; src has more than 65 536 to give
+        more = [(0, "late/%d" % i) for i in range(500)]
+        e.retain_apply("s1", more)
+        src_live = live | {("s1", p) for _, p in more}
+        own = [("s1", "base/%d" % i) for i in range(101, 241, 2)] + [("s2", "own/%d" % i) for i in range(30)]
+        dst.retain_rebuild(["s1", "s2"], [0 if t == "s1" else 1 for t, _ in own], [p for _, p in own])
+        dst.retain_apply("s2", [(0, "own/added")])
+        n_src = int(e.retain_info().n_topics)
+        assert n_src == len(src_live) > 65536
+        imported, replaced = dst.retain_import(e)
+        both = src_live & set(own)
+        assert imported + replaced == n_src and replaced == len(both) > 0
+        union = src_live | set(own) | {("s2", "own/added")}
+        assert int(dst.retain_info().n_topics) == len(union)
+        assert topics_by_tenant(dst, ["s0", "s1", "s2"]) == {t: sorted(p for tt, p in union if tt == t) for t in ("s0", "s1", "s2")}
+    assert got[0] == got[1]                                                             # the two builders agree, id for id
+
+
 def test_the_switch_has_a_value_of_its_own_and_under_1_the_three_calls_stay_the_host_builders(corpus):
     ld, m = corpus["SIZE-65"]
     for bad in (2, 4):

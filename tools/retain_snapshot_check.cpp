@@ -6,10 +6,12 @@
 //     loaded topics, a few ids are removed by id;
 //   * RetainDyn::snapshot (all live topics, then those inside a KV boundary) is compared item for item with the strings and stamps the
 //     existing host path gives for the same ids (select / boundary_select, payload, RetainIndexHost::topic, overlay_topics);
-//   * RetainBuild builds from the snapshot where it lies (in_exec) -- its permutation, tenants, counts and RNode array equal those of a build
-//     of the same items handed in from host memory;
-//   * RetainDyn::reset_exec + adopt give the mutable part the next generation serves with: live ids are the ranks, stamps and expire_at those
+//   * retain_build_next (bmq_retain_next.h: the very function bmq_retain_compact_build runs) builds from the snapshot where it lies -- the
+//     permutation, tenants, counts and RNode array equal those of a build of the same items handed in from host memory; with a topic of 129
+//     levels in the load it falls back to the host builder, whose catalogue holds exactly the snapshot's items; 128 levels do not fall back;
+//   * its RetainDyn (reset_exec), adopted, is the mutable part the next generation serves with: live ids are the ranks, stamps and expire_at those
 //     of the catalogue, every key of keys_by_id (the key store the gather laid out) equals retain_message_key of the catalogue's strings;
+//   * PackedTopics (the engine's one packer) round-trips hostile tenants, topics and stamps, once, before the rounds;
 //   * with more than one thread (the TSan form) a second thread applies batches to the serving generation while the build runs.
 // Build + run: make -C bifromq_amd/csrc rscheck   (tests/test_retain_generation.py builds and runs both forms)
 #include <algorithm>
@@ -25,6 +27,7 @@
 #include "../bifromq_amd/csrc/bmq_retain.h"
 #include "../bifromq_amd/csrc/bmq_retain_build.h"
 #include "../bifromq_amd/csrc/bmq_retain_dyn.h"
+#include "../bifromq_amd/csrc/bmq_retain_next.h"
 
 using namespace bmq;
 
@@ -112,6 +115,44 @@ static int compare_snapshot(const RetainSnapshot<HostExec>& snap, const std::vec
     return 0;
 }
 
+// PackedTopics: pack -> pad -> rb_input -> items gives the input back (an item stamped (0, 0xFFFFFFFF) as one without stamps)
+static int packed_round_trip() {
+    using It = RetainIndexHost::Item;
+    const std::string big(200, 'T'), t255 = "x/" + std::string(253, 'y');
+    auto item = [](const std::string& tn, const std::string& tp, bool has, uint64_t ts, uint32_t ex) {
+        It it;
+        it.tenant = tn, it.topic = tp, it.has_ts = has, it.ts = ts, it.expiry = ex;
+        return it;
+    };
+    const std::vector<It> in = {item("", "", true, 5, 10),          item(big, "a//b", true, 1ull << 40, 0), item("t", "/", true, 7, 0xFFFFFFFFu), item("", "$SYS/x", true, 0, 3),
+                                item(big, "$share", false, 99, 99), item("t", t255, true, 9, 9),            item("", "a/", true, 0, 0xFFFFFFFFu), item(big, "", true, 1, 1),
+                                item("t", "//", false, 0, 0),       item("", "a//b", true, 2, 2)};
+    PackedTopics P;
+    for (const It& it : in)
+        if (!P.add(it.tenant, it.topic, it.has_ts, it.ts, it.expiry)) FAIL("PackedTopics: add refused a small item\n");
+    const size_t tenant_bytes = P.tenants.size(), topic_bytes = P.topics.size();
+    P.pad();
+    const RbInput r = P.rb_input();
+    if (r.n != in.size() || r.n_tenants != 3 || P.n() != r.n || r.tenant_off[3] != tenant_bytes || tenant_bytes != 201 || r.topic_off[r.n] != topic_bytes || !P.any_ts)
+        FAIL("PackedTopics: %u items over %u tenants, %zu / %zu bytes\n", r.n, r.n_tenants, tenant_bytes, topic_bytes);
+    if (P.tenants.size() != tenant_bytes + 16 || P.topics.size() != topic_bytes + 16) FAIL("PackedTopics: pad did not add 16 bytes\n");
+    for (size_t k = 0; k < 16; k++)
+        if (r.tenants[tenant_bytes + k] || r.topics[topic_bytes + k]) FAIL("PackedTopics: the 16 bytes behind the tenants / topics are not zero\n");
+    const std::vector<It> own = P.items(), cut = PackedTopics::items(r.n, PackedTopics::by_table(r.tenants, r.tenant_off, r.item_tenant, r.topics, r.topic_off), r.ts, r.expiry),
+                          bare = PackedTopics::items(r.n, PackedTopics::by_table(r.tenants, r.tenant_off, r.item_tenant, r.topics, r.topic_off), nullptr, nullptr);
+    for (size_t i = 0; i < in.size(); i++) {
+        const bool has = in[i].has_ts && !(in[i].ts == 0 && in[i].expiry == 0xFFFFFFFFu); // the sentinel rule
+        const uint64_t ts = has ? in[i].ts : 0;
+        const uint32_t ex = has ? in[i].expiry : 0xFFFFFFFFu;
+        for (const std::vector<It>* got : {&own, &cut})
+            if ((*got)[i].tenant != in[i].tenant || (*got)[i].topic != in[i].topic || (*got)[i].has_ts != has || (*got)[i].ts != ts || (*got)[i].expiry != ex)
+                FAIL("PackedTopics: item %zu comes back as ('%s', '%s', %d, %llu, %u)\n", i, (*got)[i].tenant.c_str(), (*got)[i].topic.c_str(), (int)(*got)[i].has_ts,
+                     (unsigned long long)(*got)[i].ts, (*got)[i].expiry);
+        if (bare[i].tenant != in[i].tenant || bare[i].topic != in[i].topic || bare[i].has_ts) FAIL("PackedTopics: item %zu without stamp arrays\n", i);
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const int rounds = argc > 1 ? atoi(argv[1]) : 24;
     const uint64_t seed = argc > 2 ? strtoull(argv[2], nullptr, 10) : 1;
@@ -125,7 +166,8 @@ int main(int argc, char** argv) {
         for (size_t k = 0; k < depth; k++) p += (k ? "/" : "") + alpha[rnd(alpha.size())] + (rnd(3) ? std::to_string(rnd(40)) : "");
         return p;
     };
-    uint64_t n_items = 0, n_overlay = 0, n_bounded = 0;
+    uint64_t n_items = 0, n_overlay = 0, n_bounded = 0, n_fallback = 0, n_deep128 = 0;
+    if (packed_round_trip()) return 1;
     const size_t sizes[] = {0, 1, 64, 65, 63, 257};
     for (int round = 0; round < rounds; round++) {
         HostExec hx, bx;
@@ -136,6 +178,13 @@ int main(int argc, char** argv) {
         for (auto& t : tenants) L.tenant(t);
         const size_t n = round < 6 ? sizes[round] : 1 + rnd(900);
         for (size_t i = 0; i < n; i++) L.item((uint32_t)rnd(tenants.size()), topic(), ((uint64_t)(1 + i)) << 16, rnd(5) ? (uint32_t)rnd(1000) : 0xFFFFFFFFu);
+        // one topic at the executor builder's limit (every 8th round from 7 on) or a level past it (from 6 on): the generation change falls back
+        const size_t deep = round % 8 == 6 ? 129 : (round % 8 == 7 ? 128 : 0);
+        if (deep) {
+            std::string p = "d";
+            for (size_t k = 1; k < deep; k++) p += "/d";
+            L.item(2, p, 77ull << 16, 1000);
+        }
         L.pad();
         RetainIndexHost h;
         RetainBuild<HostExec> rb(hx);
@@ -145,8 +194,8 @@ int main(int argc, char** argv) {
             retain_catalogue(h, L.input(), rb);
             rb.view(v);
         } else {
-            std::vector<RetainIndexHost::Item> items(n);
-            for (size_t i = 0; i < n; i++) {
+            std::vector<RetainIndexHost::Item> items(L.it.size());
+            for (size_t i = 0; i < items.size(); i++) {
                 items[i].tenant = tenants[L.it[i]];
                 items[i].topic.assign(L.pb.data() + L.poff[i], L.poff[i + 1] - L.poff[i]);
                 items[i].has_ts = true, items[i].ts = L.ts[i], items[i].expiry = L.ex[i];
@@ -174,7 +223,12 @@ int main(int argc, char** argv) {
         if (round != 2 && !churn(rt, round < 6 ? 3 + (size_t)round : 1 + rnd(200), 5000)) FAIL("round %d: apply: %s\n", round, rt.error.c_str());
         if (rt.info.id_bound) {
             std::vector<uint32_t> gone;
-            for (int k = 0; k < 4; k++) gone.push_back((uint32_t)rnd(rt.info.id_bound));
+            for (int k = 0; k < 4; k++) {
+                const uint32_t id = (uint32_t)rnd(rt.info.id_bound);
+                std::string_view tn, tp;
+                if (deep && h.topic(id, tn, tp) && (size_t)std::count(tp.begin(), tp.end(), '/') + 1 == deep) continue; // (the deep topic stays: the round is about it)
+                gone.push_back(id);
+            }
             uint64_t removed = 0;
             if (!rt.remove_ids(gone.data(), (uint32_t)gone.size(), removed)) FAIL("round %d: remove_ids: %s\n", round, rt.error.c_str());
         }
@@ -184,7 +238,10 @@ int main(int argc, char** argv) {
         std::vector<Item> want;
         GcQuery q{};
         q.live_only = 1, q.override_expiry = -1;
-        RetainSnapshot<HostExec> snap(hx);
+        RetainNext<HostExec> nx;
+        nx.snap = std::make_unique<RetainSnapshot<HostExec>>(hx);
+        RetainSnapshot<HostExec>& snap = *nx.snap;
+        const RsSnap& S = snap.s;
         if (!rt.select(q, nullptr, 0, ids) || !items_of(rt, h, ids, want)) FAIL("round %d: the host path failed: %s\n", round, rt.error.c_str());
         if (!rt.snapshot(h, 0, nullptr, 0, nullptr, 0, snap)) FAIL("round %d: snapshot: %s\n", round, rt.error.c_str());
         if (compare_snapshot(snap, want, round, "all")) return 1;
@@ -203,32 +260,49 @@ int main(int argc, char** argv) {
             if (compare_snapshot(part, in_want, round, "bounded")) return 1;
             n_bounded += in_want.size();
         }
-        // ---- build from the snapshot on an executor of its own; meanwhile (threads > 1) the serving generation is mutated ----
+        // ---- the product's build step (retain_build_next) from the snapshot, on an executor of its own; meanwhile (threads > 1) the serving
+        // generation is mutated ----
         bool churn_ok = true;
         std::thread mutator;
         if (threads > 1) mutator = std::thread([&] { for (int k = 0; k < 3 && churn_ok; k++) churn_ok = churn(rt, 50, 9000 + 100 * (uint64_t)k); });
-        const RsSnap& S = snap.s;
-        std::vector<uint8_t> tb(S.tenants, S.tenants + S.tenant_off[S.n_tenants] + 16);
-        std::vector<uint32_t> toff(S.tenant_off, S.tenant_off + S.n_tenants + 1);
-        RbInput in{tb.data(), toff.data(), S.n_tenants, S.item_tenant, S.topics, S.topic_off, S.n, nullptr, nullptr};
-        in.in_exec = true, in.topic_bytes = snap.topic_bytes;
-        RetainBuild<HostExec> nb(bx), ref(bx);
-        nb.keep_perm = true;
-        const bool built = nb.build(in);
-        RetainDyn<HostExec> nrt(bx);
-        nrt.tiny = rt.tiny;
         RetainIndexHost h2;
-        bool next_ok = false;
-        if (built) {
-            RbInput host_in{tb.data(), toff.data(), S.n_tenants, S.item_tenant, S.topics, S.topic_off, S.n, (const uint64_t*)S.ts, S.expiry};
-            retain_catalogue(h2, host_in, nb);
-            next_ok = nrt.reset_exec(S, nb.d_perm, (uint32_t)nb.info.n_topics, nb.names, nb.t_begin);
-        }
+        std::string msg;
+        const int rc = retain_build_next(nx, bx, h2, rt.tiny, msg);
         if (mutator.joinable()) mutator.join();
         if (!churn_ok) FAIL("round %d: apply beside the build: %s\n", round, rt.error.c_str());
-        if (!built) FAIL("round %d: build from the snapshot: %s\n", round, nb.error.c_str());
-        if (!next_ok) FAIL("round %d: reset_exec: %s\n", round, nrt.error.c_str());
+        if (rc != BMQ_OK) FAIL("round %d: retain_build_next: %d, %s\n", round, rc, msg.c_str());
+        if (nx.n_items != want.size()) FAIL("round %d: retain_build_next counts %llu items of %zu\n", round, (unsigned long long)nx.n_items, want.size());
+        size_t max_levels = 0;
+        for (const Item& w : want) max_levels = std::max<size_t>(max_levels, 1 + (size_t)std::count(w.topic.begin(), w.topic.end(), '/'));
+        if (deep == 129 && max_levels != 129) FAIL("round %d: the topic of 129 levels is not in the snapshot\n", round);
+        if (deep == 128 && max_levels != 128) FAIL("round %d: the topic of 128 levels is not in the snapshot\n", round);
+        if (max_levels > RB_MAX_DEPTH) { // declined by the executor builder: the host builder has loaded the snapshot's items, the swap would upload
+            if (nx.fallback != 1 || nx.exec_built || nx.rb || nx.rt) FAIL("round %d: a topic of %zu levels, but no fallback to the host builder\n", round, max_levels);
+            if (h2.nodes.empty() || h2.n_topics != want.size()) FAIL("round %d: the fallback catalogue holds %llu topics of %zu\n", round, (unsigned long long)h2.n_topics, want.size());
+            std::vector<Item> got, sorted = want;
+            for (uint32_t id = 0; id < h2.n_topics; id++) {
+                std::string_view tn, tp;
+                uint64_t s0 = 0;
+                uint32_t e0 = 0;
+                if (!h2.topic(id, tn, tp, &s0, &e0)) FAIL("round %d: the fallback catalogue has no id %u\n", round, id);
+                got.push_back(Item{std::string(tn), std::string(tp), s0, e0});
+            }
+            auto by_name = [](const Item& a, const Item& b) { return a.tenant != b.tenant ? a.tenant < b.tenant : a.topic < b.topic; };
+            std::sort(got.begin(), got.end(), by_name), std::sort(sorted.begin(), sorted.end(), by_name);
+            if (!(got == sorted)) FAIL("round %d: the fallback catalogue's items are not the snapshot's\n", round);
+            RetainDyn<HostExec> frt(hx); // ... and serves like any host-built generation
+            if (!frt.reset(view_of(h2), h2) || frt.info.n_live != want.size() || !churn(frt, 20, 12000)) FAIL("round %d: the fallback generation does not serve: %s\n", round, frt.error.c_str());
+            n_fallback++;
+            continue;
+        }
+        if (nx.fallback != 0 || !nx.exec_built || !nx.rb || !nx.rt) FAIL("round %d: no topic of more than %u levels, but a fallback\n", round, RB_MAX_DEPTH);
+        n_deep128 += max_levels == 128;
+        RetainBuild<HostExec>& nb = *nx.rb;
+        RetainDyn<HostExec>& nrt = *nx.rt;
+        RetainBuild<HostExec> ref(bx);
         // the same items from host memory (copies: nothing shared with the snapshot)
+        std::vector<uint8_t> tb(S.tenants, S.tenants + S.tenant_off[S.n_tenants] + 16);
+        std::vector<uint32_t> toff(S.tenant_off, S.tenant_off + S.n_tenants + 1);
         std::vector<uint8_t> pb(S.topics, S.topics + snap.topic_bytes + 16);
         std::vector<uint32_t> poff(S.topic_off, S.topic_off + S.n + 1), itn(S.item_tenant, S.item_tenant + S.n), ex(S.expiry, S.expiry + S.n);
         std::vector<uint64_t> ts(S.ts, S.ts + S.n);
@@ -279,8 +353,9 @@ int main(int argc, char** argv) {
         // ... it takes ops like any other
         if (!churn(rt2, 20, 12000)) FAIL("round %d: apply on the adopted generation: %s\n", round, rt2.error.c_str());
     }
-    if (rounds >= 8 && (n_overlay == 0 || n_bounded == 0)) FAIL("no round reached an overlay topic / a bounded snapshot: the check proves nothing\n");
-    printf("retain_snapshot_check ok: %d rounds, %llu items (%llu from the overlay), %llu in bounded snapshots, %u threads\n", rounds, (unsigned long long)n_items,
-           (unsigned long long)n_overlay, (unsigned long long)n_bounded, threads);
+    if (rounds >= 8 && (n_overlay == 0 || n_bounded == 0 || n_fallback == 0 || n_deep128 == 0))
+        FAIL("no round reached an overlay topic / a bounded snapshot / a fallback / a topic of 128 levels: the check proves nothing\n");
+    printf("retain_snapshot_check ok: %d rounds, %llu items (%llu from the overlay), %llu in bounded snapshots, %llu fallbacks to the host builder, %llu builds of a 128-level topic, packed round trip, %u threads\n",
+           rounds, (unsigned long long)n_items, (unsigned long long)n_overlay, (unsigned long long)n_bounded, (unsigned long long)n_fallback, (unsigned long long)n_deep128, threads);
     return 0;
 }
