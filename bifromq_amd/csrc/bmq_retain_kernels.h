@@ -10,7 +10,9 @@
 // their number is known; only a filter with more than R_OUT ranges is walked a second time (count, then write).  The CSR is then produced by the dist direction's k_scan_blocks /
 // k_expand / k_sort_rows (same MatchRange plumbing).
 #pragma once
+#ifndef BMQ_WAVE_EMU // (tools/emu/retain_dyn_emu.cpp compiles this file with g++ against the wave64 emulator)
 #include <hip/hip_runtime.h>
+#endif
 
 #include "bmq_dist_kernels.h"
 #include "bmq_retain.h"
@@ -38,6 +40,7 @@ constexpr uint32_t OV_OUT = BMQ_OV_OUT;   // matched OVERLAY topic ids of one fi
 #define BMQ_R_WAVES_PER_CU 16
 #endif
 constexpr uint32_t R_WAVES_PER_CU = BMQ_R_WAVES_PER_CU; // persistent waves per CU (LDS: 16 B per frontier entry + 8 B per range / overlay id + ~1.7 KB)
+static_assert(BMQ_OV_OUT >= 64, "the overlay buffer takes the matches of a whole wave (up to 64 ids) right after it was flushed");
 static_assert(R_WAVES_PER_CU * (16u * BMQ_R_FRONT + 8u * BMQ_R_OUT + 8u * BMQ_OV_OUT + 1700u) <= 160u * 1024u, "the retain walk's LDS lists do not fit that many waves");
 struct Frontier {
     uint32_t* lb;

@@ -36,7 +36,8 @@ def test_the_emulator_against_the_definitions_of_its_operations(tmp_path):
 def test_k_retain_walk_under_the_wave_emulator(tmp_path, defs, rounds):
     """tools/emu/rwalk_emu.cpp: bifromq_amd/csrc/bmq_rwalk_kernel.h (the retain direction's walk: 8 / 4 / 2 filters per wave, lanes handed out to
     units, range / list / postings frontiers, the '$' hole, bulk chunks, merged subtrees, refills, room reservation, lists that outgrow LDS and
-    the arena, filters too deep for it) over indexes built by the product's own host builder, against a brute force over the topic strings;
+    the arena, filters too deep for it; every other round the DYN instantiation over a dead bitmap -- random, sparse, alternating whole words, word edges
+    only -- whose live counts must equal the expected ids that are not dead) over indexes built by the product's own host builder, against a brute force over the topic strings;
     the harness fails if its cases miss one of the kernel's rarely taken paths."""
     exe = str(tmp_path / "rwalk_emu")
     cmd = ["g++", "-O1", "-std=c++17", *defs, "-I", os.path.join(ROOT, "bifromq_amd", "csrc"), "-I", os.path.join(ROOT, "tools", "emu"),

@@ -182,8 +182,8 @@ def test_edge_shapes(eng):
 
 
 def test_filters_deeper_than_64_levels_inside_a_normal_batch(eng):
-    """TopicLevelTrie.lookup has no depth limit (UTIL/index/TopicLevelTrie.java:190-249).  k_retain_walk keeps a filter's per-level arrays in
-    LDS (64 levels); deeper filters are listed and answered by a second launch of the same walk with those arrays in global memory
+    """TopicLevelTrie.lookup has no depth limit (UTIL/index/TopicLevelTrie.java:190-249).  k_retain_walk handles filters of up to RW_LV = 16
+    levels; deeper filters are listed and answered by the deep pass, a one-filter-per-wave walk with its per-level arrays in global memory
     (k_retain_walk_deep, in the pipeline only while batches hold such filters).  65-, 100- and 300-level filters -- literal, '+', trailing
     '#', matching and not -- inside a batch of ordinary ones, against the oracle; before and after an apply (overlay + dead ids); the deep
     pass switches itself off again after 32 batches without such filters."""

@@ -1,7 +1,8 @@
 // rwalk_emu.cpp -- host-side logic test of k_retain_walk (bifromq_amd/csrc/bmq_rwalk_kernel.h) under the wave64 emulator of wave_emu.h.
 // Test tooling: the kernel's LOGIC -- tokeniser, the hand-out of lanes to units, range / list frontiers, the '$' hole of a first-level
 // wildcard, '+' over lists, the emission order, room reservation in `pairs`, lists that outgrow LDS and the arena, filters too deep for
-// it -- against a brute force over the topic strings (the rule of SURVEY.md 8a-0: RS/index/RetainTopicIndex.java:36-124), on indexes the
+// it, and (every other round, the DYN instantiation) the live counts of the matched ranges on an index with dead ids: random, sparse, alternating
+// whole words, word edges only -- against a brute force over the topic strings (the rule of SURVEY.md 8a-0: RS/index/RetainTopicIndex.java:36-124), on indexes the
 // product's own host builder makes (bmq_retain.cpp).  What the GPU makes of the same source is what tests/ (-m gpu) check against the oracle.
 //   g++ -O1 -g -std=c++17 -I bifromq_amd/csrc -I tools/emu tools/emu/rwalk_emu.cpp bifromq_amd/csrc/bmq_retain.cpp -o build/rwalk_emu && build/rwalk_emu [rounds] [seed]
 #define BMQ_WAVE_EMU 1
@@ -57,7 +58,7 @@ template <int G> static int run(int rounds, uint64_t seed) {
     std::mt19937_64 rng(seed);
     auto rnd = [&](size_t n) { return (size_t)(rng() % n); };
     const std::vector<std::string> tenants = {"t", "tenantB", "a-much-longer-tenant-identifier"};
-    uint64_t n_filters_checked = 0, n_ids = 0, n_reruns = 0, n_deep = 0;
+    uint64_t n_filters_checked = 0, n_ids = 0, n_reruns = 0, n_deep = 0, n_dyn_filters = 0, n_dead_ids = 0;
     for (int round = 0; round < rounds; round++) {
         // ---- an index: `wide` makes nodes with hundreds of children (lists beyond the LDS part, ranges across rounds) ----
         const bool wide = round % 3 == 1;
@@ -99,6 +100,28 @@ template <int G> static int run(int rounds, uint64_t seed) {
         v.dict = h.dict.data();
         v.dict_group_mask = (uint32_t)h.dict.size() / DICT_GROUP - 1;
         v.pool = h.pool.data();
+        // ---- a dead bitmap over the bulk-loaded ids (bits from n_topics on are set, like RetainDyn keeps them) with its rank directory: the DYN
+        // instantiation (every other round) counts the LIVE ids of a range through them; the range list stays whole ----
+        const bool dyn_round = round % 2 == 0;
+        const uint32_t n_bulk = (uint32_t)h.n_topics, dead_words = n_bulk / 64 + 2, pattern = (uint32_t)(round / 2) % 4;
+        std::vector<unsigned long long> dead_bits(dead_words, 0);
+        std::vector<uint32_t> dead_rank(dead_words + 1, 0);
+        for (uint32_t id = 0; id < dead_words * 64; id++) {
+            bool d = id >= n_bulk;
+            if (!d && pattern == 0) d = rnd(10) < 3;
+            if (!d && pattern == 1) d = rnd(20) == 0;
+            if (!d && pattern == 2) d = (id >> 6) & 1u;
+            if (!d && pattern == 3) d = (id & 63u) == 0 || (id & 63u) == 63;
+            if (d) dead_bits[id >> 6] |= 1ull << (id & 63u);
+        }
+        for (uint32_t w = 0; w < dead_words; w++) dead_rank[w + 1] = dead_rank[w] + (uint32_t)__builtin_popcountll(dead_bits[w]);
+        auto is_dead = [&](uint32_t id) { return (dead_bits[id >> 6] >> (id & 63u)) & 1ull; };
+        if (dyn_round) {
+            v.dyn.dead_bits = dead_bits.data();
+            v.dyn.dead_rank = dead_rank.data();
+            v.dyn.base_n = n_bulk;
+            v.dyn.use_dead = dead_before(dead_bits.data(), dead_rank.data(), n_bulk) != 0 ? 1u : 0u; // (as RetainDyn::view() sets it: some bulk-loaded id is dead)
+        }
         // ---- a batch of filters ----
         const uint32_t n = round == 0 ? 5 : 1 + (uint32_t)rnd(90);
         std::vector<std::string> flt(n);
@@ -188,7 +211,8 @@ template <int G> static int run(int rounds, uint64_t seed) {
             for (uint32_t blk = 0; blk < grid; blk++)
                 wemu::run_wave(blk, [&]() {
                     static RwLds<G> L;
-                    retain_walk_rounds<G, false>(r, a, L);
+                    if (dyn_round) retain_walk_rounds<G, true>(r, a, L);
+                    else retain_walk_rounds<G, false>(r, a, L);
                 });
             if (ctr.status & ~(ST_NEED_PAIRS | ST_RETAIN_LIST)) FAIL("round %d: status %#x\n", round, ctr.status);
             if (ctr.status) {
@@ -228,7 +252,11 @@ template <int G> static int run(int rounds, uint64_t seed) {
                     fprintf(stderr, "\n");
                     return 1;
                 }
-                if (route_cnt[i] != exp.size()) FAIL("round %d filter %u: route_cnt %u != %zu\n", round, i, route_cnt[i], exp.size());
+                size_t exp_live = exp.size(); // (DYN: the ids of the ranges that are not dead)
+                if (dyn_round)
+                    for (uint32_t id : exp) exp_live -= is_dead(id) ? 1 : 0, n_dead_ids += is_dead(id) ? 1 : 0;
+                if (route_cnt[i] != exp_live) FAIL("round %d filter %u '%s': route_cnt %u != %zu live of %zu ids (DYN %d, dead pattern %u)\n", round, i, flt[i].c_str(), route_cnt[i], exp_live, exp.size(), (int)dyn_round, pattern);
+                n_dyn_filters += dyn_round;
                 total += exp.size();
                 n_ids += exp.size();
                 n_filters_checked++;
@@ -244,8 +272,9 @@ template <int G> static int run(int rounds, uint64_t seed) {
         printf("  %s: %llu\n", paths[i], bmq::g_rw_cover[i]);
         bmq::g_rw_cover[i] = 0;
     }
-    printf("ok: G %d: %llu filters (%llu deeper than the kernel walks), %llu ids, %llu re-runs after growth\n", G, (unsigned long long)n_filters_checked,
-           (unsigned long long)n_deep, (unsigned long long)n_ids, (unsigned long long)n_reruns);
+    if (rounds >= 8 && n_dead_ids == 0) FAIL("G %d: no DYN round matched a dead id\n", G);
+    printf("ok: G %d: %llu filters (%llu deeper than the kernel walks, %llu through the DYN instantiation with %llu dead ids in their ranges), %llu ids, %llu re-runs after growth\n", G,
+           (unsigned long long)n_filters_checked, (unsigned long long)n_deep, (unsigned long long)n_dyn_filters, (unsigned long long)n_dead_ids, (unsigned long long)n_ids, (unsigned long long)n_reruns);
     return 0;
 }
 
