@@ -297,16 +297,21 @@ BMQ_HD uint32_t tail_hash(const uint8_t* kp, unsigned long long beg, unsigned lo
     }
     return mix32(h) | 1u;
 }
-// kp[ao, ao + n) == kp[bo, bo + n), 16 bytes per step (key pool only, see bytes_chunk16)
-BMQ_HD bool pool_bytes_equal(const uint8_t* kp, unsigned long long ao, unsigned long long bo, unsigned long long n) {
+// a[ao, ao + n) == b[bo, bo + n), 16 bytes per step: both buffers are readable 32 bytes past their last key, like the key pool (see
+// bytes_chunk16) -- a and b are two offsets of one pool for the mutation path, a pool and a batch of query keys for find_key_one
+BMQ_HD bool chunk_bytes_equal(const uint8_t* a, unsigned long long ao, const uint8_t* b, unsigned long long bo, unsigned long long n) {
     for (unsigned long long i = 0; i < n; i += 16) {
         uint32_t x[4], y[4];
         const uint32_t m = (uint32_t)(n - i < 16 ? n - i : 16);
-        bytes_chunk16(kp, ao + i, m, x);
-        bytes_chunk16(kp, bo + i, m, y);
+        bytes_chunk16(a, ao + i, m, x);
+        bytes_chunk16(b, bo + i, m, y);
         if (((x[0] ^ y[0]) | (x[1] ^ y[1]) | (x[2] ^ y[2]) | (x[3] ^ y[3])) != 0) return false;
     }
     return true;
+}
+// kp[ao, ao + n) == kp[bo, bo + n) (key pool only)
+BMQ_HD bool pool_bytes_equal(const uint8_t* kp, unsigned long long ao, unsigned long long bo, unsigned long long n) {
+    return chunk_bytes_equal(kp, ao, kp, bo, n);
 }
 BMQ_HD bool bytes_equal(const uint8_t* a, unsigned long long ao, const uint8_t* b, unsigned long long bo, unsigned long long n) {
     for (unsigned long long i = 0; i < n; i++)
@@ -811,7 +816,9 @@ BMQ_HD uint32_t idset_at(const DistIndexMut& ix, const IdSet& s, uint32_t m) { r
 // (Sixteen members per step: their ids and tail hashes are requested together -- one memory latency per sixteen members instead of two per
 // member.  A group lane is alone on its chain of dependent reads, the builder's kernels run at 1-2 waves per SIMD, and a filter with a few
 // hundred routes made its lane the one the whole k_b_group launch waited for.)
-BMQ_HD uint32_t idset_find_key(const DistIndexMut& ix, const IdSet& s, const KeyView& k, uint32_t th) {
+// (The key whose tail is looked for lies in `qb`: the key pool itself for the mutation path -- idset_find_key below --, a batch of query keys
+// for find_key_one.)
+BMQ_HD uint32_t idset_find_tail(const DistIndexMut& ix, const IdSet& s, const uint8_t* qb, const KeyView& k, uint32_t th) {
     const uint32_t n = s.count();
     const unsigned long long tl = k.end - k.tail;
     constexpr uint32_t STEP = 16;
@@ -828,11 +835,12 @@ BMQ_HD uint32_t idset_find_key(const DistIndexMut& ix, const IdSet& s, const Key
             const unsigned long long off = r & KREF_OFF_MASK, len = r >> KREF_LEN_SHIFT;
             if (len < tl) continue;
             // same filter node => same tenant + levels; the keys are equal iff their tails are
-            if (pool_bytes_equal(ix.kpool, off + len - tl, k.tail, tl)) return m0 + j;
+            if (chunk_bytes_equal(ix.kpool, off + len - tl, qb, k.tail, tl)) return m0 + j;
         }
     }
     return NONE;
 }
+BMQ_HD uint32_t idset_find_key(const DistIndexMut& ix, const IdSet& s, const KeyView& k, uint32_t th) { return idset_find_tail(ix, s, ix.kpool, k, th); }
 BMQ_HD uint32_t pow2_ceil(uint32_t v) {
     uint32_t p = 4;
     while (p < v) p <<= 1;
@@ -1214,6 +1222,63 @@ BMQ_HD void find_copy(const DistIndexMut& ix, const uint8_t* q, uint32_t tenant_
     const uint32_t n = s.count();
     out[0] = n;
     for (uint32_t m = 0; m < n && m < cap; m++) out[1 + m] = idset_at(ix, s, m);
+}
+// Route key -> route id (bmq_routes_find; the carry of the member tables of shared subscriptions through a generation change): the
+// read-only half of locate_one and idset_find_key.  The key is qb[start, end), in a buffer of its own that is readable 32 bytes past its
+// last key -- a batch of query keys, or the key pool of ANOTHER generation of the index.  Nothing of the index's CONTENT is written: no
+// dictionary token, no trie node, no Bloom or child filter bit comes into being, no tail record is invalidated.  Two words outside it can
+// be: dict_intern / trie_child raise ERR_STUCK / ERR_DICT_FULL in bc->err when a probe loop runs out on a damaged table (nobody reads it
+// after a lookup -- the batch counters are zeroed in front of the next apply --, so such a key is answered NONE, not with an error), and
+// trie_child records where the tenant root's '+' child lies (TenantSlot.root_plus) if it finds it before its creator said so, which
+// cannot happen behind a kernel boundary; both are idempotent.  NONE: no live route has this key; bad = the key is malformed (key_parse).
+struct KeySource {
+    const uint8_t* base;             // key bytes
+    const unsigned long long* refs;  // [n] offset | (length << KREF_LEN_SHIFT), the key store's form; length 0 = no key (answered NONE)
+};
+BMQ_HD uint32_t find_key_one(const DistIndexMut& ix, const uint8_t* qb, unsigned long long start, unsigned long long end, bool& bad) {
+    KeyView k;
+    bad = !key_parse(qb, start, end, k);
+    if (bad) return NONE;
+    const uint32_t d = tenant_find(ix.tenants, ix.tenant_mask, ix.tenant_names, qb, k.tenant, k.tenant_end);
+    if (d == NONE) return NONE;
+    TenantSlot* ten = ix.tenants + d;
+    const uint32_t base = ten->base, buckets = ten->buckets;
+    uint32_t node = 0;
+    unsigned long long slot_abs = 0;
+    bool at_root = true, is_hash = false, ok = true;
+    for_each_level(qb, k.esc, k.esc_end, [&](unsigned long long lstart, uint32_t len, const LevelHash& h, const uint32_t* inl, bool last) {
+        if (level_is_hash(qb, lstart, len, last)) {
+            is_hash = true;
+            return false;
+        }
+        const uint32_t tok = level_is_plus(qb, lstart, len) ? TOK_PLUS : dict_intern(ix, h, len, inl, qb, lstart, false);
+        bool created;
+        unsigned long long sa = 0;
+        const uint32_t child = tok == TOK_UNKNOWN ? NONE : trie_child(ix, ten, base, buckets, node, at_root ? PARENT_IS_ROOT : slot_abs, tok, false, sa, created);
+        if (child == NONE) {
+            ok = false;
+            return false;
+        }
+        node = child;
+        slot_abs = sa;
+        at_root = false;
+        return true;
+    });
+    if (!ok || (at_root && !is_hash)) return NONE;
+    IdSet s;
+    if (at_root) s = IdSet{ten->root_hash_begin, ten->root_hash_count};
+    else s = is_hash ? IdSet{ix.trie[slot_abs].hash_begin, ix.trie[slot_abs].hash_count} : IdSet{ix.trie[slot_abs].own_begin, ix.trie[slot_abs].own_count};
+    if (s.count() == 0) return NONE; // (the begin word of an empty range is a child filter word, not an id)
+    const uint32_t m = idset_find_tail(ix, s, qb, k, tail_hash(qb, k.tail, k.end));
+    return m == NONE ? NONE : idset_at(ix, s, m);
+}
+// key i of a key source -> out[i]; returns whether the key was malformed
+BMQ_HD bool find_keys_one(const DistIndexMut& ix, const KeySource& ks, uint32_t i, uint32_t* out) {
+    const unsigned long long r = ks.refs[i];
+    const unsigned long long off = r & KREF_OFF_MASK, len = r >> KREF_LEN_SHIFT;
+    bool bad = false;
+    out[i] = len ? find_key_one(ix, ks.base, off, off + len, bad) : NONE;
+    return bad;
 }
 // id -> key store reference (0 for ids that are out of range or dead)
 BMQ_HD void gather_ref_one(const DistIndexMut& ix, const uint32_t* ids, uint32_t i, uint32_t id_end, unsigned long long* out) {

@@ -15,7 +15,7 @@
 //   bool prepare(ix, ob), prepare_check(ix, ob, n_dir), bulk_prepare(ix, ob), scan_flags(in, out, n), bulk_tenants(ix, ob, scan),
 //        locate(ix, ob), sort_targets(ob), group(ix, ob), rehash(ix, old_base, old_slots, new_base, new_buckets), tails(ix, tail_pass, n_slots),
 //        dict_rehash(old, old_slots, ix), find(ix, query, tenant_len, filter_len, out, cap), gather_refs(ix, ids, n, out_refs),
-//        gather_bytes(ix, refs, offs, n, out)
+//        gather_bytes(ix, refs, offs, n, out), find_keys(ix, key_source, n, out_ids, n_bad)
 //   std::string err;
 #pragma once
 #include <algorithm>
@@ -455,6 +455,53 @@ public:
             return xfail();
         return true;
     }
+    // ---- key -> id (bmq_routes_find): out_ids[i] = id of the live route whose key is keys[key_off[i] .. key_off[i + 1]), NONE if there is
+    // none.  Read-only: the batch is uploaded into buffers of its own (not the key pool) and every key walks the index as a delete would,
+    // without its side effects (find_key_one).  n_bad = malformed keys (an empty key, descending offsets, what key_parse refuses): the
+    // ids mean nothing then.  find_fits: the buffers hold such a batch already (nothing is allocated or freed by the call).
+    bool find_fits(uint32_t n, uint64_t key_bytes) const { return (size_t)n + 1 <= f_ids_cap && n <= f_refs_cap && key_bytes + 32 <= f_bytes_cap; }
+    bool find_keys(const uint8_t* keys, const uint32_t* key_off, uint32_t n, uint32_t* out_ids, uint32_t& n_bad) {
+        error.clear();
+        n_bad = 0;
+        if (n == 0) return true;
+        std::vector<unsigned long long> refs(n);
+        const uint32_t k0 = key_off[0];
+        for (uint32_t i = 0; i < n; i++) {
+            if (key_off[i + 1] <= key_off[i] || key_off[i + 1] - key_off[i] >= (1u << (64 - KREF_LEN_SHIFT))) { // (a reference holds 24 bits of length)
+                n_bad++;
+                continue;
+            }
+            refs[i] = (unsigned long long)(key_off[i] - k0) | ((unsigned long long)(key_off[i + 1] - key_off[i]) << KREF_LEN_SHIFT);
+        }
+        if (n_bad) return true;
+        if (!built) { // no index: nothing is live, and a malformed key is still the caller's error (the parser the lookup runs, on the host)
+            for (uint32_t i = 0; i < n; i++) {
+                KeyView k;
+                n_bad += key_parse(keys, key_off[i], key_off[i + 1], k) ? 0u : 1u;
+            }
+            std::fill(out_ids, out_ids + n, NONE);
+            return true;
+        }
+        const uint64_t kb = key_off[n] - k0;
+        if (dir_dirty && !flush_directory()) return false;
+        if (!ensure_buf(f_bytes, f_bytes_cap, kb + 32) || !ensure_buf(f_refs, f_refs_cap, n) || !ensure_buf(f_ids, f_ids_cap, (size_t)n + 1)) return false;
+        std::vector<uint32_t> got((size_t)n + 1);
+        if (!x.copy_in_async(f_bytes, keys + k0, kb) || !x.copy_in_async(f_refs, refs.data(), sizeof(unsigned long long) * (size_t)n) ||
+            !x.zero(f_ids + n, sizeof(uint32_t)) || !x.find_keys(mut(), KeySource{f_bytes, f_refs}, n, f_ids, f_ids + n) ||
+            !x.copy_out(got.data(), f_ids, sizeof(uint32_t) * ((size_t)n + 1)))
+            return xfail();
+        n_bad = got[n];
+        memcpy(out_ids, got.data(), sizeof(uint32_t) * (size_t)n);
+        return true;
+    }
+    // the same for keys that lie in exec memory already (the carry of the member tables of shared subscriptions, bmq_share.h: the keys are
+    // another generation's, read through its own references), on the executor `on`; *n_bad (exec memory, zeroed by the caller) += malformed keys
+    template <class X> bool find_keys_in(X& on, const KeySource& ks, uint32_t n, uint32_t* out_ids, uint32_t* n_bad) {
+        error.clear();
+        if (n == 0 || !built) return true;
+        if (dir_dirty && !flush_directory()) return false;
+        return on.find_keys(mut(), ks, n, out_ids, n_bad) ? true : fail(on.err.empty() ? "exec failure" : on.err);
+    }
     // ---- generation change: THIS index (the generation being built, behind reserve_like(old)) takes the live keys among old's ids [lo, hi).
     // Two steps, so that the caller needs to keep `old` still only for the first.  import_snapshot ENQUEUES a copy of old's key references
     // kref[lo, hi) on this index's executor (the caller ordered it behind whatever old was told so far) and notes where old's key bytes
@@ -693,6 +740,8 @@ public:
         rel(s_key_off); rel(s_op); rel(s_put_rank); rel(s_dir_slot); rel(s_nn); rel(s_flag); rel(s_target); rel(s_order);
         rel(s_sorted_target); rel(s_group_done); rel(s_unknown); rel(s_grow); rel(s_bt_first); rel(s_bt_nodes); rel(s_bt_keys); rel(s_bt_dir);
         rel(g_ids); rel(g_refs); rel(g_offs); rel(g_bytes); rel(g_census); rel(q_bnd.buf); rel(imp_bnd.buf);
+        rel(f_bytes); rel(f_refs); rel(f_ids);
+        f_bytes_cap = f_refs_cap = f_ids_cap = 0;
         q_bnd = imp_bnd = StagedBoundary{};
         imp_bounded = false;
         trie_cap = trie_used = 0; dir_slots = 0; names_cap = names_used = 0; dict_slots = 0; dpool_cap = 0; rp_cap = 0; id_cap = next_id = 0;
@@ -715,6 +764,10 @@ private:
     size_t g_ids_cap = 0, g_refs_cap = 0, g_offs_cap = 0, g_bytes_cap = 0;
     unsigned long long* g_census = nullptr; // tenant_stats: four counters per directory slot
     size_t g_census_cap = 0;
+    uint8_t* f_bytes = nullptr; // find_keys: the batch's key bytes, references and ids (+ the count of malformed keys)
+    unsigned long long* f_refs = nullptr;
+    uint32_t* f_ids = nullptr;
+    size_t f_bytes_cap = 0, f_refs_cap = 0, f_ids_cap = 0;
     // a boundary in exec memory: [inside keys, their bytes: two 64-bit counters][start key][end key]
     struct StagedBoundary {
         uint8_t* buf = nullptr;

@@ -1032,7 +1032,7 @@ int bmq_engine_create(const bmq_config* cfg, bmq_engine** out) {
     if (const char* v = bmq_env("BMQ_QCAP")) c.wave_queue_cap = (uint32_t)atoi(v); // profiling experiments
     if (const char* v = bmq_env("BMQ_PCAP")) c.wave_pair_cap = (uint32_t)atoi(v);
     if ((c.wave_queue_cap != 0 && c.wave_queue_cap != 128) || (c.wave_pair_cap != 0 && c.wave_pair_cap != 128)) return BMQ_E_INVAL;
-    if (c.region_slack > 64 || c.tail_records > 1 || c.child_filters > 1 || c.retain_builder > 3 || c.retain_builder == 2) return BMQ_E_INVAL;
+    if (c.region_slack > 64 || c.tail_records > 1 || c.child_filters > 1 || c.retain_builder > 3 || c.retain_builder == 2 || c.share_carry > 1) return BMQ_E_INVAL;
     const bool smallest = c.wave_queue_cap == 128 || c.wave_pair_cap == 128;
     c.wave_queue_cap = smallest ? WALK_QC_SMALLEST : WALK_QC_DEFAULT; // (what bmq_config reports back / BatchArgs carries: the geometry in use)
     c.wave_pair_cap = smallest ? WALK_PC_SMALLEST : WALK_PC_DEFAULT;
@@ -1174,6 +1174,13 @@ int bmq_rebuild(bmq_engine* e, const uint8_t* keys, const uint32_t* key_off, uin
     return BMQ_OK;
 }
 
+// bmq_config.share_carry = 1 (bmq_share_engine.inc): the member tables of shared subscriptions through a generation change
+extern "C++" {
+static void share_carry_prepare(bmq_engine* e, bool copy_bytes);
+static void share_carry_finish(bmq_engine* e, bool changed);
+static void share_carry_swap(bmq_engine* e);
+}
+
 int bmq_compact(bmq_engine* e) {
     std::unique_lock<std::recursive_mutex> api_lock;
     if (e) api_lock = std::unique_lock<std::recursive_mutex>(e->api);
@@ -1186,11 +1193,14 @@ int bmq_compact(bmq_engine* e) {
         if (sl.pending) return set_err(e, BMQ_E_STATE, "a batch is in flight: finish / wait for it first");
     if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
     poller_stop_locked(e);
+    const bool carry = e->cfg.share_carry == 1;
+    if (carry) share_carry_prepare(e, true); // (the rebuild happens inside the same object: the tables' key bytes are copied first)
     const bool ok = with_index(e, [&](auto& ix) {
         const bool r = ix.compact();
         if (!r) e->err = ix.error;
         return r;
     });
+    if (carry) share_carry_finish(e, ok);
     if (!ok) return index_error(e, e->err, false);
     e->epoch++;
     return BMQ_OK;
@@ -1420,6 +1430,9 @@ int bmq_compact_swap(bmq_engine* e, uint64_t* out_carried, uint64_t* out_replaye
         (void)next.set_import_boundary(Boundary{}); // (a serving generation: nothing is carried into it any more)
         return true;
     });
+    // bmq_config.share_carry: the member tables of shared subscriptions follow their route keys into the new generation while both
+    // generations are alive -- the lookup reads the key bytes straight from the old generation's pool (streams drained above, poller stopped)
+    if (e->cfg.share_carry == 1) share_carry_swap(e);
     e->dfo.reset(); // (the fan-out grouping state belongs to the index it was built over: it holds a reference to it)
     e->hfo.reset();
     if (e->dix) e->dix.swap(c.next_d);
@@ -1718,6 +1731,26 @@ int bmq_route_keys(const bmq_engine* ce, const uint32_t* route_ids, uint32_t n, 
     memcpy(out_off, off.data(), sizeof(uint64_t) * ((size_t)n + 1));
     if (off[n] > cap || (off[n] && !out)) return BMQ_E_NOSPACE;
     if (off[n]) memcpy(out, bytes.data(), off[n]);
+    return BMQ_OK;
+}
+
+int bmq_routes_find(const bmq_engine* ce, const uint8_t* keys, const uint32_t* key_off, uint32_t n, uint32_t* out_ids) {
+    bmq_engine* e = const_cast<bmq_engine*>(ce);
+    if (!e || (n && (!keys || !key_off || !out_ids))) return BMQ_E_INVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (int rc_open = complete_apply(e)) return rc_open; // (a batch handed over with bmq_routes_apply_async first)
+    if (n == 0) return BMQ_OK;
+    if (e->device >= 0) HIPCHK(e, hipSetDevice(e->device));
+    uint32_t n_bad = 0;
+    const bool ok = with_index(e, [&](auto& ix) { // (the serving generation, also while a compaction builds the next one)
+        // the batch's buffers grow rarely; a free waits for every stream of the device, so the persistent matcher leaves first then
+        if (e->device >= 0 && ix.built && !ix.find_fits(n, (uint64_t)key_off[n] - key_off[0])) poller_stop_locked(e);
+        const bool r = ix.find_keys(keys, key_off, n, out_ids, n_bad);
+        if (!r) e->err = ix.error;
+        return r;
+    });
+    if (!ok) return index_error(e, e->err, false);
+    if (n_bad) return set_err(e, BMQ_E_INVAL, "malformed route key in bmq_routes_find");
     return BMQ_OK;
 }
 

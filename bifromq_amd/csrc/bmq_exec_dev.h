@@ -92,6 +92,22 @@ __global__ __launch_bounds__(BK) void k_b_dict_rehash(const DictSlot* old, uint3
 __global__ __launch_bounds__(64) void k_b_find(DistIndexMut ix, const uint8_t* q, uint32_t tenant_len, uint32_t filter_len, uint32_t* out, uint32_t cap) {
     if (threadIdx.x == 0 && blockIdx.x == 0) find_copy(ix, q, tenant_len, filter_len, out, cap);
 }
+// Route keys -> route ids (find_key_one, bmq_build_core.h): one lane per key, laid out as k_b_locate lays its ops out -- the walk is a
+// chain of dependent probes per key, bound by memory latency, and the occupancy comes from the number of keys.  The keys lie in a device
+// buffer given as (base, references): the upload of a bmq_routes_find call, or the key pool of another generation of the index through its
+// own kref entries (Share::carry).  Read-only on the index, no LDS, no cross-lane traffic but the count of malformed keys: a ballot per
+// round, kept in a register, ONE atomic per wave and launch.  A bounded grid that strides (FIND_BLOCKS one-wave workgroups at most: sixteen
+// per CU).
+constexpr uint32_t FIND_BLOCKS = 4096;
+__global__ __launch_bounds__(BK) void k_b_find_keys(DistIndexMut ix, KeySource ks, uint32_t n, uint32_t* out, uint32_t* n_bad) {
+    uint32_t bad = 0; // the wave's (the same in every lane)
+    for (unsigned long long base = (unsigned long long)blockIdx.x * BK; base < n; base += (unsigned long long)gridDim.x * BK) {
+        const unsigned long long i = base + threadIdx.x;
+        const bool b = i < n ? find_keys_one(ix, ks, (uint32_t)i, out) : false;
+        bad += (uint32_t)__popcll(__ballot(b));
+    }
+    if (threadIdx.x == 0 && bad != 0) atomicAdd(n_bad, bad);
+}
 __global__ __launch_bounds__(256) void k_b_gather_refs(DistIndexMut ix, const uint32_t* ids, uint32_t n, uint32_t id_end, unsigned long long* out) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) gather_ref_one(ix, ids, i, id_end, out);
@@ -442,6 +458,12 @@ struct DevExec {
         hipLaunchKernelGGL(k_b_find, dim3(1), dim3(64), 0, stream, ix, q, tenant_len, filter_len, out, cap);
         return launched();
     }
+    // out[i] = id of the live route whose key is key i of `ks`, NONE if there is none; *n_bad += malformed keys (the caller zeroes it)
+    bool find_keys(const DistIndexMut& ix, const KeySource& ks, uint32_t n, uint32_t* out, uint32_t* n_bad) {
+        if (n == 0) return true;
+        hipLaunchKernelGGL(k_b_find_keys, dim3((unsigned)std::min<unsigned long long>(((unsigned long long)n + BK - 1) / BK, FIND_BLOCKS)), dim3(BK), 0, stream, ix, ks, n, out, n_bad);
+        return launched();
+    }
     // ---- fan-out grouping (bmq_fanout.h) ----
     bool fill_bytes(void* p, int byte, size_t n) { return n == 0 || BMQ_X(hipMemsetAsync(p, byte, n, stream)); }
     bool fo_fill(const DistIndexMut& ix, const FanoutState& st, const FanoutBatch& b) {
@@ -567,6 +589,11 @@ struct DevExec {
     }
     bool sh_groups(const ShareTables& T, const ShareBatch& b) {
         hipLaunchKernelGGL(k_sh_groups, grid(b.n_rows, SH_BLOCK), dim3(SH_BLOCK), 0, stream, T, b);
+        return launched();
+    }
+    bool sh_rekey(uint32_t* slot_of, uint32_t id_cap, const uint32_t* new_id, const uint32_t* slot, uint32_t n) {
+        if (n == 0) return true;
+        hipLaunchKernelGGL(k_sh_rekey, grid(n, SH_BLOCK), dim3(SH_BLOCK), 0, stream, slot_of, id_cap, new_id, slot, n);
         return launched();
     }
     // ---- retain direction (bmq_retain_core.h) ----

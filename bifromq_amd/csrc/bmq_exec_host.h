@@ -135,6 +135,15 @@ struct HostExec {
         find_copy(ix, q, tenant_len, filter_len, out, cap);
         return true;
     }
+    // out[i] = id of the live route whose key is key i of `ks`, NONE if there is none; *n_bad += malformed keys (k_b_find_keys on the device)
+    bool find_keys(const DistIndexMut& ix, const KeySource& ks, uint32_t n, uint32_t* out, uint32_t* n_bad) {
+        std::atomic<uint32_t> bad{0};
+        par(n, [&](size_t i) {
+            if (find_keys_one(ix, ks, (uint32_t)i, out)) bad.fetch_add(1, std::memory_order_relaxed);
+        });
+        *n_bad += bad.load();
+        return true;
+    }
     // ---- fan-out grouping (bmq_fanout.h) ----
     static constexpr bool has_fanout_fast = false; // the counting-sort path is gfx950 kernels only; host engines take the generic passes
     bool fill_bytes(void* p, int byte, size_t n) {
@@ -232,6 +241,10 @@ struct HostExec {
     }
     bool sh_groups(const ShareTables& T, const ShareBatch& b) {
         par(b.n_rows, [&](size_t j) { sh_group_one(T, b, (uint32_t)j); });
+        return true;
+    }
+    bool sh_rekey(uint32_t* slot_of, uint32_t id_cap, const uint32_t* new_id, const uint32_t* slot, uint32_t n) {
+        par(n, [&](size_t i) { sh_rekey_one(slot_of, id_cap, new_id, slot, (uint32_t)i); });
         return true;
     }
     // ---- retain direction (bmq_retain_core.h) ----

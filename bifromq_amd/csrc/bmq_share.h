@@ -2,8 +2,10 @@
 // on the engine stream; HostExec: host threads, for host-only engines and the CPU tests): the member tables in exec memory with their
 // host mirror (the mutation path: URLs are parsed, words mixed and share-deliverer numbers handed out on the host) and the passes of a
 // resolve.  Besides what the fan-out grouping needs (bmq_fanout.h) the Exec provides
-//   bool sh_count(ix, T, b), sh_rows(T, b), sh_resolve(T, b, width), sh_heads(b, emit), sh_groups(T, b); void mark(i); float mark_ms(i, j)
-// Tables are keyed by route id: they belong to ONE generation of the route index and are dropped when it changes.
+//   bool sh_count(ix, T, b), sh_rows(T, b), sh_resolve(T, b, width), sh_heads(b, emit), sh_groups(T, b), sh_rekey(slot_of, id_cap, new_id, slot, n),
+//        find_keys(ix, key_source, n, out_ids, n_bad); void mark(i); float mark_ms(i, j)
+// Tables are keyed by route id: they belong to ONE generation of the route index and are dropped when it changes -- unless the engine
+// carries them along (bmq_config.share_carry: carry_prepare / carry_finish below move each table to the id its route KEY has next).
 #pragma once
 #include <functional>
 #include <unordered_map>
@@ -240,7 +242,132 @@ public:
         return true;
     }
 
+    // ---- the carry through a generation change of the route index (bmq_config.share_carry) -------------------------------------------
+    // The member data -- pools, descriptors, share-deliverer numbers -- does not depend on route ids; the directory slot_of[route id] and
+    // the keys of the host mirror do.  A table follows its route KEY: old id -> key reference in the old generation (gather_refs) -> id in
+    // the new generation (find_keys reads the key bytes where they lie: the old generation's key pool, or -- bmq_compact rebuilds inside
+    // the same object -- a copy of those keys taken before) -> one uint32 per table comes back, the mirror is re-keyed and the directory
+    // rewritten by k_sh_rekey.  A table whose route is dead or has no id in the new generation is dropped.
+    //   carry_prepare(old, copy_bytes)   before the generation changes; copy_bytes: `old` itself is about to be rebuilt
+    //   carry_finish(next)               `next` serves from here on (old, if it is another object, is still alive)
+    //   carry_cancel()                   the generation change failed before anything changed
+    // A failure of the executor half-way follows the rule of apply: every table goes, and the error string says so.
+    struct CarryInfo {
+        uint64_t from_generation = 0, to_generation = 0, n_carried = 0, n_dropped = 0, n_members_carried = 0;
+        float ms_gather = 0, ms_find = 0, ms_rekey = 0;
+        uint32_t status = 0; // 0 none, 1 carried, 2 failed: every table was dropped
+    } carry_info;
+    bool carry_prepare(DistIndex<Exec>& old, bool copy_bytes) {
+        cy = Carry{};
+        if (!old.built) return true;
+        if (!sync_generation(old)) return carry_failed(old.generation, 0, error);
+        cy.active = true;
+        cy.from = old.generation;
+        for (const auto& kv : tabs) cy.ids.push_back(kv.first);
+        std::sort(cy.ids.begin(), cy.ids.end());
+        const uint32_t n = (uint32_t)cy.ids.size();
+        if (n == 0) return true;
+        cy.src = old.kpool;
+        x.mark(0);
+        if (!carry_buf(c_ids, c_ids_cap, n) || !carry_buf(c_refs, c_refs_cap, n) || !carry_buf(c_new, c_new_cap, (size_t)n + 1) || !carry_buf(c_slot, c_slot_cap, n))
+            return carry_failed(cy.from, 0, error);
+        if (!x.copy_in(c_ids, cy.ids.data(), sizeof(uint32_t) * (size_t)n) || !x.gather_refs(old.mut(), c_ids, n, old.next_id, c_refs)) return carry_failed(cy.from, 0, xerr());
+        if (copy_bytes) { // the key bytes of the tables' routes into a buffer of this object: the references (8 bytes per table) visit the host for the offsets
+            std::vector<unsigned long long> refs(n), moved(n);
+            std::vector<uint64_t> offs((size_t)n + 1, 0);
+            if (!x.copy_out(refs.data(), c_refs, sizeof(unsigned long long) * (size_t)n)) return carry_failed(cy.from, 0, xerr());
+            for (uint32_t i = 0; i < n; i++) {
+                const uint64_t len = refs[i] >> KREF_LEN_SHIFT;
+                moved[i] = offs[i] | (len << KREF_LEN_SHIFT);
+                offs[i + 1] = offs[i] + len;
+            }
+            if (!carry_buf(c_offs, c_offs_cap, (size_t)n + 1) || !carry_buf(c_bytes, c_bytes_cap, offs[n] + 32)) return carry_failed(cy.from, 0, error);
+            if (!x.copy_in(c_offs, offs.data(), sizeof(uint64_t) * ((size_t)n + 1)) || !x.gather_bytes(old.mut(), c_refs, c_offs, n, c_bytes) ||
+                !x.copy_in(c_refs, moved.data(), sizeof(unsigned long long) * (size_t)n))
+                return carry_failed(cy.from, 0, xerr());
+            cy.src = c_bytes;
+        }
+        x.mark(1);
+        if (!x.sync()) return carry_failed(cy.from, 0, xerr());
+        cy.ms_gather = x.mark_ms(0, 1);
+        return true;
+    }
+    void carry_cancel() { cy = Carry{}; }
+    bool carry_finish(DistIndex<Exec>& next) {
+        if (cy.failed) { // carry_prepare dropped every table: nothing of the old generation is left to drop later
+            carry_info.to_generation = generation = next.generation;
+            cy = Carry{};
+            return false;
+        }
+        if (!cy.active) return true;
+        Carry c = std::move(cy);
+        cy = Carry{};
+        CarryInfo ci;
+        ci.from_generation = c.from;
+        ci.to_generation = next.generation;
+        ci.ms_gather = c.ms_gather;
+        ci.status = 1;
+        const uint32_t n = (uint32_t)c.ids.size();
+        if (n != 0) {
+            std::vector<uint32_t> nid((size_t)n + 1, SH_NONE);
+            x.mark(2);
+            if (!x.fill_bytes(c_new, 0xFF, sizeof(uint32_t) * (size_t)n) || !x.zero(c_new + n, sizeof(uint32_t))) return carry_failed(c.from, next.generation, xerr());
+            if (!next.find_keys_in(x, KeySource{c.src, c_refs}, n, c_new, c_new + n)) return carry_failed(c.from, next.generation, next.error);
+            x.mark(3);
+            if (!x.copy_out(nid.data(), c_new, sizeof(uint32_t) * ((size_t)n + 1))) return carry_failed(c.from, next.generation, xerr());
+            ci.ms_find = x.mark_ms(2, 3);
+            // (nid[n]: keys the new generation's parser refused -- none: they were parsed when they went into the old one)
+            // ---- the host mirror ----
+            std::unordered_map<uint32_t, HostTable> moved;
+            for (uint32_t i = 0; i < n; i++) {
+                auto it = tabs.find(c.ids[i]);
+                if (it == tabs.end()) continue;
+                if (nid[i] >= next.next_id || moved.count(nid[i])) { // dead, outside the boundary of a bounded swap, or not there
+                    nid[i] = SH_NONE;
+                    ci.n_dropped++;
+                    n_members -= it->second.urls.size();
+                    free_slots.push_back(it->second.slot);
+                    continue;
+                }
+                ci.n_carried++;
+                ci.n_members_carried += it->second.urls.size();
+                moved.emplace(nid[i], std::move(it->second));
+            }
+            tabs.swap(moved);
+        }
+        // ---- the directory: the new generation's id capacity, all SH_NONE, then the (new id, slot) pairs ----
+        x.mark(4);
+        if (!tabs.empty() || d_slot_of) {
+            if (next.id_cap > slot_cap) {
+                const uint32_t cap = next.id_cap + next.id_cap / 4 + 64;
+                if (!fresh(d_slot_of, cap)) return carry_failed(c.from, next.generation, error);
+                slot_cap = cap;
+            }
+            if (!x.fill_bytes(d_slot_of, 0xFF, sizeof(uint32_t) * (size_t)slot_cap)) return carry_failed(c.from, next.generation, xerr());
+            h_slot_of.assign(slot_cap, SH_NONE);
+        }
+        if (n != 0) {
+            std::vector<uint32_t> nid(n), slots(n);
+            uint32_t w = 0;
+            for (const auto& kv : tabs) nid[w] = kv.first, slots[w] = kv.second.slot, h_slot_of[kv.first] = kv.second.slot, w++;
+            if (w != 0 && (!x.copy_in(c_new, nid.data(), sizeof(uint32_t) * (size_t)w) || !x.copy_in(c_slot, slots.data(), sizeof(uint32_t) * (size_t)w) ||
+                           !x.sh_rekey(d_slot_of, slot_cap, c_new, c_slot, w)))
+                return carry_failed(c.from, next.generation, xerr());
+        }
+        x.mark(5);
+        if (!x.sync()) return carry_failed(c.from, next.generation, xerr());
+        ci.ms_rekey = x.mark_ms(4, 5);
+        generation = next.generation;
+        carry_info = ci;
+        return true;
+    }
+
     void drop() {
+        for (uint32_t** p : {&c_ids, &c_new, &c_slot}) rel(*p);
+        rel(c_refs);
+        rel(c_offs);
+        rel(c_bytes);
+        c_ids_cap = c_refs_cap = c_new_cap = c_slot_cap = c_offs_cap = c_bytes_cap = 0;
         rel(totals);
         for (uint32_t** p : {&d_slot_of, &d_pool32, &flags, &s_slot, &s_cnt, &s_cnt_scan, &s_row_pair, &s_row_sender, &s_row_member, &s_key, &s_key_sorted, &s_pos, &s_pos_sorted})
             rel(*p);
@@ -281,6 +408,47 @@ private:
     uint32_t *s_row_pair = nullptr, *s_row_sender = nullptr, *s_row_member = nullptr, *s_key = nullptr, *s_key_sorted = nullptr, *s_pos = nullptr, *s_pos_sorted = nullptr;
     size_t p_cap = 0, r_cap = 0;
     float last_ms[5] = {0, 0, 0, 0, 0};
+    // the carry: what carry_prepare notes for carry_finish, and its exec memory -- per table its old id, its key reference, its new id
+    // (+ one word: malformed keys), its slot; for bmq_compact the offsets and the bytes of the copied keys
+    struct Carry {
+        bool active = false, failed = false;
+        uint64_t from = 0;
+        std::vector<uint32_t> ids; // ascending
+        const uint8_t* src = nullptr; // where the key bytes lie
+        float ms_gather = 0;
+    } cy;
+    uint32_t *c_ids = nullptr, *c_new = nullptr, *c_slot = nullptr;
+    unsigned long long* c_refs = nullptr;
+    uint64_t* c_offs = nullptr;
+    uint8_t* c_bytes = nullptr;
+    size_t c_ids_cap = 0, c_new_cap = 0, c_slot_cap = 0, c_refs_cap = 0, c_offs_cap = 0, c_bytes_cap = 0;
+    template <class T> bool carry_buf(T*& p, size_t& cap, size_t need) { // grow-only, contents dropped; freed through the before_free hook
+        if (need <= cap) return true;
+        cap = 0;
+        if (!fresh(p, need + need / 4 + 64)) return false;
+        cap = need + need / 4 + 64;
+        return true;
+    }
+    std::string xerr() const { return x.err.empty() ? "exec failure" : x.err; }
+    // the rule of apply: mirror and device may be out of step, so every table goes rather than a directory that names the wrong members
+    bool carry_failed(uint64_t from, uint64_t to, const std::string& why) {
+        rel(d_slot_of);
+        rel(d_desc);
+        rel(d_pool64);
+        rel(d_pool32);
+        slot_cap = 0;
+        desc_cap = cap64 = cap32 = 0;
+        h_slot_of.clear();
+        clear_host();
+        cy = Carry{};
+        cy.failed = to == 0; // (carry_prepare failed: carry_finish records the generation that follows)
+        carry_info = CarryInfo{};
+        carry_info.from_generation = from;
+        carry_info.to_generation = to;
+        carry_info.status = 2;
+        if (to) generation = to;
+        return fail(why + " (all member tables were dropped)");
+    }
 
     ShareTables tables() const {
         ShareTables T{};

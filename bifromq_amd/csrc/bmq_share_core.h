@@ -119,6 +119,11 @@ BMQ_HD uint32_t sh_slot_of(const DistIndexMut& ix, const ShareTables& T, const S
     if (ix.kref[id] == 0) return SH_NONE; // deleted since
     return T.slot_of[id];
 }
+// a carried table's entry in the directory of the new generation (Share::carry): new_id[i] = the id its route key has there, SH_NONE = not found
+BMQ_HD void sh_rekey_one(uint32_t* slot_of, uint32_t id_cap, const uint32_t* new_id, const uint32_t* slot, uint32_t i) {
+    const uint32_t id = new_id[i];
+    if (id < id_cap) slot_of[id] = slot[i];
+}
 BMQ_HD uint32_t sh_senders_of(const ShareBatch& b, uint32_t t, uint32_t& first) {
     const uint32_t lo = b.sender_off[t], hi = b.sender_off[t + 1];
     first = lo;

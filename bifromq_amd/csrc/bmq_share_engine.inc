@@ -25,6 +25,53 @@ int share_result(bmq_engine* e, const ShareResult& r, uint32_t* out_n_rows, uint
 }
 } // namespace
 
+// ---- bmq_config.share_carry = 1: called by bmq_compact / bmq_compact_swap under the locks they hold, with the poller stopped.  A carry that
+// fails drops every table and leaves its message in the error string; the generation change goes on.
+namespace {
+DistIndex<DevExec>& next_generation(bmq_engine* e, DistIndex<DevExec>&) { return *e->cmp.next_d; }
+DistIndex<HostExec>& next_generation(bmq_engine* e, DistIndex<HostExec>&) { return *e->cmp.next_h; }
+} // namespace
+static void share_carry_prepare(bmq_engine* e, bool copy_bytes) {
+    (void)with_share(e, [&](auto& sh, auto& ix) {
+        if (!sh.carry_prepare(ix, copy_bytes)) e->err = sh.error;
+        return 0;
+    });
+}
+static void share_carry_finish(bmq_engine* e, bool changed) {
+    (void)with_share(e, [&](auto& sh, auto& ix) {
+        if (!changed) sh.carry_cancel();
+        else if (!sh.carry_finish(ix)) e->err = sh.error;
+        return 0;
+    });
+}
+static void share_carry_swap(bmq_engine* e) {
+    (void)with_share(e, [&](auto& sh, auto& ix) {
+        if (!sh.carry_prepare(ix, false) || !sh.carry_finish(next_generation(e, ix))) e->err = sh.error;
+        return 0;
+    });
+}
+
+extern "C" int bmq_share_carry_info_get(const bmq_engine* ce, bmq_share_carry_info* out) {
+    bmq_engine* e = const_cast<bmq_engine*>(ce);
+    if (!e || !out) return BMQ_E_INVAL;
+    std::unique_lock<std::recursive_mutex> api_lock(e->api);
+    std::lock_guard<std::mutex> g(e->mu);
+    memset(out, 0, sizeof(*out));
+    return with_share(e, [&](auto& sh, auto&) {
+        const auto& ci = sh.carry_info;
+        out->from_generation = ci.from_generation;
+        out->to_generation = ci.to_generation;
+        out->n_carried = ci.n_carried;
+        out->n_dropped = ci.n_dropped;
+        out->n_members_carried = ci.n_members_carried;
+        out->ms_gather = ci.ms_gather;
+        out->ms_find = ci.ms_find;
+        out->ms_rekey = ci.ms_rekey;
+        out->status = ci.status;
+        return (int)BMQ_OK;
+    });
+}
+
 extern "C" int bmq_share_members_apply(bmq_engine* e, const uint32_t* route_ids, uint32_t n, const uint32_t* member_off, const uint8_t* urls,
                                        const uint32_t* url_off) {
     if (!e) return BMQ_E_INVAL;

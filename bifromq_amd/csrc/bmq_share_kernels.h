@@ -72,5 +72,11 @@ __global__ __launch_bounds__(SH_BLOCK) void k_sh_groups(ShareTables T, ShareBatc
     const uint32_t j = blockIdx.x * SH_BLOCK + threadIdx.x;
     if (j < b.n_rows) sh_group_one(T, b, j);
 }
+// the directory of a new generation of the route index (Share::carry): table i goes to the id its route key has there.  One lane per
+// carried table into a directory filled with SH_NONE before; the ids are distinct (a key has one id), so no two lanes write one word.
+__global__ __launch_bounds__(SH_BLOCK) void k_sh_rekey(uint32_t* slot_of, uint32_t id_cap, const uint32_t* new_id, const uint32_t* slot, uint32_t n) {
+    const uint32_t i = blockIdx.x * SH_BLOCK + threadIdx.x;
+    if (i < n) sh_rekey_one(slot_of, id_cap, new_id, slot, i);
+}
 
 } // namespace bmq

@@ -185,7 +185,7 @@ class Engine:
 
     def __init__(self, device: int = 0, wave_queue_cap: int = 0, wave_pair_cap: int = 0, slow_scratch_mb: int = 0, kernel_timing: bool = False,
                  dedup_min_topics: int = 0, dedup_sorted: bool = False, region_slack: int = 0,
-                 tail_records: int = 0, child_filters: int = 0, retain_builder: int = 0):
+                 tail_records: int = 0, child_filters: int = 0, retain_builder: int = 0, share_carry: int = 0):
         L = _lib.lib()
         cfg = _lib.Config()
         cfg.struct_size = C.sizeof(_lib.Config)
@@ -200,6 +200,7 @@ class Engine:
         cfg.tail_records = tail_records  # 0: default (tail records on); 1: off
         cfg.child_filters = child_filters  # 0: default (the walk reads the nodes' child filter words); 1: it ignores them
         cfg.retain_builder = retain_builder  # 0: default (the host builder bulk-loads the retained-topic index); 1: the executor builder; 3: it also serves retain_compact_begin / _build / _swap
+        cfg.share_carry = share_carry  # 0: default (a generation change of the route index drops the member tables of shared subscriptions); 1: compact / compact_swap carry them to the ids their route keys get
         h = C.c_void_p()
         rc = L.bmq_engine_create(C.byref(cfg), C.byref(h))
         if rc:
@@ -384,6 +385,15 @@ class Engine:
             self._check(rc)
             raw = out.tobytes()
             return [raw[int(off[i]):int(off[i + 1])] for i in range(n)]
+
+    def find_routes(self, keys: Sequence[bytes] = (), packed: Optional[Tuple[np.ndarray, np.ndarray]] = None) -> np.ndarray:
+        """bmq_routes_find: the id of the live route with each key (0xFFFFFFFF: there is none), looked up where the index lives; read-only.
+        A malformed key raises BmqError(-1)."""
+        data, off = pack(list(keys)) if packed is None else packed
+        n = len(off) - 1
+        out = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+        self._check(_lib.lib().bmq_routes_find(self.h, _ptr(data), _ptr(off), n, _ptr(out)))
+        return out
 
     def find(self, tenant, topic_filter) -> List[int]:
         t, f = _b(tenant), _b(topic_filter)
@@ -644,6 +654,12 @@ class Engine:
     def share_info(self) -> _lib.ShareInfo:
         out = _lib.ShareInfo()
         self._check(_lib.lib().bmq_share_info_get(self.h, C.byref(out)))
+        return out
+
+    def share_carry_info(self) -> _lib.ShareCarryInfo:
+        """bmq_share_carry_info_get: what the last generation change that ran with share_carry = 1 did with the member tables"""
+        out = _lib.ShareCarryInfo()
+        self._check(_lib.lib().bmq_share_carry_info_get(self.h, C.byref(out)))
         return out
 
     def finish(self) -> int:

@@ -100,7 +100,10 @@ typedef struct bmq_config {
                                /* generation.  3 = 1, and the executor builder also serves the generation change that does not stop the world,       */
                                /* bmq_retain_compact_begin[_in] / _build / _swap (see there); under 0 and 1 those three stay the host builder's.      */
                                /* Any other value (2 included: the generation change needs the bulk loader): BMQ_E_INVAL                              */
-    uint32_t reserved[1];
+    uint32_t share_carry;      /* what a generation change of the route index does with the member tables of shared subscriptions                      */
+                               /* (bmq_share_members_apply): 0 = default = they are dropped; 1 = bmq_compact and bmq_compact_swap carry every table to  */
+                               /* the id its route KEY has in the new generation, on the device (see bmq_share_members_apply, bmq_share_carry_info_get). */
+                               /* Any other value: BMQ_E_INVAL                                                                                          */
 } bmq_config;
 
 /* Counters of the last completed match batch (for roofline accounting). */
@@ -165,6 +168,19 @@ int bmq_routes_apply(bmq_engine* e, const uint8_t* keys, const uint32_t* key_off
  * bmq_routes_apply[_async] completes the first. */
 int bmq_routes_apply_async(bmq_engine* e, const uint8_t* keys, const uint32_t* key_off, const uint8_t* op, uint32_t n);
 int bmq_routes_apply_wait(bmq_engine* e);
+
+/* Route keys -> route ids, batched, where the index lives: out_ids[i] = id of the live route whose key equals keys[key_off[i] .. key_off[i + 1]),
+ * 0xFFFFFFFF if there is none.  Keys are in the layout bmq_rebuild / bmq_routes_apply take, any flag (1 / 2 / 3), in any order, repeats
+ * included (the packed bytes need no padding).  This is how a caller learns the ids of the keys it put: bmq_routes_apply says only that the
+ * j-th put THAT ADDS A ROUTE gets next_route_id + j.  A malformed key fails the call with BMQ_E_INVAL, as it fails bmq_routes_apply; n = 0
+ * returns BMQ_OK.  The call is read-only: one lane per key walks the index on the device (k_b_find_keys: the read-only half of what a
+ * delete does) and creates no dictionary token, no trie node and no filter bit, invalidates no tail record and leaves the epoch alone.
+ * Locks and state are those of bmq_route_keys / bmq_routes_count_in: an open bmq_routes_apply_async batch is completed first; while a
+ * compaction runs the SERVING generation answers (keys mutated since bmq_compact_begin included); the persistent matcher keeps running (it leaves only
+ * when the call's own upload buffers have to grow -- the first call and every larger batch: a free waits for every stream of the device).  A key
+ * of 16 MiB or more is malformed.
+ * A host-only engine runs the same per-key function on host threads. */
+int bmq_routes_find(const bmq_engine* e, const uint8_t* keys, const uint32_t* key_off, uint32_t n, uint32_t* out_ids);
 
 /* Maintenance: re-build the index from its own live routes (the keys are gathered from the HBM key store).  Frees what churn leaves
  * behind until then -- abandoned tenant regions and id lists, trie nodes and dictionary tokens of filters nobody subscribes to any
@@ -674,9 +690,18 @@ int bmq_fanout_info_get(const bmq_engine* e, bmq_fanout_info* out);
  *   changes it is checked (BMQ_E_INVAL) that every id is a live route of flag 2 or 3, that every URL has exactly the three NUL-separated
  *   parts, and that no list has more than 65 535 members.  Ordered or not comes from the route key's flag.  The tables live in device
  *   memory (bmq_share_info.device_bytes), pre-mixed for the hash (bifromq_amd/csrc/bmq_share_core.h).  They are keyed by route id, so they
- *   belong to ONE generation of the route index: bmq_rebuild, bmq_compact and bmq_compact_swap drop them all (the caller reloads the KV
- *   range then anyway), and bmq_share_info.generation says which generation the tables belong to.  A route deleted by bmq_routes_apply
- *   leaves its table unreachable (its id is dead).  Every distinct (subBrokerId, delivererKey) among the members of a generation gets a
+ *   belong to ONE generation of the route index, and bmq_share_info.generation says which.  bmq_rebuild drops them all: the caller reloads
+ *   the KV range then and has the group values in hand.  bmq_compact and bmq_compact_swap (after bmq_compact_begin and after
+ *   bmq_compact_begin_in) change the generation WITHOUT a KV scan, and by default (bmq_config.share_carry = 0) they drop every table too:
+ *   all $share / $oshare rows come back unresolved until the caller has pushed every group value through this call again.  With
+ *   bmq_config.share_carry = 1 they carry the tables instead: each one moves to the id its route KEY has in the new generation (old id ->
+ *   key -> new id, looked up on the device: the keys never leave HBM); a table whose route is dead, lies outside the boundary of a bounded
+ *   swap or is otherwise not found there is dropped (its members leave bmq_share_info.n_members; the pools keep the garbage until they are
+ *   next re-laid, as replaced tables do).  Member order, the ordered / unordered flag, the URLs and the share-deliverer numbers stay as
+ *   they are (n_deliverers does not change), bmq_share_info.generation becomes the new generation, and bmq_share_carry_info_get reports
+ *   what the last carry did.  If the executor fails half-way every table is dropped (the generation change itself succeeds).
+ *   bmq_routes_import moves no tables between engines.  A route deleted by bmq_routes_apply leaves its table unreachable (its id is
+ *   dead; a put of the same key later is another route: the table does not come back).  Every distinct (subBrokerId, delivererKey) among the members of a generation gets a
  *   dense share-deliverer number (exact byte comparison); members that differ only in receiverId share one.
  *
  * bmq_share_resolve: in : n_pairs (topic index, route id) pairs -- typically the slice out_group_off[g] .. out_group_off[g + 1] of the
@@ -721,6 +746,15 @@ int bmq_share_resolve_dev(bmq_engine* e, const uint32_t* d_pair_topic, const uin
 /* receiverUrl of member `index` of the route's table -> out_url[*out_len]; BMQ_E_INVAL: no such table / member; BMQ_E_NOSPACE: cap < *out_len */
 int bmq_share_member(const bmq_engine* e, uint32_t route_id, uint32_t index, uint8_t* out_url, uint32_t cap, uint32_t* out_len);
 int bmq_share_info_get(const bmq_engine* e, bmq_share_info* out);
+/* What the last generation change that ran with bmq_config.share_carry = 1 did with the member tables. */
+typedef struct bmq_share_carry_info {
+    uint64_t from_generation, to_generation;  /* of the last generation change that ran with share_carry = 1 (0, 0: none yet) */
+    uint64_t n_carried, n_dropped, n_members_carried;
+    float ms_gather, ms_find, ms_rekey;       /* HIP-event times while bmq_set_kernel_timing is on, else 0 */
+    uint32_t status;                          /* 0 none, 1 carried, 2 failed: every table was dropped */
+    uint32_t reserved0;
+} bmq_share_carry_info;
+int bmq_share_carry_info_get(const bmq_engine* e, bmq_share_carry_info* out);
 
 /* ---- dist-server side range pruning ---------------------------------------------------------------------- */
 /* TenantRangeLookupCache.lookup (bifromq-dist/bifromq-dist-server/src/main/java/org/apache/bifromq/dist/server/scheduler/

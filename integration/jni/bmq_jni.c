@@ -28,6 +28,7 @@
 #define NS(name) Java_org_apache_bifromq_retain_store_gpu_NativeStore_##name
 #define NK(name) Java_org_apache_bifromq_retain_store_gpu_NativeKeys_##name
 #define NR(name) Java_org_apache_bifromq_retain_store_gpu_NativeRange_##name
+#define NF(name) Java_org_apache_bifromq_routes_gpu_NativeRoutes_##name
 
 static void throw_state(JNIEnv* env, bmq_engine* e, const char* what, int rc) {
     char msg[512];
@@ -110,6 +111,13 @@ JNIEXPORT void JNICALL NM(routesApply)(JNIEnv* env, jclass c, jlong h, jobject k
     (void)c;
     const int rc = bmq_routes_apply(ENGINE(h), (const uint8_t*)ADDR(keys), (const uint32_t*)ADDR(keyOff), (const uint8_t*)ADDR(ops), (uint32_t)n);
     if (rc != BMQ_OK) throw_state(env, ENGINE(h), "bmq_routes_apply", rc);
+}
+/* NativeRoutes: void routesFind(long engine, ByteBuffer keys, IntBuffer keyOff, int n, IntBuffer outIds)   bmq_routes_find: route keys -> route
+ * ids (0xFFFFFFFF: no such live route), looked up on the device; read-only.  All buffers DIRECT. */
+JNIEXPORT void JNICALL NF(routesFind)(JNIEnv* env, jclass c, jlong h, jobject keys, jobject keyOff, jint n, jobject outIds) {
+    (void)c;
+    const int rc = bmq_routes_find(ENGINE(h), (const uint8_t*)ADDR(keys), (const uint32_t*)ADDR(keyOff), (uint32_t)n, (uint32_t*)ADDR(outIds));
+    if (rc != BMQ_OK) throw_state(env, ENGINE(h), "bmq_routes_find", rc);
 }
 /* void routesApplyAsync(long engine, ByteBuffer keys, IntBuffer keyOff, ByteBuffer ops, int n) / void routesApplyWait(long engine)
  * bmq_routes_apply_async / _wait: the ops are uploaded beside the batch in flight and applied behind it; the call returns after the enqueue.

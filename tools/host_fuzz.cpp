@@ -11,6 +11,9 @@
 //   * every third round a random KV boundary: count_in and the per-tenant census (tenant_stats) against the model, a bounded generation change (reserve_like with the boundary,
 //     the boundary predicate on every chunk) and an import into a second index (import_refs: unknown tenants, duplicates) against the
 //     model's key set restricted to the boundary.
+//   * after every step bmq_routes_find's per-key lookup (DistIndex::find_keys over find_key_one) against the model's key -> id, absent, deleted and
+//     malformed keys included; member tables of shared subscriptions carried through a bmq_compact and through the generation change
+//     beside the index (Share::carry_prepare / carry_finish) against the model: carried iff the route was not deleted since, at its key's new id.
 // Build + run: make -C bifromq_amd/csrc fuzz   (tests/test_host.py runs short rounds)
 #include <cstdio>
 #include <algorithm>
@@ -26,6 +29,7 @@
 #include "../bifromq_amd/csrc/bmq_dist_index.h"
 #include "../bifromq_amd/csrc/bmq_exec_host.h"
 #include "../bifromq_amd/csrc/bmq_fanout.h"
+#include "../bifromq_amd/csrc/bmq_share.h"
 
 using namespace bmq;
 
@@ -224,6 +228,118 @@ int main(int argc, char** argv) {
     uint64_t checks = 0, n_apply = 0, n_rebuild = 0, fo_pairs = 0, n_generations = 0, n_census = 0, n_bounded = 0, n_imports = 0, plus_stat[2] = {0, 0};
     Fanout<HostExec> fo(hx, h); // fan-out grouping (bmq_fanout.h) over the same index, kept across rebuilds and applies
     fo.initial_table = 4;       // 36 deliverer keys: the group table grows twice
+    // ---- key -> id (bmq_routes_find: DistIndex::find_keys over find_key_one) against the model, after every step: a sample of the live keys, keys
+    // deleted at some point (live again or not: the model decides), random keys, repeats -- and nothing may come into being by looking
+    std::vector<std::string> once_deleted;
+    uint64_t n_find = 0, n_carries = 0, n_tables_carried = 0, n_tables_dropped = 0;
+    auto check_find = [&](int round, const char* what) -> bool {
+        std::vector<std::string> q;
+        size_t pos = 0;
+        for (auto& e : model)
+            if (pos++ % (1 + model.size() / 400) == 0) q.push_back(e.first);
+        for (size_t i = 0; i < 40; i++) q.push_back(rand_key());
+        for (size_t i = 0; i < 40 && !once_deleted.empty(); i++) q.push_back(once_deleted[rnd(once_deleted.size())]);
+        for (size_t i = 0; i < 20; i++) q.push_back(q[rnd(q.size())]);
+        std::shuffle(q.begin(), q.end(), rng);
+        if (once_deleted.size() > 4000) once_deleted.erase(once_deleted.begin(), once_deleted.begin() + 2000);
+        std::vector<uint8_t> qb;
+        std::vector<uint32_t> qo{0};
+        for (auto& k : q) {
+            qb.insert(qb.end(), k.begin(), k.end());
+            qo.push_back((uint32_t)qb.size());
+        }
+        DistIndexStats before, after;
+        h.stats(before);
+        std::vector<uint32_t> got(q.size(), 12345u);
+        uint32_t n_bad = 0;
+        if (!h.find_keys(qb.data(), qo.data(), (uint32_t)q.size(), got.data(), n_bad) || n_bad) { // (the exact bytes: no padding behind the last key)
+            fprintf(stderr, "round %d (%s): find_keys failed (%u malformed): %s\n", round, what, n_bad, h.error.c_str());
+            return false;
+        }
+        for (size_t i = 0; i < q.size(); i++) {
+            auto it = model.find(q[i]);
+            const uint32_t want = it == model.end() ? NONE : it->second;
+            if (got[i] != want) {
+                fprintf(stderr, "round %d (%s): find_keys gives id %u for query %zu, the model %u\n", round, what, got[i], i, want);
+                return false;
+            }
+        }
+        h.stats(after);
+        if (before.n_nodes != after.n_nodes || before.n_tokens != after.n_tokens || before.n_routes != after.n_routes || before.next_id != after.next_id) {
+            fprintf(stderr, "round %d (%s): find_keys changed the index\n", round, what);
+            return false;
+        }
+        std::vector<uint8_t> one(q[0].begin(), q[0].end() - 1); // a malformed key is counted, whatever stands beside it
+        const uint32_t oo[2] = {0, (uint32_t)one.size()};
+        uint32_t id1 = 0;
+        if (!h.find_keys(one.data(), oo, 1, &id1, n_bad) || n_bad != 1) {
+            fprintf(stderr, "round %d (%s): a truncated key was not refused\n", round, what);
+            return false;
+        }
+        n_find += q.size();
+        return true;
+    };
+    // ---- member tables of shared subscriptions through a generation change (bmq_config.share_carry: Share::carry_prepare / carry_finish) ----
+    Share<HostExec> sh(hx);
+    std::map<uint32_t, std::pair<std::string, std::vector<std::string>>> sh_model; // route id -> (its key when the table was given, URLs)
+    auto give_tables = [&](int round) -> bool { // fresh tables for up to 40 group routes of the model
+        sh.drop();
+        sh_model.clear();
+        std::vector<uint32_t> ids, moff{0}, uoff{0};
+        std::vector<uint8_t> urls;
+        for (auto& e : model) {
+            RouteKeyParts kp;
+            if (ids.size() >= 40 || !decode_route_key(e.first, kp) || kp.flag == 1 || rnd(3) == 0) continue;
+            auto& t = sh_model[e.second];
+            t.first = e.first;
+            const size_t n = 1 + rnd(rnd(5) == 0 ? 70 : 4);
+            for (size_t m = 0; m < n; m++) {
+                t.second.push_back(std::to_string(rnd(3)) + std::string("\0", 1) + "r" + std::to_string(m) + std::string("\0", 1) + "dk" + std::to_string(rnd(5)));
+                urls.insert(urls.end(), t.second.back().begin(), t.second.back().end());
+                uoff.push_back((uint32_t)urls.size());
+            }
+            ids.push_back(e.second);
+            moff.push_back((uint32_t)(uoff.size() - 1));
+        }
+        if (!ids.empty() && !sh.apply(h, ids.data(), (uint32_t)ids.size(), moff.data(), urls.data(), uoff.data())) {
+            fprintf(stderr, "round %d: share apply failed: %s\n", round, sh.error.c_str());
+            return false;
+        }
+        return true;
+    };
+    // after carry_finish(next): the tables of the routes that were not deleted since (same id, same key in the model) sit at the ids `next` gives their keys
+    auto check_carry = [&](int round, DistIndex<HostExec>& next, const std::map<std::string, uint32_t>& old_ids, const std::map<std::string, uint32_t>& new_ids, uint64_t from) -> bool {
+        size_t want_carried = 0, want_members = 0;
+        for (auto& e : sh_model) {
+            auto was = old_ids.find(e.second.first);
+            auto now = new_ids.find(e.second.first);
+            if (was == old_ids.end() || was->second != e.first || now == new_ids.end()) continue;
+            want_carried++;
+            want_members += e.second.second.size();
+            for (size_t m = 0; m <= e.second.second.size(); m++) {
+                std::string url;
+                const bool ok = sh.member(next, now->second, (uint32_t)m, url);
+                if (ok != (m < e.second.second.size()) || (ok && url != e.second.second[m])) {
+                    fprintf(stderr, "round %d: carried table of id %u -> %u: member %zu differs\n", round, e.first, now->second, m);
+                    return false;
+                }
+            }
+        }
+        ShareInfo si;
+        const auto& ci = sh.carry_info;
+        if (!sh.info(next, si) || si.n_tables != want_carried || si.n_members != want_members || si.generation != next.generation || ci.status != 1 ||
+            ci.n_carried != want_carried || ci.n_dropped != sh_model.size() - want_carried || ci.n_members_carried != want_members || ci.from_generation != from ||
+            ci.to_generation != next.generation) {
+            fprintf(stderr, "round %d: carry: %llu tables / %llu members (want %zu / %zu), %llu carried %llu dropped of %zu, status %u: %s\n", round,
+                    (unsigned long long)si.n_tables, (unsigned long long)si.n_members, want_carried, want_members, (unsigned long long)ci.n_carried,
+                    (unsigned long long)ci.n_dropped, sh_model.size(), ci.status, sh.error.c_str());
+            return false;
+        }
+        n_carries++;
+        n_tables_carried += want_carried;
+        n_tables_dropped += sh_model.size() - want_carried;
+        return true;
+    };
     for (int round = 0; round < rounds; round++) {
         std::vector<std::string> keys;
         std::vector<uint8_t> ops;
@@ -257,7 +373,7 @@ int main(int argc, char** argv) {
             }
             uint32_t put_no = 0;
             for (size_t i = 0; i < keys.size(); i++) { // in order; a put's id = next_id + number of puts before it
-                if (ops[i]) model.erase(keys[i]);
+                if (ops[i]) model.erase(keys[i]), once_deleted.push_back(keys[i]);
                 else {
                     if (!model.count(keys[i])) model[keys[i]] = next_id + put_no;
                     put_no++;
@@ -322,6 +438,21 @@ int main(int argc, char** argv) {
                 i++;
             }
         }
+        if (!check_find(round, full ? "rebuild" : "apply")) return 1;
+        // ---- bmq_compact with share_carry: the rebuild happens inside the same object, so the tables' key bytes are copied first; ids become ranks ----
+        if (h.built && rnd(5) == 0) {
+            if (!give_tables(round)) return 1;
+            const std::map<std::string, uint32_t> old_ids = model;
+            const uint64_t from = h.generation;
+            if (!sh.carry_prepare(h, true) || !h.compact() || !sh.carry_finish(h)) {
+                fprintf(stderr, "round %d: compact with a carry failed: %s | %s\n", round, h.error.c_str(), sh.error.c_str());
+                return 1;
+            }
+            uint32_t r = 0;
+            for (auto& e : model) e.second = r++;
+            next_id = r;
+            if (!check_carry(round, h, old_ids, model, from) || !check_find(round, "compact")) return 1;
+        }
         // ---- a generation change beside this index (bmq_compact_begin / _poll / _swap: DistIndex::reserve_like, import_snapshot, import_apply,
         // the log, its replay): chunks of random size, `h` mutated between a chunk's snapshot and its apply and between the chunks; afterwards
         // the new generation holds exactly the model's keys, with dense ids + at most the replayed ops' garbage.  `h` stays the index of the
@@ -334,6 +465,7 @@ int main(int argc, char** argv) {
                 return 1;
             }
             h.defer_release = true;
+            if (!give_tables(round)) return 1;
             std::vector<std::string> log_keys;
             std::vector<uint8_t> log_ops;
             auto mutate = [&]() -> bool { // a small batch into h, the model and the log
@@ -353,7 +485,7 @@ int main(int argc, char** argv) {
                 }
                 uint32_t put_no = 0;
                 for (size_t i = 0; i < mk.size(); i++) {
-                    if (mo[i]) model.erase(mk[i]);
+                    if (mo[i]) model.erase(mk[i]), once_deleted.push_back(mk[i]);
                     else {
                         if (!model.count(mk[i])) model[mk[i]] = next_id + put_no;
                         put_no++;
@@ -370,7 +502,7 @@ int main(int argc, char** argv) {
                 log_keys.insert(log_keys.end(), mk.begin(), mk.end());
                 log_ops.insert(log_ops.end(), mo.begin(), mo.end());
                 n_apply++;
-                return h.apply(mb.data(), mf.data(), mo.data(), (uint32_t)mk.size());
+                return h.apply(mb.data(), mf.data(), mo.data(), (uint32_t)mk.size()) && check_find(round, "apply during a generation change");
             };
             const uint32_t n_ids = h.id_bound();
             uint64_t carried = 0;
@@ -400,6 +532,24 @@ int main(int argc, char** argv) {
                     fprintf(stderr, "round %d: replay failed: %s\n", round, g.error.c_str());
                     return 1;
                 }
+            }
+            { // the swap's carry, while both generations are alive: the lookup reads the key bytes from h's pool
+                g.generation = h.generation + 1;
+                DistIndexStats cs;
+                g.stats(cs);
+                std::vector<uint32_t> gi(cs.next_id);
+                for (uint32_t i = 0; i < cs.next_id; i++) gi[i] = i;
+                std::vector<uint8_t> gb;
+                std::vector<uint64_t> go;
+                if (!g.route_keys(gi.data(), cs.next_id, gb, go)) return 3;
+                std::map<std::string, uint32_t> new_ids;
+                for (uint32_t i = 0; i < cs.next_id; i++)
+                    if (go[i + 1] > go[i]) new_ids[std::string((const char*)gb.data() + go[i], go[i + 1] - go[i])] = i;
+                if (!sh.carry_prepare(h, false) || !sh.carry_finish(g)) {
+                    fprintf(stderr, "round %d: the carry of a generation change failed: %s\n", round, sh.error.c_str());
+                    return 1;
+                }
+                if (!check_carry(round, g, model, new_ids, h.generation)) return 1;
             }
             h.defer_release = false;
             h.release_deferred();
@@ -682,6 +832,8 @@ int main(int argc, char** argv) {
     DistIndexStats st;
     h.stats(st);
     printf("layout v3: %llu of the %llu nodes the checks discovered through a '+' edge below a non-root node lay beside their parent\n", (unsigned long long)plus_stat[0], (unsigned long long)plus_stat[1]);
+    printf("find and carry: %llu keys looked up, %llu carries (%llu tables carried, %llu dropped)\n", (unsigned long long)n_find, (unsigned long long)n_carries,
+           (unsigned long long)n_tables_carried, (unsigned long long)n_tables_dropped);
     printf("host_fuzz ok: seed %llu, %d rounds (%llu rebuilds, %llu applies, %llu generation changes, %llu bounded ones, %llu imports, %llu tenant censuses), %llu topic checks, final %zu routes, %llu nodes, %llu tokens, "
            "%llu trie slots (%llu garbage), %llu id-list words (%llu garbage), %llu fan-out pairs grouped\n",
            (unsigned long long)seed, rounds, (unsigned long long)n_rebuild, (unsigned long long)n_apply, (unsigned long long)n_generations, (unsigned long long)n_bounded, (unsigned long long)n_imports, (unsigned long long)n_census, (unsigned long long)checks, model.size(),
