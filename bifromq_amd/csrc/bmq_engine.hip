@@ -25,6 +25,7 @@
 #include "../../include/bmq.h"
 #include "bmq_codec.h"
 #include "bmq_dist_index.h"
+#include "bmq_delivery.h"
 #include "bmq_dist_kernels.h"
 #include "bmq_poll_kernel.h"
 #include "bmq_exec_dev.h"
@@ -234,6 +235,10 @@ struct bmq_engine {
     std::unique_ptr<Share<DevExec>> dsh;
     std::unique_ptr<Share<HostExec>> hsh;
     DevBuf sh_buf; // staging of bmq_share_resolve
+    // the delivery plan (bmq_delivery.h): scratch of the map and the merge, created by the first call
+    std::unique_ptr<Delivery<DevExec>> ddl;
+    std::unique_ptr<Delivery<HostExec>> hdl;
+    DevBuf dl_buf; // staging of bmq_delivery_plan / bmq_delivery_wait
     // multi-GPU exchange inside the library (bmq_exchange.inc): RCCL communicator of this rank, its own stream
     void* comm = nullptr;
     int comm_world = 0, comm_rank = 0;
@@ -925,7 +930,7 @@ int ticket_begin(bmq_engine* e, int ticket, int format, bool devptr, std::unique
     }
     (void)hipEventSynchronize(S.ev_done); // outside the lock: other threads may submit / apply meanwhile
     g.lock();
-    const bool own_ids = !devptr && (format == BMQ_FMT_IDS || format == BMQ_FMT_GROUPED);
+    const bool own_ids = !devptr && (format == BMQ_FMT_IDS || format == BMQ_FMT_GROUPED || format == BMQ_FMT_DELIVERY);
     int rc = BMQ_OK;
     for (int attempt = 0; attempt < 3; attempt++) {
         rc = finish_dist(e, S, total); // grows internal scratch and re-runs if a kernel asked for it
@@ -1132,6 +1137,7 @@ void bmq_engine_destroy(bmq_engine* e) {
         if (e->ev_lend) (void)hipEventDestroy(e->ev_lend);
         if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
         if (e->ev_join) (void)hipEventDestroy(e->ev_join);
+        e->ddl.reset();
         e->dfo.reset();
         e->dsh.reset();
         e->drt.reset();
@@ -1141,6 +1147,7 @@ void bmq_engine_destroy(bmq_engine* e) {
         e->dx.tmp = nullptr;
         if (e->stream) (void)hipStreamDestroy(e->stream);
     }
+    e->hdl.reset();
     e->hfo.reset(); // (before the index it refers to)
     e->rcmp = bmq_engine::RetainCompaction{}; // (a host-only engine's half-built retain generation: before the executor it refers to)
     delete e;
@@ -1900,7 +1907,7 @@ int bmq_match_submit_fmt(bmq_engine* e, const uint8_t* tenants, const uint32_t* 
                          const uint8_t* topics, const uint32_t* topic_off, uint32_t n_topics, int format, int* out_ticket) {
     int rc = check_dist_ready(e);
     if (rc) return rc;
-    if (format < BMQ_FMT_IDS || format > BMQ_FMT_GROUPED) return set_err(e, BMQ_E_INVAL, "unknown result format");
+    if (format < BMQ_FMT_IDS || format > BMQ_FMT_DELIVERY) return set_err(e, BMQ_E_INVAL, "unknown result format");
     if (!out_ticket || n_topics == 0 || !topics || !topic_off || !topic_tenant || (n_tenants && (!tenants || !tenant_off)))
         return set_err(e, BMQ_E_INVAL, "null pointer or empty batch");
     std::lock_guard<std::mutex> g(e->mu);
@@ -1910,7 +1917,7 @@ int bmq_match_submit_fmt(bmq_engine* e, const uint8_t* tenants, const uint32_t* 
     bmq_engine::BatchSlot& S = e->slots[1 + k]; // ticket k: never the slot the blocking entry points stage into
     if ((rc = ensure_batch_scratch(e, S, n_tenants, n_topics))) return rc;
     // upload on the copy-in stream: it overlaps the kernels of the batch submitted before (pinned sources: bmq_host_alloc)
-    const bool with_ids = format == BMQ_FMT_IDS || format == BMQ_FMT_GROUPED;
+    const bool with_ids = format == BMQ_FMT_IDS || format == BMQ_FMT_GROUPED || format == BMQ_FMT_DELIVERY;
     BatchInput d;
     const BatchInput in{tenants, tenant_off, n_tenants, topic_tenant, topics, topic_off, n_topics};
     if ((rc = stage_input(e, S, in, e->s_in, with_ids ? 24 : 0, d))) return rc;
@@ -2251,4 +2258,5 @@ int32_t bmq_java_string_hash(const uint8_t* utf8, uint32_t len) { return java_st
 #include "bmq_exchange.inc"
 #include "bmq_fanout_engine.inc"
 #include "bmq_share_engine.inc"
+#include "bmq_delivery_engine.inc"
 #include "bmq_formats.inc"

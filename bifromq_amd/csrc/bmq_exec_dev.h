@@ -14,6 +14,7 @@
 
 #include "bmq_build_core.h"
 #include "bmq_census_kernels.h"
+#include "bmq_delivery_kernels.h"
 #include "bmq_fanout_core.h"
 #include "bmq_fanout_kernels.h"
 #include "bmq_retain_build_kernels.h"
@@ -551,7 +552,7 @@ struct DevExec {
     }
     // ---- optional HIP-event marks between the steps of a pipeline (bmq_set_kernel_timing) ----
     bool marks_on = false;
-    hipEvent_t marks[8] = {};
+    hipEvent_t marks[16] = {}; // 0 .. 7: the resolve and the carry of bmq_share.h, 8 .. 12: the delivery plan
     void mark(int i) {
         if (!marks_on) return;
         if (!marks[i] && hipEventCreate(&marks[i]) != hipSuccess) return;
@@ -589,6 +590,25 @@ struct DevExec {
     }
     bool sh_groups(const ShareTables& T, const ShareBatch& b) {
         hipLaunchKernelGGL(k_sh_groups, grid(b.n_rows, SH_BLOCK), dim3(SH_BLOCK), 0, stream, T, b);
+        return launched();
+    }
+    // ---- the delivery plan (bmq_delivery.h) ----
+    bool dl_map(const DistIndexMut& ix, const FanoutState& st, const DeliveryPlan& P) { // slot_group[] is filled with DL_NONE before
+        if (P.n_norm) hipLaunchKernelGGL(k_dl_scatter, grid(P.n_norm, DL_BLOCK), dim3(DL_BLOCK), 0, stream, st, P);
+        hipLaunchKernelGGL(k_dl_map, grid(P.n_sgroups, DL_BLOCK), dim3(DL_BLOCK), 0, stream, ix, st, P);
+        return launched();
+    }
+    bool dl_assign(const DeliveryPlan& P) {
+        hipLaunchKernelGGL(k_dl_assign, grid(P.n_sgroups, DL_BLOCK), dim3(DL_BLOCK), 0, stream, P);
+        return launched();
+    }
+    bool dl_count(const DeliveryPlan& P) {
+        hipLaunchKernelGGL(k_dl_count, grid(P.n_groups, DL_BLOCK), dim3(DL_BLOCK), 0, stream, P);
+        return launched();
+    }
+    bool dl_merge(const DeliveryPlan& P) {
+        const uint32_t n = std::max(P.n_rows, P.n_groups + 1);
+        hipLaunchKernelGGL(k_dl_merge, grid(n, DL_BLOCK), dim3(DL_BLOCK), 0, stream, P, n);
         return launched();
     }
     bool sh_rekey(uint32_t* slot_of, uint32_t id_cap, const uint32_t* new_id, const uint32_t* slot, uint32_t n) {

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "bmq_build_core.h"
+#include "bmq_delivery_core.h"
 #include "bmq_fanout_core.h"
 #include "bmq_retain_build_core.h"
 #include "bmq_retain_core.h"
@@ -245,6 +246,24 @@ struct HostExec {
     }
     bool sh_rekey(uint32_t* slot_of, uint32_t id_cap, const uint32_t* new_id, const uint32_t* slot, uint32_t n) {
         par(n, [&](size_t i) { sh_rekey_one(slot_of, id_cap, new_id, slot, (uint32_t)i); });
+        return true;
+    }
+    // ---- the delivery plan (bmq_delivery.h) ----
+    bool dl_map(const DistIndexMut& ix, const FanoutState& st, const DeliveryPlan& P) { // slot_group[] is filled with DL_NONE before
+        par(P.n_norm, [&](size_t g) { dl_scatter_one(st, P, (uint32_t)g); });
+        par(P.n_sgroups, [&](size_t j) { dl_map_one(ix, st, P, (uint32_t)j); });
+        return true;
+    }
+    bool dl_assign(const DeliveryPlan& P) {
+        par(P.n_sgroups, [&](size_t j) { dl_assign_one(P, (uint32_t)j); });
+        return true;
+    }
+    bool dl_count(const DeliveryPlan& P) {
+        par(P.n_groups, [&](size_t g) { dl_count_one(P, (uint32_t)g); });
+        return true;
+    }
+    bool dl_merge(const DeliveryPlan& P) {
+        par(std::max(P.n_rows, P.n_groups + 1), [&](size_t i) { dl_merge_one(P, (uint32_t)i, DeliveryHint{0u, 0u, 0u}); });
         return true;
     }
     // ---- retain direction (bmq_retain_core.h) ----

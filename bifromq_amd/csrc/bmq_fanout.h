@@ -40,6 +40,9 @@ public:
     uint32_t keys_mapped() const { return used_slots; }
     uint32_t table_slots() const { return st.gt_cap; }
     uint64_t state_generation() const { return generation; } // ~0: no state yet
+    // the group table and per-route cache as the last group() left them (the delivery plan probes them: bmq_delivery.h); seed and
+    // table change with every reset, so a reader takes them afresh after each call
+    const FanoutState& state() const { return st; }
 
     // All pointers are exec memory.  row_ptr[n_topics + 1] with row_ptr[n_topics] == total; out_topic / out_route [total];
     // group_off [group_cap + 1], group_rep [group_cap].

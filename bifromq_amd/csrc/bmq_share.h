@@ -98,6 +98,10 @@ public:
                 const size_t a = url.find('\0'), c = url.find('\0', a + 1);
                 const std::string dk = url.substr(0, a + 1) + url.substr(c + 1); // subBrokerId NUL delivererKey (neither part holds a NUL)
                 auto ins = sd_num.emplace(dk, (uint32_t)sd_num.size());
+                if (ins.second) { // a new number: its bytes go to exec memory as well (upload_deliverers)
+                    h_sd_bytes.insert(h_sd_bytes.end(), dk.begin(), dk.end());
+                    h_sd_off.push_back((uint32_t)h_sd_bytes.size());
+                }
                 t.sd.push_back(ins.first->second);
                 t.entries = std::max<uint32_t>(t.entries, (uint32_t)((4 + url.size() + 15) / 16));
                 t.urls.push_back(std::move(url));
@@ -108,7 +112,7 @@ public:
         std::sort(changed.begin(), changed.end());
         changed.erase(std::unique(changed.begin(), changed.end()), changed.end());
         changed.erase(std::remove_if(changed.begin(), changed.end(), [&](uint32_t id) { return !tabs.count(id); }), changed.end());
-        if (upload(ix, changed, route_ids, n)) return true;
+        if (upload(ix, changed, route_ids, n) && upload_deliverers()) return true;
         // the executor failed half-way (out of memory, a copy error): mirror and device are out of step.  Every table goes -- rows come
         // back unresolved until the caller loads them again -- rather than a directory that names memory that is not there.
         const std::string why = error;
@@ -242,6 +246,15 @@ public:
         return true;
     }
 
+    // ---- what the delivery plan (bmq_delivery.h) reads behind a resolve ------------------------------------------------------------------
+    // The share-deliverer number of every SORTED row of the last resolve (group g of its output is number last_keys()[group_off[g]];
+    // n_deliverers() marks the unresolved rows), and the bytes "subBrokerId NUL delivererKey" of number k in exec memory:
+    // deliverer_bytes()[deliverer_off()[k] .. deliverer_off()[k + 1]).  Uploaded where the numbers are handed out (apply), kept by the carry.
+    const uint32_t* last_keys() const { return s_key_sorted; }
+    uint32_t n_deliverers() const { return (uint32_t)sd_num.size(); }
+    const uint8_t* deliverer_bytes() const { return d_sd_bytes; }
+    const uint32_t* deliverer_off() const { return d_sd_off; }
+
     // ---- the carry through a generation change of the route index (bmq_config.share_carry) -------------------------------------------
     // The member data -- pools, descriptors, share-deliverer numbers -- does not depend on route ids; the directory slot_of[route id] and
     // the keys of the host mirror do.  A table follows its route KEY: old id -> key reference in the old generation (gather_refs) -> id in
@@ -373,6 +386,9 @@ public:
             rel(*p);
         rel(d_desc);
         rel(d_pool64);
+        rel(d_sd_bytes);
+        rel(d_sd_off);
+        sd_bytes_cap = sd_off_cap = 0;
         slot_cap = 0;
         desc_cap = cap64 = cap32 = p_cap = r_cap = 0;
         clear_host();
@@ -393,6 +409,9 @@ private:
     std::unordered_map<uint32_t, HostTable> tabs;    // by route id
     std::unordered_map<std::string, uint32_t> sd_num; // subBrokerId NUL delivererKey -> share-deliverer number
     std::vector<uint32_t> h_slot_of, free_slots;
+    std::vector<uint8_t> h_sd_bytes;       // the keys of sd_num, in number order ...
+    std::vector<uint32_t> h_sd_off{0u};    // ... number k: [h_sd_off[k], h_sd_off[k + 1])
+    size_t sd_uploaded = 0;                // numbers whose bytes are in exec memory
     std::vector<ShareDesc> h_desc;
     uint32_t n_slots = 0;
     uint64_t n_members = 0, used64 = 0, used32 = 0;
@@ -403,6 +422,9 @@ private:
     unsigned long long* d_pool64 = nullptr;
     uint32_t* d_pool32 = nullptr;
     size_t desc_cap = 0, cap64 = 0, cap32 = 0;
+    uint8_t* d_sd_bytes = nullptr; // share-deliverer bytes and offsets (grow-only, freed through the before_free hook)
+    uint32_t* d_sd_off = nullptr;
+    size_t sd_bytes_cap = 0, sd_off_cap = 0;
     uint32_t *flags = nullptr, *s_slot = nullptr, *s_cnt = nullptr, *s_cnt_scan = nullptr;
     unsigned long long* totals = nullptr;
     uint32_t *s_row_pair = nullptr, *s_row_sender = nullptr, *s_row_member = nullptr, *s_key = nullptr, *s_key_sorted = nullptr, *s_pos = nullptr, *s_pos_sorted = nullptr;
@@ -463,6 +485,9 @@ private:
     void clear_host() {
         tabs.clear();
         sd_num.clear();
+        h_sd_bytes.clear();
+        h_sd_off.assign(1, 0u);
+        sd_uploaded = 0;
         free_slots.clear();
         h_desc.clear();
         std::fill(h_slot_of.begin(), h_slot_of.end(), SH_NONE);
@@ -575,6 +600,33 @@ private:
             id_hi = std::max(id_hi, id);
         }
         if (!x.copy_in(d_slot_of + id_lo, h_slot_of.data() + id_lo, sizeof(uint32_t) * ((size_t)id_hi - id_lo + 1))) return xfail();
+        return true;
+    }
+
+    // the bytes of the share-deliverer numbers handed out since the last upload, appended (a buffer that grows is written whole)
+    bool upload_deliverers() {
+        const size_t n = sd_num.size();
+        if (n == sd_uploaded) return true;
+        size_t first = sd_uploaded;
+        if (h_sd_bytes.size() > sd_bytes_cap || n + 1 > sd_off_cap) {
+            if (!x.sync()) return xfail();
+            if (h_sd_bytes.size() > sd_bytes_cap) {
+                sd_bytes_cap = 0;
+                if (!fresh(d_sd_bytes, h_sd_bytes.size() * 2 + 256)) return false;
+                sd_bytes_cap = h_sd_bytes.size() * 2 + 256;
+            }
+            if (n + 1 > sd_off_cap) {
+                sd_off_cap = 0;
+                if (!fresh(d_sd_off, (n + 1) * 2 + 64)) return false;
+                sd_off_cap = (n + 1) * 2 + 64;
+            }
+            first = 0;
+        }
+        const size_t b0 = h_sd_off[first];
+        if (!x.copy_in(d_sd_bytes + b0, h_sd_bytes.data() + b0, h_sd_bytes.size() - b0) ||
+            !x.copy_in(d_sd_off + first, h_sd_off.data() + first, sizeof(uint32_t) * (n + 1 - first)))
+            return xfail();
+        sd_uploaded = n;
         return true;
     }
 

@@ -446,7 +446,7 @@ class Engine:
         return need.value
 
     # ---- result formats that fit the wire (include/bmq.h: BMQ_FMT_*) ------------------------------------------------------------
-    FMT_IDS, FMT_COUNTS, FMT_RANGES, FMT_GROUPED = 0, 1, 2, 3
+    FMT_IDS, FMT_COUNTS, FMT_RANGES, FMT_GROUPED, FMT_DELIVERY = 0, 1, 2, 3, 4
     RANGE_SIDE = 0x80000000
 
     def match_submit_fmt(self, tdata, toff, n_tenants, tt, pdata, poff, n_topics, fmt: int) -> int:
@@ -661,6 +661,64 @@ class Engine:
         out = _lib.ShareCarryInfo()
         self._check(_lib.lib().bmq_share_carry_info_get(self.h, C.byref(out)))
         return out
+
+    # ---- the delivery plan of a match batch (DeliverExecutorGroup.submit: one set of calls per DelivererKey) --------------------------
+    def _delivery_error(self, rc: int, info: "_lib.DeliveryInfo") -> BmqError:
+        err = BmqError(rc, (_lib.lib().bmq_last_error(self.h) or b"").decode())
+        err.info = info
+        err.needed = (info.n_rows, info.n_share_rows, info.n_groups)
+        return err
+
+    def delivery_plan(self, row_ptr, route_ids, sender_off, sender_hash, nonce: int, row_cap: Optional[int] = None, share_cap: int = 256,
+                      group_cap: int = 256, retry: bool = True):
+        """bmq_delivery_plan -> (topic, route, aux, share_sender, share_member, group_off, info): the delivery rows of a match CSR grouped by
+        DelivererKey, shared subscriptions resolved and merged in; group g owns rows group_off[g] .. group_off[g + 1], ordered by
+        (topic, route, sender); aux == 0xFFFFFFFF: the route itself receives, else it indexes (share_sender, share_member).  A capacity that
+        is too small is retried once with the sizes the call reports (retry=False: BmqError -3, .needed = (rows, share rows, groups))."""
+        row = np.ascontiguousarray(row_ptr, dtype=np.uint32)
+        ids = np.ascontiguousarray(route_ids, dtype=np.uint32)
+        so = np.ascontiguousarray(sender_off, dtype=np.uint32)
+        sh = np.ascontiguousarray(sender_hash, dtype=np.int32)
+        if row_cap is None:
+            row_cap = max(int(row[-1]), 1)
+        info = _lib.DeliveryInfo()
+        for attempt in range(2):
+            ot, orr, oa = (np.zeros(max(row_cap, 1), dtype=np.uint32) for _ in range(3))
+            ss, sm = (np.zeros(max(share_cap, 1), dtype=np.uint32) for _ in range(2))
+            goff = np.zeros(group_cap + 1, dtype=np.uint32)
+            rc = _lib.lib().bmq_delivery_plan(self.h, _ptr(row), _ptr(ids), len(row) - 1, _ptr(so), _ptr(sh), nonce & 0xFFFFFFFFFFFFFFFF, _ptr(ot), _ptr(orr),
+                                              _ptr(oa), row_cap, _ptr(ss), _ptr(sm), share_cap, _ptr(goff), group_cap, C.byref(info))
+            if rc == -3 and retry and attempt == 0:
+                row_cap, share_cap, group_cap = max(row_cap, info.n_rows), max(share_cap, info.n_share_rows), max(group_cap, info.n_groups)
+                continue
+            if rc:
+                raise self._delivery_error(rc, info)
+            return ot[:info.n_rows], orr[:info.n_rows], oa[:info.n_rows], ss[:info.n_share_rows], sm[:info.n_share_rows], goff[:info.n_groups + 1], info
+
+    def delivery_plan_device(self, d_row_ptr, d_ids, n_topics, total, d_sender_off, d_sender_hash, n_senders, nonce: int, d_out_topic, d_out_route,
+                             d_out_aux, row_cap, d_out_share_sender, d_out_share_member, share_cap, d_group_off, group_cap) -> "_lib.DeliveryInfo":
+        """All d_* are device pointers (ints).  -> DeliveryInfo; BmqError -3 (.needed = (rows, share rows, groups)) if a capacity is too small."""
+        info = _lib.DeliveryInfo()
+        rc = _lib.lib().bmq_delivery_plan_dev(self.h, d_row_ptr, d_ids, n_topics, total, d_sender_off, d_sender_hash, n_senders, nonce & 0xFFFFFFFFFFFFFFFF,
+                                              d_out_topic, d_out_route, d_out_aux, row_cap, d_out_share_sender, d_out_share_member, share_cap, d_group_off,
+                                              group_cap, C.byref(info))
+        if rc:
+            raise self._delivery_error(rc, info)
+        return info
+
+    def match_wait_delivery(self, ticket: int, sender_off, sender_hash, nonce: int, out_topic: np.ndarray, out_route: np.ndarray, out_aux: np.ndarray,
+                            share_sender: np.ndarray, share_member: np.ndarray, group_off: np.ndarray):
+        """The wait of a FMT_DELIVERY ticket -> (total ids of the CSR, DeliveryInfo); the capacities are the lengths of the arrays
+        (group_off: groups + 1).  BmqError -3 carries .needed = (rows, share rows, groups) and the ticket is released."""
+        so = np.ascontiguousarray(sender_off, dtype=np.uint32)
+        sh = np.ascontiguousarray(sender_hash, dtype=np.int32)
+        info, tot = _lib.DeliveryInfo(), C.c_uint64()
+        rc = _lib.lib().bmq_delivery_wait(self.h, ticket, _ptr(so), _ptr(sh), nonce & 0xFFFFFFFFFFFFFFFF, _ptr(out_topic), _ptr(out_route), _ptr(out_aux),
+                                                min(len(out_topic), len(out_route), len(out_aux)), _ptr(share_sender), _ptr(share_member),
+                                                min(len(share_sender), len(share_member)), _ptr(group_off), len(group_off) - 1, C.byref(info), C.byref(tot))
+        if rc:
+            raise self._delivery_error(rc, info)
+        return tot.value, info
 
     def finish(self) -> int:
         total = C.c_uint64()

@@ -372,7 +372,9 @@ int bmq_match_wait_dev(bmq_engine* e, int ticket, uint64_t* out_total /* may be 
  *                    BMQ_E_NOSPACE when range_cap / side_cap are too small: out_info holds the sizes, row pointers are written, the ticket
  *                    is released (as with bmq_match_wait).
  *   BMQ_FMT_GROUPED  bmq_match_wait_grouped: the (topic, route) pairs of the batch regrouped by DelivererKey -- the output of
- *                    bmq_fanout_group (see there for the meaning of every array) without the CSR ever leaving the GPU. */
+ *                    bmq_fanout_group (see there for the meaning of every array) without the CSR ever leaving the GPU.
+ *   BMQ_FMT_DELIVERY (4, defined with bmq_delivery_plan below) bmq_delivery_wait: the delivery plan of the batch -- those groups with
+ *                    the receivers of shared subscriptions resolved and merged in. */
 #define BMQ_FMT_IDS 0
 #define BMQ_FMT_COUNTS 1
 #define BMQ_FMT_RANGES 2
@@ -755,6 +757,62 @@ typedef struct bmq_share_carry_info {
     uint32_t reserved0;
 } bmq_share_carry_info;
 int bmq_share_carry_info_get(const bmq_engine* e, bmq_share_carry_info* out);
+
+/* ---- the delivery plan of a match batch: the step behind the two above -------------------------------------------------------------- */
+/* What DeliverExecutorGroup.submit (DW/DeliverExecutorGroup.java:112-278) produces is ONE set of delivery calls per
+ * DelivererKey(subBrokerId, delivererKey): inside a key per tenant -> message pack (topic) -> MatchInfo (BatchDeliveryCall.java:71-76), and the
+ * member picked for a $share / $oshare route is filed by DeliverExecutor.send (DW/DeliverExecutor.java:85-90) under ITS OWN DelivererKey,
+ * beside the normal routes of that key.  bmq_fanout_group names its groups by a route, bmq_share_resolve names its groups by a member; whether
+ * two of them are one DelivererKey is decided here, on the executor, by the key bytes -- a 64-bit hash that agrees never merges two keys.
+ *
+ * bmq_delivery_plan: in : a match CSR as for bmq_fanout_group (row_ptr[n_topics + 1], route_ids[row_ptr[n_topics]]); the publishers of every
+ *        topic's message pack and a nonce as for bmq_share_resolve (sender_off[n_topics + 1], sender_hash[sender_off[n_topics]]).
+ *   out: delivery rows (out_topic[r], out_route[r], out_aux[r]), r < out_info->n_rows.
+ *        out_aux[r] == 0xFFFFFFFF: the route itself is the receiver (a normal route -- or, in the trailing group of dead ids, what is left of it).
+ *        otherwise s = out_aux[r] < out_info->n_share_rows indexes (out_share_sender[s], out_share_member[s]): the sender index (0xFFFFFFFF for
+ *        an unordered share: the whole pack) and the chosen member of the route's table, 0xFFFFFFFF when there is none -- exactly the values
+ *        bmq_share_resolve documents for out_sender / out_member (the pick formula, the signed rendezvous comparison and the first-of-equals
+ *        rule are those: the same code runs).  One row per (pair, sender) of an ordered share, none for a topic without senders.
+ *        out_group_off[n_groups + 1]: group g owns the rows out_group_off[g] .. out_group_off[g + 1].  A group is exactly one DelivererKey;
+ *        inside it the rows are ordered by (topic, route id, sender index), so all deliveries of one message pack to one deliverer are
+ *        adjacent, whether they come from normal routes or from chosen members.  There is no representative array: the DelivererKey of
+ *        group g is that of its first row -- out_aux == 0xFFFFFFFF: the route's receiverUrl (bmq_route_key), else the member's URL
+ *        (bmq_share_member(route, out_share_member[aux])) --, subBrokerId and delivererKey being parts 0 and 2 of "<subBrokerId> NUL
+ *        <receiverId> NUL <delivererKey>".
+ *        Group order: the resolved groups first, in no particular order; then the group of shared rows that could not be resolved (no
+ *        table, not a shared route: out_info->special bit 0; its side entries carry member 0xFFFFFFFF); then the group of route ids deleted
+ *        since the match or never handed out (bit 1; a shared route deleted since is found here too).  Either is absent when empty.
+ *   out_info: n_rows, n_share_rows, n_groups as written; n_merged_groups: groups that hold rows of both kinds; n_share_only_groups: a
+ *        DelivererKey reached through members only -- none of its normal routes, if the index has any, matched in this batch --; generation:
+ *        of the route index the ids belong to; ms_*: HIP-event times of the four steps while bmq_set_kernel_timing is on, else 0 (the
+ *        grouping, the resolve, the map of share groups to normal groups, the merge).
+ *   BMQ_E_NOSPACE: row_cap < n_rows, share_cap < n_share_rows or group_cap < n_groups; out_info holds all three counts, nothing else is valid.
+ *   Fewer than 2^31 pairs and rows per call.  Works on a host-only engine too (the same per-item functions on host threads).
+ * _dev: every array is a device pointer (the CSR may be what bmq_match_submit_dev left in HBM), total = d_row_ptr[n_topics], n_senders = the
+ *   length of d_sender_hash; runs on the engine stream and returns when the rows are complete.  Needs a device.
+ * bmq_delivery_wait: the wait of a BMQ_FMT_DELIVERY ticket (bmq_match_submit_fmt): the plan of the batch without its CSR ever leaving
+ *   the GPU.  The senders are handed over here -- a few bytes per publisher, staged on the engine stream in front of the plan's kernels.
+ *   *out_total = the ids the CSR holds.  BMQ_E_NOSPACE as above, and the ticket is released, as with the other waits; waiting on a ticket
+ *   of another format, or on this one with another format's call, is BMQ_E_STATE and leaves the ticket in flight.  Needs a device. */
+#define BMQ_FMT_DELIVERY 4
+typedef struct bmq_delivery_info {
+    uint32_t n_rows, n_share_rows, n_groups;
+    uint32_t n_merged_groups, n_share_only_groups;
+    uint32_t special; /* bit 0: the group of unresolved shared rows is present, bit 1: the group of dead route ids */
+    uint64_t generation;
+    float ms_group, ms_resolve, ms_map, ms_merge;
+} bmq_delivery_info;
+int bmq_delivery_plan(bmq_engine* e, const uint32_t* row_ptr, const uint32_t* route_ids, uint32_t n_topics, const uint32_t* sender_off,
+                      const int32_t* sender_hash, uint64_t nonce, uint32_t* out_topic, uint32_t* out_route, uint32_t* out_aux, uint32_t row_cap,
+                      uint32_t* out_share_sender, uint32_t* out_share_member, uint32_t share_cap, uint32_t* out_group_off, uint32_t group_cap,
+                      bmq_delivery_info* out_info);
+int bmq_delivery_plan_dev(bmq_engine* e, const uint32_t* d_row_ptr, const uint32_t* d_route_ids, uint32_t n_topics, uint64_t total,
+                          const uint32_t* d_sender_off, const int32_t* d_sender_hash, uint32_t n_senders, uint64_t nonce, uint32_t* d_out_topic,
+                          uint32_t* d_out_route, uint32_t* d_out_aux, uint32_t row_cap, uint32_t* d_out_share_sender, uint32_t* d_out_share_member,
+                          uint32_t share_cap, uint32_t* d_out_group_off, uint32_t group_cap, bmq_delivery_info* out_info);
+int bmq_delivery_wait(bmq_engine* e, int ticket, const uint32_t* sender_off, const int32_t* sender_hash, uint64_t nonce, uint32_t* out_topic,
+                            uint32_t* out_route, uint32_t* out_aux, uint32_t row_cap, uint32_t* out_share_sender, uint32_t* out_share_member,
+                            uint32_t share_cap, uint32_t* out_group_off, uint32_t group_cap, bmq_delivery_info* out_info, uint64_t* out_total);
 
 /* ---- dist-server side range pruning ---------------------------------------------------------------------- */
 /* TenantRangeLookupCache.lookup (bifromq-dist/bifromq-dist-server/src/main/java/org/apache/bifromq/dist/server/scheduler/

@@ -14,6 +14,9 @@
 //   * after every step bmq_routes_find's per-key lookup (DistIndex::find_keys over find_key_one) against the model's key -> id, absent, deleted and
 //     malformed keys included; member tables of shared subscriptions carried through a bmq_compact and through the generation change
 //     beside the index (Share::carry_prepare / carry_finish) against the model: carried iff the route was not deleted since, at its key's new id.
+//   * after every step the delivery plan (Delivery::plan, bmq_delivery.h) of a random CSR -- live, deleted and never handed out ids, fresh member
+//     tables whose members live under the deliverer keys of normal routes and under keys of their own -- against a plain merge, by key bytes, of
+//     Fanout::group and Share::resolve over the same CSR: the same rows per DelivererKey in (topic, route, sender) order, special groups last.
 // Build + run: make -C bifromq_amd/csrc fuzz   (tests/test_host.py runs short rounds)
 #include <cstdio>
 #include <algorithm>
@@ -23,9 +26,11 @@
 #include <random>
 #include <set>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../bifromq_amd/csrc/bmq_codec.h"
+#include "../bifromq_amd/csrc/bmq_delivery.h"
 #include "../bifromq_amd/csrc/bmq_dist_index.h"
 #include "../bifromq_amd/csrc/bmq_exec_host.h"
 #include "../bifromq_amd/csrc/bmq_fanout.h"
@@ -212,7 +217,7 @@ int main(int argc, char** argv) {
     auto rand_key = [&]() {
         if (rnd(400) == 0) tenants.push_back("late-tenant-" + std::to_string(extra_tenants++)); // tenants appear over time
         const std::string& tn = tenants[rnd(tenants.size())];
-        const uint8_t flag = rnd(10) == 0 ? 2 : 1;
+        const uint8_t flag = rnd(10) == 0 ? (uint8_t)(2 + rnd(2)) : 1; // ($share and $oshare routes: the delivery plan below resolves both)
         // receiverUrl = subBrokerId NUL receiverId NUL delivererKey: a few brokers x a few deliverer keys (the fan-out grouping below)
         return encode_route_key(tn, rand_filter(), flag,
                                 flag == 1 ? std::to_string(rnd(3)) + std::string("\0", 1) + "inbox" + std::to_string(rnd(40)) + std::string("\0d", 2) +
@@ -281,6 +286,9 @@ int main(int argc, char** argv) {
     };
     // ---- member tables of shared subscriptions through a generation change (bmq_config.share_carry: Share::carry_prepare / carry_finish) ----
     Share<HostExec> sh(hx);
+    Share<HostExec> sh_plan(hx); // the tables of the delivery-plan check: given afresh for every CSR (sh above belongs to the carry checks)
+    Delivery<HostExec> dl(hx);
+    uint64_t dl_rows = 0, dl_merged = 0;
     std::map<uint32_t, std::pair<std::string, std::vector<std::string>>> sh_model; // route id -> (its key when the table was given, URLs)
     auto give_tables = [&](int round) -> bool { // fresh tables for up to 40 group routes of the model
         sh.drop();
@@ -807,6 +815,132 @@ int main(int argc, char** argv) {
                 return 1;
             }
             fo_pairs += total;
+            // ---- the delivery plan of the same CSR (bmq_delivery.h) against a plain merge, by key BYTES, of the groups above and a resolve of
+            // their shared slice.  Members live under the deliverer keys of normal routes (so that groups merge) and under keys of their own.
+            std::map<uint32_t, std::vector<std::string>> tabs;
+            {
+                std::vector<std::string> normal_dk;
+                for (auto& e : by_id) {
+                    RouteKeyParts kp;
+                    decode_route_key(*e.second, kp);
+                    const auto parts = split(kp.receiver, '\0');
+                    if (kp.flag == 1 && parts.size() == 3) normal_dk.push_back(parts[0] + std::string("\0", 1) + "m" + std::to_string(rnd(3)) + std::string("\0", 1) + parts[2]);
+                }
+                std::vector<uint32_t> t_ids, moff{0}, uoff{0};
+                std::vector<uint8_t> urls;
+                for (auto& e : by_id) {
+                    RouteKeyParts kp;
+                    decode_route_key(*e.second, kp);
+                    if (kp.flag == 1 || rnd(4) == 0) continue;
+                    auto& t = tabs[e.first];
+                    for (size_t m = 1 + rnd(4); m > 0; m--) {
+                        if (!normal_dk.empty() && rnd(2)) t.push_back(normal_dk[rnd(normal_dk.size())]);
+                        else t.push_back(std::to_string(rnd(3)) + std::string("\0", 1) + "r" + std::to_string(m) + std::string("\0", 1) + "own" + std::to_string(rnd(4)));
+                        urls.insert(urls.end(), t.back().begin(), t.back().end());
+                        uoff.push_back((uint32_t)urls.size());
+                    }
+                    t_ids.push_back(e.first);
+                    moff.push_back((uint32_t)(uoff.size() - 1));
+                }
+                sh_plan.drop();
+                if (!t_ids.empty() && !sh_plan.apply(h, t_ids.data(), (uint32_t)t_ids.size(), moff.data(), urls.data(), uoff.data())) {
+                    fprintf(stderr, "round %d: delivery plan: share apply failed: %s\n", round, sh_plan.error.c_str());
+                    return 1;
+                }
+            }
+            std::vector<uint32_t> s_off{0}, s_hash;
+            for (uint32_t r = 0; r < n_rows; r++) {
+                for (size_t k = rnd(4); k > 0; k--) s_hash.push_back((uint32_t)rnd(1ull << 32));
+                s_off.push_back((uint32_t)s_hash.size());
+            }
+            s_hash.resize(s_hash.size() + 4);
+            const unsigned long long nonce = rnd(1ull << 62);
+            using Row = std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>; // topic, route, sender, member
+            auto key_name = [&](uint32_t route, uint32_t member) -> std::string {
+                if (member != SH_NONE) {
+                    const auto parts = split(tabs[route][member], '\0');
+                    return "k:" + parts[0] + "|" + parts[2];
+                }
+                RouteKeyParts kp;
+                decode_route_key(*by_id.at(route), kp);
+                const auto parts = split(kp.receiver, '\0');
+                return "k:" + parts[0] + "|" + parts[2];
+            };
+            std::map<std::string, std::vector<Row>> want_plan, got_plan;
+            uint32_t s_lo = total, s_hi = total;
+            for (uint32_t g = 0; g < fr.n_groups; g++) {
+                if (grep[g] == 0xFFFFFFFEu) {
+                    s_lo = goff[g], s_hi = goff[g + 1];
+                    continue;
+                }
+                const std::string name = grep[g] == 0xFFFFFFFFu ? "dead" : key_name(grep[g], SH_NONE);
+                for (uint32_t k = goff[g]; k < goff[g + 1]; k++) want_plan[name].push_back(Row{ot[k], orr[k], SH_NONE, SH_NONE});
+            }
+            const uint32_t rcap = (s_hi - s_lo) * 4 + 4;
+            std::vector<uint32_t> rp(rcap), rs(rcap), rm(rcap), rgo(rcap + 1);
+            ShareResult sres;
+            if (!sh_plan.resolve(h, ot.data() + s_lo, orr.data() + s_lo, s_hi - s_lo, s_off.data(), s_hash.data(), n_rows, s_off.back(), nonce, rp.data(), rs.data(),
+                                 rm.data(), rcap, rgo.data(), rcap, sres) || sres.overflow) {
+                fprintf(stderr, "round %d: delivery plan: resolve failed: %s\n", round, sh_plan.error.c_str());
+                return 1;
+            }
+            for (uint32_t k = 0; k < sres.n_rows; k++) {
+                const uint32_t t = ot[s_lo + rp[k]], route = orr[s_lo + rp[k]];
+                want_plan[rm[k] == SH_NONE ? std::string("unresolved") : key_name(route, rm[k])].push_back(Row{t, route, rs[k], rm[k]});
+            }
+            for (auto& e : want_plan) std::sort(e.second.begin(), e.second.end());
+            const uint32_t n_want_rows = total - (s_hi - s_lo) + sres.n_rows;
+            std::vector<uint32_t> pt(n_want_rows + 1), pr(n_want_rows + 1), pa(n_want_rows + 1), ps(sres.n_rows + 1), pm(sres.n_rows + 1), pgo(want_plan.size() + 2);
+            DeliveryResult dr;
+            if (!dl.plan(fo, sh_plan, h, row.data(), ids.data(), n_rows, total, s_off.data(), s_hash.data(), s_off.back(), nonce, pt.data(), pr.data(), pa.data(), n_want_rows,
+                         ps.data(), pm.data(), sres.n_rows, pgo.data(), (uint32_t)want_plan.size(), dr) || dr.overflow) {
+                fprintf(stderr, "round %d: delivery plan failed (%u rows, %u share rows, %u groups; the merge has %u, %u, %zu): %s\n", round, dr.n_rows, dr.n_share_rows,
+                        dr.n_groups, n_want_rows, sres.n_rows, want_plan.size(), dl.error.c_str());
+                return 1;
+            }
+            bool bad_plan = dr.n_rows != n_want_rows || dr.n_share_rows != sres.n_rows || dr.n_groups != want_plan.size() || pgo[0] != 0 || pgo[dr.n_groups] != dr.n_rows;
+            uint32_t n_merged = 0;
+            for (uint32_t g = 0; g < dr.n_groups && !bad_plan; g++) {
+                std::vector<Row> rows_g;
+                std::string name;
+                bool both[2] = {false, false};
+                for (uint32_t k = pgo[g]; k < pgo[g + 1] && !bad_plan; k++) {
+                    const uint32_t a = pa[k];
+                    if (a != SH_NONE && a >= dr.n_share_rows) {
+                        bad_plan = true;
+                        break;
+                    }
+                    const Row rw{pt[k], pr[k], a == SH_NONE ? SH_NONE : ps[a], a == SH_NONE ? SH_NONE : pm[a]};
+                    std::string nm;
+                    if (a != SH_NONE) nm = pm[a] == SH_NONE ? std::string("unresolved") : key_name(pr[k], pm[a]);
+                    else nm = by_id.count(pr[k]) ? std::string() : std::string("dead");
+                    if (nm.empty()) {
+                        RouteKeyParts kp;
+                        decode_route_key(*by_id.at(pr[k]), kp);
+                        nm = kp.flag == 1 ? key_name(pr[k], SH_NONE) : std::string("dead?");
+                    }
+                    both[a != SH_NONE] = true;
+                    if (k == pgo[g]) name = nm;
+                    bad_plan |= nm != name; // every row of a group names the group's DelivererKey
+                    rows_g.push_back(rw);
+                }
+                bad_plan |= rows_g.empty() || got_plan.count(name) || !std::is_sorted(rows_g.begin(), rows_g.end());
+                n_merged += both[0] && both[1];
+                got_plan[name] = std::move(rows_g);
+            }
+            if (!bad_plan && dr.n_groups) { // the special groups come last: unresolved, then dead
+                const uint32_t n_sp = (dr.special & 1u) + ((dr.special >> 1) & 1u);
+                bad_plan |= ((dr.special & 1u) != 0) != (want_plan.count("unresolved") != 0) || ((dr.special & 2u) != 0) != (want_plan.count("dead") != 0);
+                if (!bad_plan && (dr.special & 2u)) bad_plan |= pa[pgo[dr.n_groups - 1]] != SH_NONE || by_id.count(pr[pgo[dr.n_groups - 1]]);
+                if (!bad_plan && (dr.special & 1u)) bad_plan |= pa[pgo[dr.n_groups - n_sp]] == SH_NONE || pm[pa[pgo[dr.n_groups - n_sp]]] != SH_NONE;
+            }
+            if (bad_plan || got_plan != want_plan || n_merged != dr.n_merged_groups) {
+                fprintf(stderr, "round %d: the delivery plan differs from the merge of its parts (%zu vs %zu groups, %u vs %u rows, special %u, merged %u vs %u)\n", round,
+                        got_plan.size(), want_plan.size(), dr.n_rows, n_want_rows, dr.special, dr.n_merged_groups, n_merged);
+                return 1;
+            }
+            dl_rows += dr.n_rows;
+            dl_merged += dr.n_merged_groups;
         }
         for (int tq = 0; tq < 150; tq++) {
             const std::string& tn = tq % 25 == 24 ? std::string("nobody") : tenants[rnd(tenants.size())];
@@ -834,6 +968,7 @@ int main(int argc, char** argv) {
     printf("layout v3: %llu of the %llu nodes the checks discovered through a '+' edge below a non-root node lay beside their parent\n", (unsigned long long)plus_stat[0], (unsigned long long)plus_stat[1]);
     printf("find and carry: %llu keys looked up, %llu carries (%llu tables carried, %llu dropped)\n", (unsigned long long)n_find, (unsigned long long)n_carries,
            (unsigned long long)n_tables_carried, (unsigned long long)n_tables_dropped);
+    printf("delivery plan: %llu rows planned, %llu groups held normal and member rows\n", (unsigned long long)dl_rows, (unsigned long long)dl_merged);
     printf("host_fuzz ok: seed %llu, %d rounds (%llu rebuilds, %llu applies, %llu generation changes, %llu bounded ones, %llu imports, %llu tenant censuses), %llu topic checks, final %zu routes, %llu nodes, %llu tokens, "
            "%llu trie slots (%llu garbage), %llu id-list words (%llu garbage), %llu fan-out pairs grouped\n",
            (unsigned long long)seed, rounds, (unsigned long long)n_rebuild, (unsigned long long)n_apply, (unsigned long long)n_generations, (unsigned long long)n_bounded, (unsigned long long)n_imports, (unsigned long long)n_census, (unsigned long long)checks, model.size(),
