@@ -9,10 +9,13 @@
 //   k_fmt_count : per topic, its number of ranges and of side ids            -> two exclusive prefix sums (hipcub) -> range_ptr, side_ptr
 //   k_fmt_emit  : per topic, its ranges in ascending order of their first id (insertion sort while copying: lists are 1-8 long;
 //                 lists longer than FMT_SORT_MAX are copied as they are), indirect lists copied to the side array
-// A row whose consecutive ranges overlap after ordering (interleaved id sets: possible only after churn) is counted in sums[2]: the
-// consumer orders the expanded ids of such rows itself (it sees the overlap while expanding).
+// A row whose consecutive ranges overlap as emitted (interleaved id sets: possible only after churn; a row of more than FMT_SORT_MAX ranges
+// that the walk did not match in id order: at any time) is counted in sums[2]: the consumer orders the expanded ids of such rows itself (it
+// sees the overlap while expanding).
 #pragma once
+#ifndef BMQ_WAVE_EMU // (tools/emu/format_emu.cpp and walk_emu.cpp compile this file with g++ against the wave64 emulator)
 #include <hip/hip_runtime.h>
+#endif
 
 #include "bmq_dist_kernels.h"
 

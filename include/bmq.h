@@ -367,8 +367,12 @@ int bmq_match_wait_dev(bmq_engine* e, int ticket, uint64_t* out_total /* may be 
  *                    ranges: as matched); expanding them in that order yields the row's ids in ascending order -- exactly the row of
  *                    BMQ_FMT_IDS -- unless ranges overlap (interleaved id sets: only after churn), which the consumer sees while expanding
  *                    (first id <= last id of the range before it) and repairs by ordering that row's ids;
- *                    out_info->n_overlapping_rows says how many such rows the batch has (0 after a rebuild).  out_row_ptr (may be NULL)
- *                    receives the id row pointers as well, so that the consumer knows where every expanded row goes.
+ *                    out_info->n_overlapping_rows says how many such rows the batch has.  After a rebuild no row of up to 32 ranges
+ *                    is among them; rows of more than 32 ranges may be at any time: "as matched" is the order the walk found the
+ *                    filters in, which is not the order of their ids, so such a row is counted wherever a range begins at or below the
+ *                    end of the one before it.  A consumer may skip the ordering only for a batch with n_overlapping_rows == 0.
+ *                    out_row_ptr (may be NULL) receives the id row pointers as well, so that the consumer knows where every expanded
+ *                    row goes.
  *                    BMQ_E_NOSPACE when range_cap / side_cap are too small: out_info holds the sizes, row pointers are written, the ticket
  *                    is released (as with bmq_match_wait).
  *   BMQ_FMT_GROUPED  bmq_match_wait_grouped: the (topic, route) pairs of the batch regrouped by DelivererKey -- the output of

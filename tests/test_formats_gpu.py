@@ -10,6 +10,7 @@ from bifromq_amd.engine import pinned
 from oracle import oracle as O
 from bifromq_amd.workload import unpack
 from tests import util as U
+from tests.ranges_ref import check_ranges_contract
 from tests.test_fanout import _check as check_groups_vs_oracle
 
 pytestmark = pytest.mark.gpu
@@ -56,6 +57,7 @@ def _check_ranges(eng, p_t, p_to, n_tenants, pinned_batch, n, erow, eids, expect
     rows = eng.expand_ranges(rptr, ranges, side, n)
     for i in range(n):
         assert np.array_equal(rows[i], eids[erow[i]:erow[i + 1]]), i
+    check_ranges_contract(info, rptr, ranges, side, n, erow, eids)  # ... and the strict consumer: the order and the count of overlapping rows as promised
     if expect_overlap is not None:
         assert (info.n_overlapping_rows > 0) == expect_overlap
     return info

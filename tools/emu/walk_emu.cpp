@@ -9,7 +9,8 @@
 // records), every batch with the child filter words read and ignored, the count of discovered nodes of every batch (and of every row of the ordered
 // batches) against a model of the trie's nodes, and the whole pipeline of an engine with bmq_config.dedup_sorted
 // (k_dd_adj_heads -> k_dd_adj_scatter -> the walk kernels on the dense batch -> k_fill_adj -> k_expand, wired as launch_dist wires them) on
-// ordered batches full of repeats -- against a brute force over the model's route keys (the rule of SURVEY.md 8a-0).  What the GPU makes of the same source is what tests/ (-m gpu) check against the oracle.
+// ordered batches full of repeats -- against a brute force over the model's route keys (the rule of SURVEY.md 8a-0); behind k_expand of every batch the kernels
+// of the RANGES result format (bmq_format_kernels.h) over the pairs the walk left, read by a consumer that follows include/bmq.h to the letter (run_format).  What the GPU makes of the same source is what tests/ (-m gpu) check against the oracle.
 //   g++ -O1 -g -std=c++17 -I bifromq_amd/csrc -I tools/emu tools/emu/walk_emu.cpp bifromq_amd/csrc/bmq_codec.cpp -o build/walk_emu -pthread && build/walk_emu [rounds] [seed]
 //   add -fsanitize=address,undefined (ASAN_OPTIONS=detect_stack_use_after_return=0: the lanes are ucontext fibers): LDS arrays are function statics here, so a read or
 //   write past one is reported -- both harnesses run clean that way (round 5)
@@ -42,6 +43,7 @@ inline uint32_t lds_word_at(const uint32_t* words, uint32_t rel) { // (bmq_dedup
 }
 } // namespace bmq
 #include "bmq_dist_kernels.h"
+#include "bmq_format_kernels.h"
 
 using namespace bmq;
 
@@ -91,7 +93,73 @@ struct Coverage {
     uint64_t rows = 0, ids = 0, batches = 0, mixed = 0, slow_rows = 0, spills = 0, chunked = 0, sorted_rows = 0, after_apply = 0, two_tenant_waves = 0;
     uint64_t adj_batches = 0, adj_rows = 0, adj_walked = 0, adj_slow = 0;
     uint64_t split_blocks = 0, split_overflow = 0, split_adj = 0; // k_expand: heavy blocks expanded by four waves, blocks the list had no room for
+    uint64_t fmt_ranges = 0, fmt_side_rows = 0, fmt_over_rows = 0, fmt_empty = 0, fmt_empty_lists = 0, fmt_overlap_rows = 0, fmt_overlap_over = 0, fmt_adj_rows = 0, fmt_fresh_rows = 0, fmt_fresh_over = 0, fmt_fresh_overlap_over = 0; // the RANGES format behind the walk
 };
+
+// The RANGES result format (bmq_format_kernels.h) over the pairs the walk left, launched as enqueue_ranges launches it; then a consumer that follows
+// include/bmq.h to the letter: a row's ranges expanded in the order given, the row ordered only where a non-empty range begins at or below the last id
+// of the non-empty range before it.  Its rows must be `rows` (which main compares with the brute force), its count of ordered rows sums[2].
+static bool g_fresh_index = false; // the batch runs on an index as a rebuild / compaction left it: ids are ranks in key order
+static int run_format(const BatchArgs& a, const std::vector<std::vector<uint32_t>>& rows, Coverage& cov, bool adj) {
+    const uint32_t n = a.n_topics;
+    static std::vector<uint8_t> s_cnt, s_ptr, s_out, s_side;
+    static unsigned long long sums[4] = {~0ull, ~0ull, ~0ull, ~0ull}; // (reused from batch to batch, like the slot's)
+    FmtArgs f{};
+    f.ix = a.ix, f.pair_off = a.pair_off, f.pair_cnt = a.pair_cnt, f.pairs = a.pairs, f.ctr = a.ctr, f.n_topics = n;
+    f.range_cap = 0, f.side_cap = 0; // an exact fit
+    for (uint32_t t = 0; t < n; t++) {
+        f.range_cap += a.pair_cnt[t];
+        for (uint32_t i = 0; i < a.pair_cnt[t]; i++) {
+            const uint32_t c = a.pairs[a.pair_off[t] + i].count;
+            if (c & RANGE_INDIRECT) f.side_cap += c & ~RANGE_INDIRECT;
+        }
+    }
+    f.cnt_r = buf_stale<uint32_t>(s_cnt, 2 * (size_t)(n + 1)), f.cnt_s = f.cnt_r + (n + 1);
+    f.range_ptr = buf_stale<uint32_t>(s_ptr, 2 * (size_t)(n + 1)), f.side_ptr = f.range_ptr + (n + 1);
+    f.out_ranges = buf_stale<MatchRange>(s_out, f.range_cap + 1), f.out_side = buf_stale<uint32_t>(s_side, f.side_cap + 1), f.sums = sums;
+    const uint32_t blocks = (n + 1 + 255) / 256;
+    wemu::grid_size() = blocks;
+    for (uint32_t b = 0; b < blocks; b++)
+        for (uint32_t w = 0; w < 4; w++) wemu::run_wave(b, [&] { k_fmt_count(f); }, w);
+    for (uint32_t t = 0, rr = 0, rs = 0; t <= n; t++) f.range_ptr[t] = rr, f.side_ptr[t] = rs, rr += f.cnt_r[t], rs += f.cnt_s[t];
+    for (uint32_t b = 0; b < blocks; b++)
+        for (uint32_t w = 0; w < 4; w++) wemu::run_wave(b, [&] { k_fmt_emit(f); }, w);
+    if (sums[3] != 0) FAIL("format: flags %llu on a complete batch with buffers that fit\n", sums[3]);
+    if (sums[0] != f.range_cap || sums[1] != f.side_cap) FAIL("format: %llu ranges / %llu side ids, the pairs hold %llu / %llu\n", sums[0], sums[1], f.range_cap, f.side_cap);
+    unsigned long long flagged = 0;
+    for (uint32_t t = 0; t < n; t++) {
+        std::vector<uint32_t> ids;
+        bool bad = false, have = false, side = false;
+        uint32_t last = 0, prev_first = 0;
+        const uint32_t nr = f.range_ptr[t + 1] - f.range_ptr[t];
+        for (uint32_t i = 0; i < nr; i++) {
+            const MatchRange q = f.out_ranges[f.range_ptr[t] + i];
+            const uint32_t len = q.count & ~RANGE_INDIRECT;
+            if (q.count & RANGE_INDIRECT) {
+                side = true;
+                if (q.begin < f.side_ptr[t] || q.begin + len > f.side_ptr[t + 1]) FAIL("format row %u: the list [%u, +%u) leaves the row's side slice [%u, %u)\n", t, q.begin, len, f.side_ptr[t], f.side_ptr[t + 1]);
+            }
+            cov.fmt_empty += len == 0, cov.fmt_empty_lists += len == 0 && (q.count & RANGE_INDIRECT);
+            if (len == 0) continue;
+            const uint32_t first = (q.count & RANGE_INDIRECT) ? f.out_side[q.begin] : q.begin;
+            if (have && first <= last) bad = true;
+            if (have && nr <= 32 && first <= prev_first) FAIL("format row %u (%u ranges): first id %u behind first id %u: not ascending\n", t, nr, first, prev_first);
+            prev_first = first;
+            for (uint32_t k = 0; k < len; k++) ids.push_back((q.count & RANGE_INDIRECT) ? f.out_side[q.begin + k] : q.begin + k);
+            last = ids.back(), have = true;
+        }
+        if (bad) std::sort(ids.begin(), ids.end());
+        if (ids != rows[t]) FAIL("format row %u (%u ranges%s): the strict consumer's row of %zu ids is not the expanded row of %zu ids\n", t, nr, bad ? ", ordered" : "", ids.size(), rows[t].size());
+        flagged += bad;
+        // include/bmq.h: no row of up to 32 ranges overlaps after a rebuild; rows of more come as matched, and the walk does not match in id order
+        if (g_fresh_index && bad && nr <= 32) FAIL("format row %u (%u ranges): ranges overlap on an index without mutations\n", t, nr);
+        cov.fmt_fresh_rows += g_fresh_index, cov.fmt_fresh_over += g_fresh_index && nr > 32, cov.fmt_fresh_overlap_over += g_fresh_index && bad && nr > 32;
+        cov.fmt_ranges += nr, cov.fmt_side_rows += side, cov.fmt_over_rows += nr > 32, cov.fmt_overlap_over += bad && nr > 32, cov.fmt_adj_rows += adj;
+    }
+    if (sums[2] != flagged) FAIL("format: a count of %llu rows whose ranges overlap, the strict consumer ordered %llu rows\n", sums[2], flagged);
+    cov.fmt_overlap_rows += flagged;
+    return 0;
+}
 
 // one batch through walk (+ slow) + expand; rows -> sorted id lists
 template <int TC, int QC, int PC>
@@ -205,6 +273,7 @@ static int run_batch(const DistIndexView& ix, const std::vector<std::string>& tn
         cov.ids += rows[t].size();
     }
     cov.rows += n, cov.batches++;
+    if (run_format(a, rows, cov, adj)) return 1;
     n_visit = a.ctr->n_visit; // (summed by k_expand from the walk's block records / added by k_walk_slow)
     row_visit.clear();
     if (adj) // BatchArgs.visit_cnt is wired: per row of the dense batch; row t's figure is that of its run head
@@ -402,6 +471,8 @@ int main(int argc, char** argv) {
             for (auto& c : family)
                 for (auto& k : chain_keys(c)) ks.insert(k);
             ks.insert(fam_key("+", "p0")), ks.insert(fam_key("+/+", "pp0"));
+            // a filter whose id set becomes a list and is emptied: "el/x" holds one route from here, gets two by apply and loses all three; its sibling "el/+" keeps one
+            ks.insert(fam_key("el/x", "e0")), ks.insert(fam_key("el/+", "sib"));
             for (uint32_t i = 0; i < 40; i++) ks.insert(fam_key("+/f" + std::to_string(i), "p0c")), ks.insert(fam_key("+/+/f" + std::to_string(i), "pp0c"));
             std::vector<uint8_t> bytes;
             std::vector<uint32_t> off{0};
@@ -480,6 +551,8 @@ int main(int argc, char** argv) {
                         for (auto& k : chain_keys(c)) put(k);
             // the own routes of P0 and PP0 leave with the leaves and come back with them: in between their own filter words are all-ones
             if (state == S_LEAVE) del(fam_key("+", "p0")), del(fam_key("+/+", "pp0"));
+            if (state == S_OWN_ON_INNER) put(fam_key("el/x", "e1")), put(fam_key("el/x", "e2"));
+            if (state == S_OTHER_KIND) del(fam_key("el/x", "e0")), del(fam_key("el/x", "e1")), del(fam_key("el/x", "e2"));
             if (state == S_BACK) put(fam_key("+", "p0")), put(fam_key("+/+", "pp0"));
             if (!keys.empty() && apply_ops(keys, ops)) return 1;
             if (state == S_COMPACT) { // a new generation from the live keys: ids are ranks again, nodes without routes below them are gone
@@ -564,6 +637,7 @@ int main(int argc, char** argv) {
                         blocks.insert(blocks.begin() + (long)rnd(blocks.size() + 1), blk); // (anywhere among the others: a wave of an ungrouped batch holds many tenants)
                     }
                 }
+                blocks.insert(blocks.begin() + (long)rnd(blocks.size() + 1), {{fam_t, "el/x"}}); // (the emptied list and its sibling)
                 std::vector<std::pair<uint32_t, std::string>> rowsrc;
                 for (auto& b : blocks) rowsrc.insert(rowsrc.end(), b.begin(), b.end());
                 const bool grouped = bt != 2; // the third batch of a state arrives in any order: waves hold many tenants each (MIXED)
@@ -608,6 +682,7 @@ int main(int argc, char** argv) {
                 for (int sw = 0; sw < 2; sw++) {
                     DistIndexView ix = h.view();
                     ix.filter_off = sw ? 0xFFFFFFFFu : 0u;
+                    g_fresh_index = state == S_FRESH || state == S_COMPACT;
                     std::vector<std::vector<uint32_t>> got;
                     std::vector<uint32_t> row_visit;
                     unsigned long long n_visit = 0;
@@ -641,6 +716,16 @@ int main(int argc, char** argv) {
            (unsigned long long)cov.split_adj, (unsigned long long)cov.split_overflow);
     if (rounds >= 8 && (!cov.split_blocks || !cov.split_overflow || !cov.split_adj)) FAIL("coverage: the cases missed k_expand's split blocks: %llu listed, %llu overflowed, %llu in ordered batches\n",
                                                                                          (unsigned long long)cov.split_blocks, (unsigned long long)cov.split_overflow, (unsigned long long)cov.split_adj);
+    printf("RANGES format behind every batch: %llu ranges, %llu rows with side lists, %llu rows of more than 32 ranges (%llu of them with overlapping ranges), %llu empty ranges (%llu of them "
+           "emptied id lists), %llu rows the strict consumer ordered, %llu rows of ordered batches; on indexes without mutations %llu rows, %llu of more than 32 ranges, %llu of those with overlapping ranges\n",
+           (unsigned long long)cov.fmt_ranges, (unsigned long long)cov.fmt_side_rows, (unsigned long long)cov.fmt_over_rows, (unsigned long long)cov.fmt_overlap_over,
+           (unsigned long long)cov.fmt_empty, (unsigned long long)cov.fmt_empty_lists, (unsigned long long)cov.fmt_overlap_rows, (unsigned long long)cov.fmt_adj_rows,
+           (unsigned long long)cov.fmt_fresh_rows, (unsigned long long)cov.fmt_fresh_over, (unsigned long long)cov.fmt_fresh_overlap_over);
+    // (no floor on empty ranges: an id list emptied by deletes goes back to (0, 0) -- bmq_build_core.h, the end of the group step -- and k_walk emits no range of count 0;
+    // the directed filter "el/x" below is such a list.  tools/emu/format_emu.cpp feeds the format kernels empty ranges directly)
+    if (rounds >= 8 && (!cov.fmt_side_rows || !cov.fmt_over_rows || !cov.fmt_fresh_over || !cov.fmt_overlap_rows || !cov.fmt_adj_rows))
+        FAIL("coverage: the cases missed a shape of the RANGES format: rows with side lists %llu, rows of more than 32 ranges %llu (%llu on an index without mutations), ordered rows %llu\n",
+             (unsigned long long)cov.fmt_side_rows, (unsigned long long)cov.fmt_over_rows, (unsigned long long)cov.fmt_fresh_over, (unsigned long long)cov.fmt_overlap_rows);
     printf("k_walk's work stack and range buffer: the range buffer flushed %llu times, the stack parked %llu times, %llu chunks taken back\n", walk_cov.flushes, walk_cov.parks, walk_cov.restores);
     if (rounds >= 8 && (walk_cov.flushes < 20 || walk_cov.parks < 20 || walk_cov.restores < 20)) FAIL("coverage: the cases hardly touched the cold paths of k_walk's lists\n");
     printf("tail records: %llu read, %llu chain levels resolved from them, %llu leaves reached, %llu tombstones met\n", walk_cov.tails, walk_cov.tail_levels, walk_cov.tail_leaves, walk_cov.tombs);
