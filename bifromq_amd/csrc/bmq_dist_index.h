@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "bmq_build_core.h"
+#include "bmq_order_core.h"
 
 // A tenant's region holds nodes * (1 + slack / 4) two-slot buckets (DistIndex::slack_num, bmq_config.region_slack): 1 -> load factor 0.4
 // (rounds 2-5), 3 -> 0.29, 6 -> 0.2 (the default since round 6).  What the slack buys is fewer SECOND probes: at 0.4 a publish of the survey's
@@ -590,6 +591,185 @@ public:
         bytes = c[1];
         return true;
     }
+    // ---- key-ordered window (bmq_routes_window; bmq_order_core.h): the ids of the first min(max_routes, C) of the C live routes whose key
+    // is >= the cursor (> if exclusive; all live routes without a cursor), ascending in KV order; more = a further live key follows.
+    // The cursor is key bytes (lo) or, by_id, the key of the live route lo_id (nothing is uploaded then: the sweep's next window begins
+    // behind the last key of the one before).  Read-only.  One pass flags and compacts the candidates (o_flag); then a list of ids is
+    // split by <= 255 pivot keys taken at a fixed stride of it (o_pivots ranks them, o_bucket bins every id and counts, the host reads
+    // the counters and decides per bin: kept or dropped, o_scatter moves the kept bins, in bin order, into the other list) until every
+    // piece holds <= ORDER_BUCKET_MAX ids; neighbouring small bins make one piece.  Bins behind the one where the running count reaches
+    // `keep` are dropped, so the same round narrows C candidates to max_routes and orders what it keeps.  The pieces are ranked by
+    // counting in one launch (o_leaves).  A piece that is split again lies inside ONE bin of even number, which holds none of the
+    // round's pivots (order_bin_one) while its list held 255: every round shortens what it splits, so the loop ends.
+    // A piece at [off, off + n) of one list owns that range of both lists: its children are written there.
+    // the scratch holds such a call already (nothing is allocated or freed by it)
+    bool window_fits(uint32_t lo_len) const {
+        return !built || next_id == 0 ||
+               (o_list_cap[0] >= next_id && o_list_cap[1] >= next_id && o_bins_cap >= next_id && o_ctr_cap >= O_CTR_WORDS && o_out_cap >= ORDER_WINDOW_MAX &&
+                o_leaves_cap >= O_LEAVES_MAX && o_key_cap >= (size_t)lo_len + 32);
+    }
+    uint64_t window_scratch_bytes() const {
+        return 4 * (uint64_t)(o_list_cap[0] + o_list_cap[1] + o_ctr_cap + o_out_cap) + 2 * (uint64_t)o_bins_cap + sizeof(OrderLeaf) * (uint64_t)o_leaves_cap + o_key_cap;
+    }
+    bool window(const uint8_t* lo, uint32_t lo_len, bool has_lo, bool exclusive, bool by_id, uint32_t lo_id, uint32_t max_routes, uint32_t* out_ids,
+                uint32_t& out_n, uint32_t& more, OrderStats& st) {
+        error.clear();
+        out_n = more = 0;
+        st.n_calls++;
+        if (max_routes > ORDER_WINDOW_MAX) return fail("window: more than BMQ_WINDOW_MAX routes asked for");
+        if (!built || next_id == 0) return true;
+        if (by_id && (lo_id >= next_id || !has_lo)) return fail("window: no such route to begin behind");
+        if (!ensure_buf(o_list[0], o_list_cap[0], next_id) || !ensure_buf(o_list[1], o_list_cap[1], next_id) || !ensure_buf(o_bins, o_bins_cap, next_id) ||
+            !ensure_buf(o_ctr, o_ctr_cap, O_CTR_WORDS) || !ensure_buf(o_out, o_out_cap, ORDER_WINDOW_MAX) || !ensure_buf(o_leaves, o_leaves_cap, O_LEAVES_MAX) ||
+            !ensure_buf(o_key, o_key_cap, (size_t)lo_len + 32))
+            return false;
+        OrderCursor cur{};
+        cur.key = o_key;
+        cur.len = by_id ? 0u : lo_len;
+        cur.flags = (has_lo ? 1u : 0u) | (exclusive ? 2u : 0u) | (by_id ? 4u : 0u);
+        cur.id = lo_id;
+        uint32_t* hist = o_ctr + 16;
+        uint32_t* cursor = hist + ORDER_BINS;
+        uint32_t* base = cursor + ORDER_BINS;
+        uint32_t* piv = base + ORDER_BINS;
+        uint32_t C = 0;
+        if ((has_lo && !by_id && lo_len && !x.copy_in_async(o_key, lo, lo_len)) || !x.zero(o_ctr, sizeof(uint32_t)) ||
+            !x.o_flag(mut(), next_id, cur, o_list[0], o_ctr) || !x.copy_out(&C, o_ctr, sizeof(C)))
+            return xfail();
+        if (C > next_id) return fail("window: more candidates than ids");
+        st.n_candidates += C;
+        const uint32_t take = std::min(C, max_routes);
+        more = C > max_routes ? 1u : 0u;
+        if (take == 0) return true;
+        struct Piece {
+            uint32_t list, off, n, keep, out, depth;
+        };
+        std::vector<Piece> work{Piece{0u, 0u, C, take, 0u, 0u}};
+        std::vector<OrderLeaf> leaves;
+        std::vector<uint32_t> h(ORDER_BINS), b(ORDER_BINS);
+        while (!work.empty()) {
+            const Piece s = work.back();
+            work.pop_back();
+            if (s.n <= ORDER_BUCKET_MAX) {
+                leaves.push_back(OrderLeaf{s.list, s.off, s.n, s.keep, s.out});
+                st.max_bucket = std::max<uint64_t>(st.max_bucket, s.n);
+                continue;
+            }
+            st.n_rounds++;
+            if (s.depth) st.n_rebucketed++;
+            const uint32_t* src = o_list[s.list] + s.off;
+            if (!x.zero(hist, sizeof(uint32_t) * 2 * ORDER_BINS) || !x.o_pivots(mut(), src, s.n / ORDER_PIVOTS, ORDER_PIVOTS, piv) ||
+                !x.o_bucket(mut(), src, s.n, piv, ORDER_PIVOTS, o_bins, hist) || !x.copy_out(h.data(), hist, sizeof(uint32_t) * ORDER_BINS))
+                return xfail();
+            uint32_t acc = 0, c_at = 0, c_n = 0, seen = 0; // kept so far; the piece being gathered from small neighbouring bins
+            auto flush = [&]() {
+                if (c_n) work.push_back(Piece{s.list ^ 1u, s.off + c_at, c_n, std::min(c_n, s.keep - c_at), s.out + c_at, s.depth + 1});
+                c_n = 0;
+            };
+            for (uint32_t k = 0; k < ORDER_BINS; k++) {
+                const uint32_t cnt = h[k];
+                seen += cnt;
+                b[k] = ORDER_DROP;
+                if (cnt == 0 || acc >= s.keep) continue;
+                if (cnt >= s.n) return fail("window: a bin holds its whole list");
+                b[k] = s.off + acc;
+                if (c_n + cnt > ORDER_BUCKET_MAX) flush();
+                if (c_n == 0) c_at = acc;
+                c_n += cnt;
+                acc += cnt;
+                if (cnt > ORDER_BUCKET_MAX) flush(); // (a piece of its own: it is split again)
+            }
+            flush();
+            if (seen != s.n || acc < s.keep) return fail("window: the bins do not add up");
+            if (!x.copy_in_async(base, b.data(), sizeof(uint32_t) * ORDER_BINS) || !x.o_scatter(src, o_bins, s.n, base, cursor, o_list[s.list ^ 1u]) || !x.sync())
+                return xfail();
+        }
+        if (leaves.size() > O_LEAVES_MAX) return fail("window: more pieces than ids");
+        st.n_bucket_sorts += leaves.size();
+        if (!x.copy_in_async(o_leaves, leaves.data(), sizeof(OrderLeaf) * leaves.size()) ||
+            !x.o_leaves(mut(), o_list[0], o_list[1], o_leaves, (uint32_t)leaves.size(), o_out) || !x.copy_out(out_ids, o_out, sizeof(uint32_t) * (size_t)take))
+            return xfail();
+        out_n = take;
+        return true;
+    }
+    // ---- the dist worker's GC sweep (DW/DistWorkerCoProc.java:554-701) over positions of the key order, the keys fetched window by window
+    // as the loop reaches them: the first window of a phase from its cursor, every further one behind the last key of the one before
+    // (by id: nothing is uploaded).  include/bmq.h, bmq_routes_gc_sweep, says what the loop does; out_ids[0 .. min(inspected, cap)).
+    struct SweepResult {
+        uint64_t inspected = 0;
+        bool wrapped = false, has_next = false;
+        uint32_t next_id = 0;
+    };
+    static uint64_t sweep_keys_needed(uint32_t step_hint, uint32_t scan_quota) { // of one phase: the last inspected position, and the one the cursor ends on
+        const uint64_t step = std::max<uint32_t>(step_hint, 1u), quota = scan_quota > 0 ? (uint64_t)scan_quota : 256 * step;
+        return (quota - 1) * step + 2;
+    }
+    bool gc_sweep(const uint8_t* start, uint32_t start_len, bool has_start, uint32_t step_hint, uint32_t scan_quota, uint32_t* out_ids, uint32_t cap, SweepResult& res,
+                  OrderStats& st) {
+        res = SweepResult{};
+        const uint64_t step = std::max<uint32_t>(step_hint, 1u), quota = scan_quota > 0 ? (uint64_t)scan_quota : 256 * step;
+        const uint64_t need = sweep_keys_needed(step_hint, scan_quota);
+        if (need > 16ull * ORDER_WINDOW_MAX) return fail("a sweep of more than 16 windows per phase");
+        struct Stream { // the live keys from a cursor on, in key order
+            std::vector<uint32_t> ids;
+            uint64_t budget;  // keys the sweep can still ask for
+            bool more = true; // keys may follow ids.back()
+        } a{{}, need}, b{{}, need}; // from the start key; from the first key
+        bool failed = false;
+        auto at = [&](Stream& sm, bool from_start, uint64_t i) -> uint32_t { // the id at position i of a stream, NONE behind its last key
+            while (i >= sm.ids.size()) {
+                if (!sm.more || sm.budget == 0) return NONE;
+                const uint32_t want = (uint32_t)std::min<uint64_t>(sm.budget, ORDER_WINDOW_MAX);
+                const size_t have = sm.ids.size();
+                sm.ids.resize(have + want);
+                uint32_t n = 0, m = 0;
+                const bool ok = have ? window(nullptr, 0, true, true, true, sm.ids[have - 1], want, sm.ids.data() + have, n, m, st)
+                                     : window(from_start ? start : nullptr, from_start ? start_len : 0u, from_start && has_start, false, false, 0, want, sm.ids.data() + have, n, m, st);
+                if (!ok) {
+                    failed = true;
+                    return NONE;
+                }
+                sm.ids.resize(have + n);
+                sm.budget -= n;
+                sm.more = m != 0;
+                if (n == 0) return NONE;
+            }
+            return sm.ids[i];
+        };
+        const uint32_t first = at(a, true, 0); // K[p0]: the session's start key
+        if (failed) return false;
+        if (first == NONE) { // (:584-591: nothing at or behind the cursor, whatever lies in front of it)
+            res.wrapped = true;
+            return true;
+        }
+        uint64_t pos = 0; // a position of the stream in use
+        uint32_t next = NONE;
+        for (;;) {
+            uint32_t id = res.wrapped ? at(b, false, pos) : at(a, true, pos);
+            if (id == NONE && !res.wrapped && !failed) { // the tail, the first time: on from the first key
+                res.wrapped = true;
+                pos = 0;
+                id = at(b, false, 0);
+            }
+            if (failed) return false;
+            if (id == NONE) break;            // the tail again
+            if (res.wrapped && id == first) { // the start key after the wrap: the cursor stays on it
+                next = id;
+                break;
+            }
+            if (res.inspected < cap) out_ids[res.inspected] = id;
+            res.inspected++;
+            if (res.inspected >= quota) { // one position on, whatever the step
+                next = res.wrapped ? at(b, false, pos + 1) : at(a, true, pos + 1);
+                if (failed) return false;
+                break;
+            }
+            pos += step;
+        }
+        res.has_next = next != NONE;
+        res.next_id = next != NONE ? next : 0u;
+        return true;
+    }
     // The per-tenant census of the live keys inside `b` (TenantsStats.doReset, DW/TenantsStats.java:229-246: normal and shared routes per
     // tenant from the key's flag; :140-162: the tenant's space): one READ-ONLY pass over kref[0, next_id) (on the device: k_b_census,
     // bmq_census_kernels.h) into a table of four 64-bit counters per directory slot, zeroed per call.  Tenants with nothing inside are
@@ -742,6 +922,8 @@ public:
         rel(g_ids); rel(g_refs); rel(g_offs); rel(g_bytes); rel(g_census); rel(q_bnd.buf); rel(imp_bnd.buf);
         rel(f_bytes); rel(f_refs); rel(f_ids);
         f_bytes_cap = f_refs_cap = f_ids_cap = 0;
+        rel(o_list[0]); rel(o_list[1]); rel(o_bins); rel(o_ctr); rel(o_out); rel(o_leaves); rel(o_key);
+        o_list_cap[0] = o_list_cap[1] = o_bins_cap = o_ctr_cap = o_out_cap = o_leaves_cap = o_key_cap = 0;
         q_bnd = imp_bnd = StagedBoundary{};
         imp_bounded = false;
         trie_cap = trie_used = 0; dir_slots = 0; names_cap = names_used = 0; dict_slots = 0; dpool_cap = 0; rp_cap = 0; id_cap = next_id = 0;
@@ -768,6 +950,15 @@ private:
     unsigned long long* f_refs = nullptr;
     uint32_t* f_ids = nullptr;
     size_t f_bytes_cap = 0, f_refs_cap = 0, f_ids_cap = 0;
+    // window: the two id lists, the bin of every id of the list being split, [candidates | 16 .. : counters per bin, places taken per
+    // bin, the bins' places, the sorted pivots], the window, the pieces to rank, the cursor key
+    static constexpr size_t O_CTR_WORDS = 16 + 3 * ORDER_BINS + 256, O_LEAVES_MAX = ORDER_WINDOW_MAX + 1;
+    uint32_t* o_list[2] = {nullptr, nullptr};
+    uint16_t* o_bins = nullptr;
+    uint32_t *o_ctr = nullptr, *o_out = nullptr;
+    OrderLeaf* o_leaves = nullptr;
+    uint8_t* o_key = nullptr;
+    size_t o_list_cap[2] = {0, 0}, o_bins_cap = 0, o_ctr_cap = 0, o_out_cap = 0, o_leaves_cap = 0, o_key_cap = 0;
     // a boundary in exec memory: [inside keys, their bytes: two 64-bit counters][start key][end key]
     struct StagedBoundary {
         uint8_t* buf = nullptr;

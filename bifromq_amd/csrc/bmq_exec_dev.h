@@ -17,6 +17,7 @@
 #include "bmq_delivery_kernels.h"
 #include "bmq_fanout_core.h"
 #include "bmq_fanout_kernels.h"
+#include "bmq_order_kernels.h"
 #include "bmq_retain_build_kernels.h"
 #include "bmq_retain_core.h"
 #include "bmq_retain_snap_kernels.h"
@@ -463,6 +464,30 @@ struct DevExec {
     bool find_keys(const DistIndexMut& ix, const KeySource& ks, uint32_t n, uint32_t* out, uint32_t* n_bad) {
         if (n == 0) return true;
         hipLaunchKernelGGL(k_b_find_keys, dim3((unsigned)std::min<unsigned long long>(((unsigned long long)n + BK - 1) / BK, FIND_BLOCKS)), dim3(BK), 0, stream, ix, ks, n, out, n_bad);
+        return launched();
+    }
+    // ---- key-ordered window (bmq_order_core.h, bmq_order_kernels.h): bounded grids that stride ----
+    static dim3 o_grid(uint32_t n) { return dim3((unsigned)std::min<unsigned long long>(((unsigned long long)n + ORD_BLOCK - 1) / ORD_BLOCK, ORD_BLOCKS)); }
+    bool o_flag(const DistIndexMut& ix, uint32_t n_ids, const OrderCursor& c, uint32_t* cand, uint32_t* n_cand) {
+        if (n_ids == 0) return true;
+        hipLaunchKernelGGL(k_o_flag, o_grid(n_ids), dim3(ORD_BLOCK), 0, stream, ix, n_ids, c, cand, n_cand);
+        return launched();
+    }
+    bool o_pivots(const DistIndexMut& ix, const uint32_t* list, uint32_t stride, uint32_t P, uint32_t* piv) {
+        hipLaunchKernelGGL(k_o_pivots, dim3(P), dim3(64), 0, stream, ix, list, stride, P, piv);
+        return launched();
+    }
+    bool o_bucket(const DistIndexMut& ix, const uint32_t* list, uint32_t n, const uint32_t* piv, uint32_t P, uint16_t* bins, uint32_t* hist) {
+        hipLaunchKernelGGL(k_o_bucket, o_grid(n), dim3(ORD_BLOCK), 0, stream, ix, list, n, piv, P, bins, hist);
+        return launched();
+    }
+    bool o_scatter(const uint32_t* list, const uint16_t* bins, uint32_t n, const uint32_t* base, uint32_t* cursor, uint32_t* dst) {
+        hipLaunchKernelGGL(k_o_scatter, o_grid(n), dim3(ORD_BLOCK), 0, stream, list, bins, n, base, cursor, dst);
+        return launched();
+    }
+    bool o_leaves(const DistIndexMut& ix, const uint32_t* list0, const uint32_t* list1, const OrderLeaf* leaves, uint32_t n_leaves, uint32_t* out) {
+        if (n_leaves == 0) return true;
+        hipLaunchKernelGGL(k_o_leaves, dim3(n_leaves * ORDER_BUCKET_MAX), dim3(64), 0, stream, ix, list0, list1, leaves, out);
         return launched();
     }
     // ---- fan-out grouping (bmq_fanout.h) ----

@@ -15,6 +15,7 @@
 #include "bmq_build_core.h"
 #include "bmq_delivery_core.h"
 #include "bmq_fanout_core.h"
+#include "bmq_order_core.h"
 #include "bmq_retain_build_core.h"
 #include "bmq_retain_core.h"
 #include "bmq_retain_snap_core.h"
@@ -143,6 +144,35 @@ struct HostExec {
             if (find_keys_one(ix, ks, (uint32_t)i, out)) bad.fetch_add(1, std::memory_order_relaxed);
         });
         *n_bad += bad.load();
+        return true;
+    }
+    // ---- key-ordered window (bmq_order_core.h; k_o_* on the device): the same passes, one after the other ----
+    bool o_flag(const DistIndexMut& ix, uint32_t n_ids, OrderCursor c, uint32_t* cand, uint32_t* n_cand) {
+        order_cursor_resolve(ix, c);
+        for (uint32_t i = 0; i < n_ids; i++)
+            if (order_flag_one(ix, i, c)) cand[(*n_cand)++] = i;
+        return true;
+    }
+    bool o_pivots(const DistIndexMut& ix, const uint32_t* list, uint32_t stride, uint32_t P, uint32_t* piv) {
+        for (uint32_t j = 0; j < P; j++) piv[order_rank_one(ix, list, P, stride, j)] = list[(size_t)j * stride];
+        return true;
+    }
+    bool o_bucket(const DistIndexMut& ix, const uint32_t* list, uint32_t n, const uint32_t* piv, uint32_t P, uint16_t* bins, uint32_t* hist) {
+        par(n, [&](size_t i) { bins[i] = (uint16_t)order_bin_one(ix, list[i], piv, P); });
+        for (uint32_t i = 0; i < n; i++) hist[bins[i]]++;
+        return true;
+    }
+    bool o_scatter(const uint32_t* list, const uint16_t* bins, uint32_t n, const uint32_t* base, uint32_t* cursor, uint32_t* dst) {
+        for (uint32_t i = 0; i < n; i++)
+            if (base[bins[i]] != ORDER_DROP) dst[base[bins[i]] + cursor[bins[i]]++] = list[i];
+        return true;
+    }
+    bool o_leaves(const DistIndexMut& ix, const uint32_t* list0, const uint32_t* list1, const OrderLeaf* leaves, uint32_t n_leaves, uint32_t* out) {
+        par((size_t)n_leaves * ORDER_BUCKET_MAX, [&](size_t i) { // (one item per key slot of a piece: the ranking is the expensive pass)
+            const OrderLeaf& lf = leaves[i / ORDER_BUCKET_MAX];
+            const uint32_t j = (uint32_t)(i % ORDER_BUCKET_MAX);
+            if (j < lf.n) order_leaf_one(ix, lf.list ? list1 : list0, lf, j, out);
+        });
         return true;
     }
     // ---- fan-out grouping (bmq_fanout.h) ----

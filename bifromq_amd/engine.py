@@ -12,6 +12,7 @@ import numpy as np
 from . import _lib
 
 INT_MAX = 2**31 - 1
+BMQ_WINDOW_MAX = 65536  # include/bmq.h
 STATUS = {0: "OK", -1: "INVAL", -2: "NODEVICE", -3: "NOSPACE", -4: "NOMEM", -5: "HIP", -6: "RANGE", -7: "STATE"}
 
 
@@ -394,6 +395,50 @@ class Engine:
         out = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
         self._check(_lib.lib().bmq_routes_find(self.h, _ptr(data), _ptr(off), n, _ptr(out)))
         return out
+
+    def window(self, start=None, n: int = BMQ_WINDOW_MAX, exclusive: bool = False) -> Tuple[np.ndarray, bool]:
+        """bmq_routes_window: (the ids of the first n live routes whose key is >= start -- > start if exclusive, all without a start --
+        in KV order, whether a further live key follows); ordered on the device, read-only.  n <= BMQ_WINDOW_MAX."""
+        lo = None if start is None else _b(start)
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        got, more = C.c_uint32(), C.c_uint32()
+        self._check(_lib.lib().bmq_routes_window(self.h, lo, 0 if lo is None else len(lo), 1 if exclusive else 0, n, _ptr(out), C.byref(got), C.byref(more)))
+        return out[:got.value], bool(more.value)
+
+    def gc_sweep(self, start_key=None, step_hint: int = 1, scan_quota: int = 0, boundary=None) -> Tuple[np.ndarray, bool, Optional[bytes]]:
+        """bmq_routes_gc_sweep, the loop of DistWorkerCoProc.gc (DW/DistWorkerCoProc.java:554-701): (the inspected route ids in inspection
+        order, wrapped, nextStartKey or None).  boundary = (start, end), either may be None: the clamp of :563-574 -- a cursor below the
+        start or at / beyond the end becomes the start (the engine holds exactly its range's keys and takes no boundary itself)."""
+        lo = None if start_key is None else _b(start_key)
+        if lo is not None and boundary is not None:
+            b0, b1 = (None if x is None else _b(x) for x in boundary)
+            if (b0 is not None and lo < b0) or (b1 is not None and lo >= b1):
+                lo = b0
+        step = max(int(step_hint), 1)
+        cap = scan_quota if scan_quota > 0 else 256 * step
+        rep = _lib.GcSweepReply()
+        while True:
+            out = np.zeros(max(cap, 1), dtype=np.uint32)
+            rc = _lib.lib().bmq_routes_gc_sweep(self.h, lo, 0 if lo is None else len(lo), step_hint, scan_quota, _ptr(out), cap, C.byref(rep))
+            if rc == -3 and rep.inspected > cap:
+                cap = int(rep.inspected)
+                continue
+            self._check(rc)
+            return out[:rep.inspected], bool(rep.wrapped), (self.route_key(rep.next_route_id) if rep.has_next else None)
+
+    def window_info(self) -> _lib.WindowInfo:
+        """bmq_routes_window_info_get: cumulative counters of this engine's windows (those of sweeps included)"""
+        out = _lib.WindowInfo()
+        self._check(_lib.lib().bmq_routes_window_info_get(self.h, C.byref(out)))
+        return out
+
+    def split_key_after(self, prefix, split_at_scale: int) -> Optional[bytes]:
+        """FanoutSplitHinter.doEstimate's seek-and-advance (DW/hinter/FanoutSplitHinter.java:187-198) as one window: the key at index
+        split_at_scale among the live keys >= prefix (not bounded by the prefix), None if there are not that many."""
+        if split_at_scale < 0 or split_at_scale >= BMQ_WINDOW_MAX:
+            raise ValueError("split_at_scale must lie in [0, BMQ_WINDOW_MAX)")
+        ids, _ = self.window(prefix, split_at_scale + 1)
+        return self.route_key(int(ids[split_at_scale])) if len(ids) > split_at_scale else None
 
     def find(self, tenant, topic_filter) -> List[int]:
         t, f = _b(tenant), _b(topic_filter)

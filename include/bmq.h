@@ -182,6 +182,44 @@ int bmq_routes_apply_wait(bmq_engine* e);
  * A host-only engine runs the same per-key function on host threads. */
 int bmq_routes_find(const bmq_engine* e, const uint8_t* keys, const uint32_t* key_off, uint32_t n, uint32_t* out_ids);
 
+/* ---- reads in KEY order: a window of the route keys, and the dist worker's GC sweep over it ------------------------------------
+ * The index holds every route key in device memory, under ids that follow the key order only right after bmq_rebuild.  A WINDOW is
+ * what a KV iterator gives after seek(lo): the ids of the first min(max_routes, C) of the C live routes whose key is >= lo (> lo with
+ * lo_exclusive != 0; lo NULL: from the first key; a present lo may be empty), ascending in KV order -- unsigned bytes, a proper prefix
+ * first, as BoundaryUtil orders keys.  *out_more = 1 if a further live key follows the window.  lo is compared as bytes: it need not
+ * be a well-formed route key.  max_routes <= BMQ_WINDOW_MAX (more: BMQ_E_INVAL); out_route_ids holds max_routes ids.
+ * Read-only, on the device: one pass flags and compacts the candidates, rounds of <= 255 pivot keys narrow them to max_routes and
+ * split them into buckets, each bucket is ranked by counting, a wave per key (bifromq_amd/csrc/bmq_order_kernels.h).  The key bytes stay where they
+ * are; only the cursor goes up and counters and ids come down.  Locks and state are those of bmq_routes_find / bmq_routes_count_in:
+ * an open bmq_routes_apply_async batch is completed first, the SERVING generation answers while a compaction runs, the epoch stays;
+ * the persistent matcher leaves only when the call's scratch has to grow (the first call, and after the id space grew).  A host-only
+ * engine runs the same passes on the host.  FanoutSplitHinter.doEstimate (bifromq-dist-worker/.../hinter/FanoutSplitHinter.java:
+ * 187-198) is one window: seek(prefix), split_at_scale steps, the key there. */
+#define BMQ_WINDOW_MAX 65536u
+int bmq_routes_window(const bmq_engine* e, const uint8_t* lo, uint32_t lo_len /* lo NULL: from the first key */, uint32_t lo_exclusive,
+                      uint32_t max_routes, uint32_t* out_route_ids, uint32_t* out_n, uint32_t* out_more);
+/* DistWorkerCoProc.gc (bifromq-dist-worker/.../DistWorkerCoProc.java:554-701; DistWorkerCleaner.java:57-66,216-217 drives it) over
+ * positions of the key order K[0 .. N): step = max(step_hint, 1), quota = scan_quota > 0 ? scan_quota : 256 * step, p0 = the position
+ * of the first key >= start_key (0: start_key NULL).  N == 0 or p0 == N: inspected 0, wrapped 1, no next key (:584-591; also when keys
+ * lie in front of the cursor).  Else positions p0, p0 + step, ... are inspected; running off the tail the first time sets wrapped and
+ * goes on at position 0 (the stride's phase is not kept), where the sweep stops in front of a position that holds K[p0] -- tested at
+ * inspected positions only, so a stride that jumps over p0 goes on and inspects routes again (:613-617) -- and running off the tail a
+ * second time ends it without a next key.  After the quota-th inspection the cursor moves ONE position on and the sweep ends
+ * (:654-657).  has_next / next_route_id name the key under the cursor when the sweep ends, if there is one (nextStartKey, :669-671;
+ * bmq_route_key gives its bytes).  out_route_ids[0 .. inspected) are the inspected routes in inspection order; cap < inspected:
+ * BMQ_E_NOSPACE with out->inspected = the count needed.  The keys come from successive windows of <= BMQ_WINDOW_MAX, each behind the
+ * last key of the one before; a sweep that could span more than 16 of them per phase ((quota - 1) * step + 2 keys) is refused with
+ * BMQ_E_INVAL -- the reference's largest is 51 200 keys.  The boundary clamp of :563-574 is the caller's (the engine holds exactly its
+ * range's keys), and so are the routeCache.isCached filter, the members of group routes and the CheckRequests. */
+typedef struct bmq_gc_sweep_reply { uint32_t struct_size, inspected, wrapped, has_next, next_route_id; uint64_t epoch; } bmq_gc_sweep_reply;
+int bmq_routes_gc_sweep(const bmq_engine* e, const uint8_t* start_key, uint32_t start_len /* start_key NULL: absent */, uint32_t step_hint,
+                        uint32_t scan_quota, uint32_t* out_route_ids, uint32_t cap /* < inspected: BMQ_E_NOSPACE, reply.inspected = needed */,
+                        bmq_gc_sweep_reply* out);
+/* Cumulative counters of the windows of this engine (those of sweeps included): calls, candidates behind the cursors, bucketing rounds,
+ * buckets ranked, the largest of them, rounds that split a bucket of an earlier round again; last_ms: host time of the last window or sweep. */
+typedef struct bmq_window_info { uint32_t struct_size, window_max, bucket_max; uint64_t n_calls, n_candidates, n_rounds, n_bucket_sorts, max_bucket, n_rebucketed; double last_ms; } bmq_window_info;
+int bmq_routes_window_info_get(const bmq_engine* e, bmq_window_info* out);
+
 /* Maintenance: re-build the index from its own live routes (the keys are gathered from the HBM key store).  Frees what churn leaves
  * behind until then -- abandoned tenant regions and id lists, trie nodes and dictionary tokens of filters nobody subscribes to any
  * more (bmq_index_info.garbage_bytes) -- and re-numbers the route ids to ranks: a new generation, like bmq_rebuild. */

@@ -29,6 +29,7 @@
 #define NK(name) Java_org_apache_bifromq_retain_store_gpu_NativeKeys_##name
 #define NR(name) Java_org_apache_bifromq_retain_store_gpu_NativeRange_##name
 #define NF(name) Java_org_apache_bifromq_routes_gpu_NativeRoutes_##name
+#define NG(name) Java_org_apache_bifromq_routes_gpu_NativeGc_##name
 
 static void throw_state(JNIEnv* env, bmq_engine* e, const char* what, int rc) {
     char msg[512];
@@ -118,6 +119,52 @@ JNIEXPORT void JNICALL NF(routesFind)(JNIEnv* env, jclass c, jlong h, jobject ke
     (void)c;
     const int rc = bmq_routes_find(ENGINE(h), (const uint8_t*)ADDR(keys), (const uint32_t*)ADDR(keyOff), (uint32_t)n, (uint32_t*)ADDR(outIds));
     if (rc != BMQ_OK) throw_state(env, ENGINE(h), "bmq_routes_find", rc);
+}
+/* NativeGc: int routesWindow(long engine, ByteBuffer lo, int loLen, boolean exclusive, int maxRoutes, IntBuffer outIds, IntBuffer outMore)
+ * bmq_routes_window: the first maxRoutes live routes at / behind lo in KV order (lo null: from the first key) -> their count; outMore[0] = 1 if
+ * more follow.  All buffers DIRECT. */
+JNIEXPORT jint JNICALL NG(routesWindow)(JNIEnv* env, jclass c, jlong h, jobject lo, jint loLen, jboolean exclusive, jint maxRoutes, jobject outIds, jobject outMore) {
+    (void)c;
+    uint32_t n = 0, more = 0;
+    const int rc = bmq_routes_window(ENGINE(h), (const uint8_t*)ADDR(lo), (uint32_t)loLen, exclusive ? 1u : 0u, (uint32_t)maxRoutes, (uint32_t*)ADDR(outIds), &n, &more);
+    if (rc != BMQ_OK) {
+        throw_state(env, ENGINE(h), "bmq_routes_window", rc);
+        return 0;
+    }
+    if (outMore) ((uint32_t*)ADDR(outMore))[0] = more;
+    return (jint)n;
+}
+/* NativeGc: int routesGcSweep(long engine, ByteBuffer startKey, int startLen, int stepHint, int scanQuota, IntBuffer outIds, int cap, LongBuffer reply)
+ * bmq_routes_gc_sweep: DistWorkerCoProc.gc's loop over the key order -> inspected count, -(needed) if cap is too small; reply[0 .. 4) = wrapped,
+ * has next start key, its route id, epoch. */
+JNIEXPORT jint JNICALL NG(routesGcSweep)(JNIEnv* env, jclass c, jlong h, jobject startKey, jint startLen, jint stepHint, jint scanQuota, jobject outIds, jint cap,
+                                         jobject reply) {
+    (void)c;
+    bmq_gc_sweep_reply r;
+    const int rc = bmq_routes_gc_sweep(ENGINE(h), (const uint8_t*)ADDR(startKey), (uint32_t)startLen, (uint32_t)stepHint, (uint32_t)scanQuota, (uint32_t*)ADDR(outIds),
+                                       (uint32_t)cap, &r);
+    if (rc == BMQ_E_NOSPACE && r.inspected > (uint32_t)cap) return -(jint)r.inspected;
+    if (rc != BMQ_OK) {
+        throw_state(env, ENGINE(h), "bmq_routes_gc_sweep", rc);
+        return 0;
+    }
+    if (reply) {
+        int64_t* out = (int64_t*)ADDR(reply);
+        out[0] = r.wrapped, out[1] = r.has_next, out[2] = r.next_route_id, out[3] = (int64_t)r.epoch;
+    }
+    return (jint)r.inspected;
+}
+/* NativeGc: int routeKey(long engine, int routeId, ByteBuffer out)   bmq_route_key -> key length, -(needed) if out is too small */
+JNIEXPORT jint JNICALL NG(routeKey)(JNIEnv* env, jclass c, jlong h, jint id, jobject out) {
+    (void)c;
+    uint32_t len = 0;
+    const int rc = bmq_route_key(ENGINE(h), (uint32_t)id, (uint8_t*)ADDR(out), (uint32_t)CAP(out), &len);
+    if (rc == BMQ_E_NOSPACE) return -(jint)len;
+    if (rc != BMQ_OK) {
+        throw_state(env, ENGINE(h), "bmq_route_key", rc);
+        return 0;
+    }
+    return (jint)len;
 }
 /* void routesApplyAsync(long engine, ByteBuffer keys, IntBuffer keyOff, ByteBuffer ops, int n) / void routesApplyWait(long engine)
  * bmq_routes_apply_async / _wait: the ops are uploaded beside the batch in flight and applied behind it; the call returns after the enqueue.

@@ -17,6 +17,8 @@
 //   * after every step the delivery plan (Delivery::plan, bmq_delivery.h) of a random CSR -- live, deleted and never handed out ids, fresh member
 //     tables whose members live under the deliverer keys of normal routes and under keys of their own -- against a plain merge, by key bytes, of
 //     Fanout::group and Share::resolve over the same CSR: the same rows per DelivererKey in (topic, route, sender) order, special groups last.
+//   * after every step reads in key order (DistIndex::window, ::gc_sweep: bmq_routes_window / bmq_routes_gc_sweep) against the model's map order:
+//     windows from every kind of cursor, sweeps of random step and quota against the reference's loop walked over the map.
 // Build + run: make -C bifromq_amd/csrc fuzz   (tests/test_host.py runs short rounds)
 #include <cstdio>
 #include <algorithm>
@@ -233,6 +235,111 @@ int main(int argc, char** argv) {
     uint64_t checks = 0, n_apply = 0, n_rebuild = 0, fo_pairs = 0, n_generations = 0, n_census = 0, n_bounded = 0, n_imports = 0, plus_stat[2] = {0, 0};
     Fanout<HostExec> fo(hx, h); // fan-out grouping (bmq_fanout.h) over the same index, kept across rebuilds and applies
     fo.initial_table = 4;       // 36 deliverer keys: the group table grows twice
+    // ---- reads in key order (bmq_routes_window / bmq_routes_gc_sweep: DistIndex::window and ::gc_sweep) against the model, whose std::map IS the
+    // key order: windows from cursors absent, equal to a key, a proper prefix of one, a key plus a byte, below and above all keys, inclusive and
+    // exclusive, of 1 key, a few, all and more than all; sweeps of random step and quota from such cursors against the loop of
+    // DW/DistWorkerCoProc.java:554-701 walked over the map with an iterator -- and nothing may change by looking
+    uint64_t n_windows = 0, n_sweeps = 0, n_sweeps_wrapped = 0, n_windows_over_a_bucket = 0;
+    OrderStats order_stats;
+    auto check_order = [&](int round, const char* what) -> bool {
+        std::vector<std::pair<std::string, uint32_t>> mk(model.begin(), model.end()); // sorted by key
+        auto rand_cursor = [&](bool& has) {
+            has = true;
+            const std::string some = mk.empty() ? rand_key() : mk[rnd(mk.size())].first;
+            switch (rnd(7)) {
+            case 0: has = false; return std::string();
+            case 1: return some;
+            case 2: return some.substr(0, some.size() - 1 - rnd(std::min<size_t>(some.size() - 1, 4)));
+            case 3: return some + std::string(1, (char)rnd(256));
+            case 4: return std::string();
+            case 5: return std::string(3, '\xff');
+            default: return rand_key();
+            }
+        };
+        auto lower = [&](const std::string& lo, bool has, bool exclusive) {
+            if (!has) return (size_t)0;
+            auto cmp = [](const std::pair<std::string, uint32_t>& e, const std::string& k) { return e.first < k; };
+            size_t at = (size_t)(std::lower_bound(mk.begin(), mk.end(), lo, cmp) - mk.begin());
+            if (exclusive && at < mk.size() && mk[at].first == lo) at++;
+            return at;
+        };
+        DistIndexStats before, after;
+        h.stats(before);
+        for (int w = 0; w < 6; w++) {
+            bool has;
+            const std::string lo = rand_cursor(has);
+            const bool exclusive = has && rnd(2);
+            const uint32_t sizes[5] = {1, 7, (uint32_t)mk.size(), (uint32_t)mk.size() + 3, (uint32_t)(1 + rnd(mk.size() + 1))};
+            const uint32_t m = std::min<uint32_t>(sizes[rnd(5)], ORDER_WINDOW_MAX);
+            std::vector<uint32_t> got(m ? m : 1, 12345u);
+            uint32_t n = 0, more = 0;
+            std::vector<uint8_t> lob(lo.begin(), lo.end()); // (the exact bytes: no padding)
+            if (!h.window(has ? lob.data() : nullptr, (uint32_t)lob.size(), has, exclusive, false, 0, m, got.data(), n, more, order_stats)) {
+                fprintf(stderr, "round %d (%s): window failed: %s\n", round, what, h.error.c_str());
+                return false;
+            }
+            const size_t at = lower(lo, has, exclusive), want = std::min<size_t>(m, mk.size() - at);
+            if (n != want || (more != 0) != (mk.size() - at > m)) {
+                fprintf(stderr, "round %d (%s): window gives %u routes, more %u; the model %zu of %zu behind the cursor\n", round, what, n, more, want, mk.size() - at);
+                return false;
+            }
+            for (size_t i = 0; i < want; i++)
+                if (got[i] != mk[at + i].second) {
+                    fprintf(stderr, "round %d (%s): window position %zu holds id %u, the model %u\n", round, what, i, got[i], mk[at + i].second);
+                    return false;
+                }
+            n_windows++, n_windows_over_a_bucket += mk.size() - at > ORDER_BUCKET_MAX;
+        }
+        for (int w = 0; w < 4; w++) {
+            bool has;
+            const std::string lo = rand_cursor(has);
+            const uint32_t step_hint = (uint32_t)rnd(12), scan_quota = rnd(3) == 0 ? 0u : (uint32_t)(1 + rnd(mk.size() + 2));
+            // the reference's loop over the model
+            const uint64_t step = std::max<uint32_t>(step_hint, 1u), quota = scan_quota ? scan_quota : 256 * step;
+            std::vector<uint32_t> x_ids;
+            bool x_wrapped = false;
+            size_t itr = lower(lo, has, false);
+            long long x_start = -1;
+            if (itr >= mk.size()) x_wrapped = true, itr = mk.size();
+            else
+                for (;;) {
+                    if (itr >= mk.size()) {
+                        if (x_wrapped) break;
+                        itr = 0, x_wrapped = true;
+                    }
+                    if (x_wrapped && (long long)itr == x_start) break;
+                    if (x_start < 0) x_start = (long long)itr;
+                    x_ids.push_back(mk[itr].second);
+                    if (x_ids.size() >= quota) {
+                        itr++;
+                        break;
+                    }
+                    itr += step; // (the skip loop and the next() behind it: invalid as soon as one of them leaves the tail)
+                }
+            const bool x_has_next = itr < mk.size();
+            const uint32_t cap = rnd(4) == 0 ? (uint32_t)(x_ids.size() / 2) : (uint32_t)x_ids.size() + 2;
+            std::vector<uint32_t> got(cap ? cap : 1, 12345u);
+            std::vector<uint8_t> lob(lo.begin(), lo.end());
+            DistIndex<HostExec>::SweepResult r;
+            if (!h.gc_sweep(has ? lob.data() : nullptr, (uint32_t)lob.size(), has, step_hint, scan_quota, got.data(), cap, r, order_stats)) {
+                fprintf(stderr, "round %d (%s): gc_sweep failed: %s\n", round, what, h.error.c_str());
+                return false;
+            }
+            if (r.inspected != x_ids.size() || r.wrapped != x_wrapped || r.has_next != x_has_next || (x_has_next && r.next_id != mk[itr].second) ||
+                !std::equal(x_ids.begin(), x_ids.begin() + std::min<size_t>(cap, x_ids.size()), got.begin())) {
+                fprintf(stderr, "round %d (%s): gc_sweep(step %u, quota %u) inspected %llu wrapped %d next %d; the model %zu %d %d\n", round, what, step_hint, scan_quota,
+                        (unsigned long long)r.inspected, (int)r.wrapped, (int)r.has_next, x_ids.size(), (int)x_wrapped, (int)x_has_next);
+                return false;
+            }
+            n_sweeps++, n_sweeps_wrapped += x_wrapped;
+        }
+        h.stats(after);
+        if (before.n_nodes != after.n_nodes || before.n_tokens != after.n_tokens || before.n_routes != after.n_routes || before.next_id != after.next_id) {
+            fprintf(stderr, "round %d (%s): a read in key order changed the index\n", round, what);
+            return false;
+        }
+        return true;
+    };
     // ---- key -> id (bmq_routes_find: DistIndex::find_keys over find_key_one) against the model, after every step: a sample of the live keys, keys
     // deleted at some point (live again or not: the model decides), random keys, repeats -- and nothing may come into being by looking
     std::vector<std::string> once_deleted;
@@ -282,7 +389,7 @@ int main(int argc, char** argv) {
             return false;
         }
         n_find += q.size();
-        return true;
+        return check_order(round, what);
     };
     // ---- member tables of shared subscriptions through a generation change (bmq_config.share_carry: Share::carry_prepare / carry_finish) ----
     Share<HostExec> sh(hx);
@@ -966,6 +1073,12 @@ int main(int argc, char** argv) {
     DistIndexStats st;
     h.stats(st);
     printf("layout v3: %llu of the %llu nodes the checks discovered through a '+' edge below a non-root node lay beside their parent\n", (unsigned long long)plus_stat[0], (unsigned long long)plus_stat[1]);
+    printf("reads in key order: %llu windows, %llu sweeps (%llu wrapped); %llu bucketing rounds, %llu buckets ranked\n", (unsigned long long)n_windows, (unsigned long long)n_sweeps,
+           (unsigned long long)n_sweeps_wrapped, (unsigned long long)order_stats.n_rounds, (unsigned long long)order_stats.n_bucket_sorts);
+    if (n_windows == 0 || n_sweeps == 0 || n_sweeps_wrapped == 0 || (n_windows_over_a_bucket != 0 && order_stats.n_rounds == 0)) {
+        fprintf(stderr, "the reads in key order were not exercised\n");
+        return 1;
+    }
     printf("find and carry: %llu keys looked up, %llu carries (%llu tables carried, %llu dropped)\n", (unsigned long long)n_find, (unsigned long long)n_carries,
            (unsigned long long)n_tables_carried, (unsigned long long)n_tables_dropped);
     printf("delivery plan: %llu rows planned, %llu groups held normal and member rows\n", (unsigned long long)dl_rows, (unsigned long long)dl_merged);
