@@ -28,7 +28,7 @@ ABI_SYMBOLS = [
     "bmq_batcher_match_all", "bmq_batcher_submit", "bmq_batcher_stats_get", "bmq_poller_stats_get", "bmq_poller_control",
     "bmq_route_cache_create", "bmq_route_cache_destroy", "bmq_route_cache_get", "bmq_route_cache_get_async", "bmq_route_cache_get_batch", "bmq_batcher_match_batch", "bmq_route_cache_is_cached", "bmq_route_cache_apply",
     "bmq_route_cache_rebuild", "bmq_route_cache_reset", "bmq_route_cache_expire", "bmq_route_cache_stats_get", "bmq_route_cache_tenant_stats_get",
-    "bmq_route_cache_set_caps", "bmq_route_cache_set_event_sink", "bmq_routes_cap", "bmq_fanout_group", "bmq_fanout_group_dev", "bmq_fanout_info_get", "bmq_share_members_apply", "bmq_share_resolve", "bmq_share_resolve_dev", "bmq_share_member", "bmq_share_info_get", "bmq_share_carry_info_get", "bmq_delivery_plan", "bmq_delivery_plan_dev", "bmq_delivery_wait", "bmq_routes_find", "bmq_routes_window", "bmq_routes_gc_sweep", "bmq_routes_window_info_get", "bmq_router_find_by_key", "bmq_router_find_by_boundary", "bmq_retain_range_lookup", "bmq_router_create", "bmq_router_destroy", "bmq_router_lookup_key", "bmq_router_lookup_boundary", "bmq_router_retain_lookup",
+    "bmq_route_cache_set_caps", "bmq_route_cache_set_event_sink", "bmq_routes_cap", "bmq_fanout_group", "bmq_fanout_group_dev", "bmq_fanout_info_get", "bmq_share_members_apply", "bmq_share_resolve", "bmq_share_resolve_dev", "bmq_share_member", "bmq_share_info_get", "bmq_share_carry_info_get", "bmq_delivery_plan", "bmq_delivery_plan_dev", "bmq_delivery_wait", "bmq_routes_find", "bmq_routes_window", "bmq_routes_gc_sweep", "bmq_routes_window_info_get", "bmq_routes_prefix_census", "bmq_routes_prefix_census_info_get", "bmq_router_find_by_key", "bmq_router_find_by_boundary", "bmq_retain_range_lookup", "bmq_router_create", "bmq_router_destroy", "bmq_router_lookup_key", "bmq_router_lookup_boundary", "bmq_router_retain_lookup",
 ]
 
 
@@ -134,6 +134,11 @@ class GcSweepReply(C.Structure):
 class WindowInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("window_max", C.c_uint32), ("bucket_max", C.c_uint32), ("n_calls", C.c_uint64), ("n_candidates", C.c_uint64),
                 ("n_rounds", C.c_uint64), ("n_bucket_sorts", C.c_uint64), ("max_bucket", C.c_uint64), ("n_rebucketed", C.c_uint64), ("last_ms", C.c_double)]
+
+
+class PrefixCensusInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("prefix_max", C.c_uint32), ("n_calls", C.c_uint64), ("n_prefixes", C.c_uint64), ("n_distinct", C.c_uint64),
+                ("n_nested", C.c_uint64), ("n_keys_scanned", C.c_uint64), ("max_chain", C.c_uint64), ("last_ms", C.c_double)]
 
 
 class FanoutInfo(C.Structure):
@@ -287,6 +292,8 @@ def lib() -> C.CDLL:
             "bmq_routes_window": (C.c_int, [vp, C.c_char_p, u32, u32, u32, vp, P(u32), P(u32)]),
             "bmq_routes_gc_sweep": (C.c_int, [vp, C.c_char_p, u32, u32, u32, vp, u32, P(GcSweepReply)]),
             "bmq_routes_window_info_get": (C.c_int, [vp, P(WindowInfo)]),
+            "bmq_routes_prefix_census": (C.c_int, [vp, vp, vp, u32, vp]),
+            "bmq_routes_prefix_census_info_get": (C.c_int, [vp, P(PrefixCensusInfo)]),
             "bmq_router_find_by_key": (C.c_int, [vp, vp, vp, vp, vp, u32, C.c_char_p, u32, P(i32)]),
             "bmq_router_find_by_boundary": (C.c_int, [vp, vp, vp, vp, vp, u32, C.c_uint8, C.c_char_p, u32, C.c_char_p, u32, P(u32), P(u32)]),
             "bmq_retain_range_lookup": (C.c_int, [C.c_char_p, u32, vp, vp, u32, vp, vp, vp, vp, vp, u32, u32, vp]),

@@ -32,6 +32,7 @@
 
 #include "bmq_build_core.h"
 #include "bmq_order_core.h"
+#include "bmq_prefix_core.h"
 
 // A tenant's region holds nodes * (1 + slack / 4) two-slot buckets (DistIndex::slack_num, bmq_config.region_slack): 1 -> load factor 0.4
 // (rounds 2-5), 3 -> 0.29, 6 -> 0.2 (the default since round 6).  What the slack buys is fewer SECOND probes: at 0.4 a publish of the survey's
@@ -801,6 +802,85 @@ public:
         });
         return true;
     }
+    // ---- per-prefix census (bmq_routes_prefix_census; bmq_prefix_core.h): for each of n byte prefixes (prefix i = bytes[off[i], off[i + 1]),
+    // any order, repeats and nesting allowed) the live keys that start with it, per flag, and the sum of their lengths -- what
+    // reader.size([prefix, upperBound(prefix))) tells the split hinter per prefix (DW/hinter/FanoutSplitHinter.java:175-178), for a whole
+    // mutation batch in ONE READ-ONLY pass over kref[0, next_id) (on the device: k_b_prefix_census, bmq_prefix_kernels.h).  The host sorts
+    // and de-duplicates the prefixes (at most PREFIX_MAX strings) and links every distinct one to its parent; the pass adds every key to
+    // the deepest prefix it has; the sums are carried to the parents here and copied out through the input-to-slot map.
+    // before_grow() runs before the scratch of the call is allocated anew (a free waits for every stream of the device).
+    static size_t prefix_need(size_t m, size_t bytes) { return 32 * m + 4 * (m + 1) + 4 * m + bytes + 16; }
+    template <class F> bool prefix_census(const uint8_t* bytes, const uint32_t* off, uint32_t n, uint64_t* out, PrefixStats& stats, F&& before_grow) {
+        error.clear();
+        for (size_t i = 0; i < 4 * (size_t)n; i++) out[i] = 0;
+        stats.n_calls++;
+        stats.n_prefixes += n;
+        if (n == 0) return true;
+        auto at = [&](uint32_t i) { return bytes + off[i]; };
+        auto len = [&](uint32_t i) { return (unsigned long long)(off[i + 1] - off[i]); };
+        std::vector<uint32_t> order(n);
+        for (uint32_t i = 0; i < n; i++) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t c) { return key_compare(at(a), len(a), at(c), len(c)) < 0; });
+        std::vector<uint32_t> slot_of(n), rep; // input -> table slot; table slot -> one input that holds its bytes
+        for (uint32_t j = 0; j < n; j++) {
+            if (j == 0 || key_compare(at(order[j - 1]), len(order[j - 1]), at(order[j]), len(order[j])) != 0) rep.push_back(order[j]);
+            slot_of[order[j]] = (uint32_t)rep.size() - 1;
+        }
+        const uint32_t m = (uint32_t)rep.size();
+        // the parents: sorted with a proper prefix first, the table is the preorder of the prefixes' trie -- a stack holds the chain of
+        // the entry before, and the nearest entry of it that is a proper prefix of this one is the parent
+        std::vector<uint32_t> parent(m, NONE), depth(m, 0), stack;
+        uint64_t nested = 0, chain = 0, total = 0;
+        for (uint32_t s = 0; s < m; s++) {
+            while (!stack.empty() && !prefix_is_of(at(rep[stack.back()]), len(rep[stack.back()]), at(rep[s]), len(rep[s]))) stack.pop_back();
+            if (!stack.empty()) {
+                parent[s] = stack.back();
+                depth[s] = depth[stack.back()] + 1;
+                nested++;
+                chain = std::max<uint64_t>(chain, depth[s]);
+            }
+            stack.push_back(s);
+            total += len(rep[s]);
+        }
+        stats.n_distinct += m;
+        stats.n_nested += nested;
+        stats.max_chain = std::max(stats.max_chain, chain);
+        if (!built || next_id == 0) return true;
+        stats.n_keys_scanned += next_id;
+        // exec memory: [4 m counters][m + 1 offsets][m parents][the prefixes' bytes]
+        const size_t o_off = 32 * (size_t)m, o_par = o_off + 4 * ((size_t)m + 1), o_bytes = o_par + 4 * (size_t)m, need = prefix_need(m, total);
+        if (need > g_prefix_cap) before_grow();
+        if (!ensure_buf(g_prefix, g_prefix_cap, need)) return false;
+        std::vector<uint8_t> h(need - o_off, 0);
+        uint32_t* h_off = reinterpret_cast<uint32_t*>(h.data());
+        uint32_t* h_par = reinterpret_cast<uint32_t*>(h.data() + (o_par - o_off));
+        uint8_t* h_bytes = h.data() + (o_bytes - o_off);
+        uint32_t pos = 0;
+        for (uint32_t s = 0; s < m; s++) {
+            h_off[s] = pos;
+            h_par[s] = parent[s];
+            if (len(rep[s])) memcpy(h_bytes + pos, at(rep[s]), len(rep[s]));
+            pos += (uint32_t)len(rep[s]);
+        }
+        h_off[m] = pos;
+        PrefixTable T{};
+        T.bytes = g_prefix + o_bytes;
+        T.off = reinterpret_cast<const uint32_t*>(g_prefix + o_off);
+        T.parent = reinterpret_cast<const uint32_t*>(g_prefix + o_par);
+        T.n = m;
+        unsigned long long* table = reinterpret_cast<unsigned long long*>(g_prefix);
+        std::vector<unsigned long long> t(4 * (size_t)m);
+        if (!x.zero(g_prefix, o_off) || !x.copy_in_async(g_prefix + o_off, h.data(), h.size()) || !x.prefix_census(mut(), next_id, T, table) ||
+            !x.copy_out(t.data(), g_prefix, o_off))
+            return xfail();
+        for (uint32_t s = m; s-- > 0;) { // a child sorts behind its parent: its sums are complete when its turn comes
+            if (parent[s] == NONE) continue;
+            for (uint32_t w = 0; w < 4; w++) t[4 * (size_t)parent[s] + w] += t[4 * (size_t)s + w];
+        }
+        for (uint32_t i = 0; i < n; i++) // (repeated inputs share a slot)
+            for (uint32_t w = 0; w < 4; w++) out[4 * (size_t)i + w] = t[4 * (size_t)slot_of[i] + w];
+        return true;
+    }
     // The buffers a chunk of `n` ids / `bytes` key bytes of a generation change goes through, taken NOW: the first bmq_compact_poll used to
     // allocate them -- a dozen device allocations beside a saturated matcher, the one batch of a compaction that took 10 ms instead of 0.35.
     bool reserve_import(uint32_t n, uint64_t bytes) {
@@ -919,7 +999,7 @@ public:
         rel(trie); rel(dir); rel(names); rel(dict); rel(dpool); rel(route_pos); rel(kref); rel(khash); rel(kpool); rel(bc);
         rel(s_key_off); rel(s_op); rel(s_put_rank); rel(s_dir_slot); rel(s_nn); rel(s_flag); rel(s_target); rel(s_order);
         rel(s_sorted_target); rel(s_group_done); rel(s_unknown); rel(s_grow); rel(s_bt_first); rel(s_bt_nodes); rel(s_bt_keys); rel(s_bt_dir);
-        rel(g_ids); rel(g_refs); rel(g_offs); rel(g_bytes); rel(g_census); rel(q_bnd.buf); rel(imp_bnd.buf);
+        rel(g_ids); rel(g_refs); rel(g_offs); rel(g_bytes); rel(g_census); rel(g_prefix); rel(q_bnd.buf); rel(imp_bnd.buf);
         rel(f_bytes); rel(f_refs); rel(f_ids);
         f_bytes_cap = f_refs_cap = f_ids_cap = 0;
         rel(o_list[0]); rel(o_list[1]); rel(o_bins); rel(o_ctr); rel(o_out); rel(o_leaves); rel(o_key);
@@ -927,7 +1007,7 @@ public:
         q_bnd = imp_bnd = StagedBoundary{};
         imp_bounded = false;
         trie_cap = trie_used = 0; dir_slots = 0; names_cap = names_used = 0; dict_slots = 0; dpool_cap = 0; rp_cap = 0; id_cap = next_id = 0;
-        kpool_cap = kpool_used = 0; s_cap = 0; s_bt_cap = 0; s_grow_cap = 0; g_ids_cap = g_refs_cap = g_offs_cap = g_bytes_cap = g_census_cap = 0;
+        kpool_cap = kpool_used = 0; s_cap = 0; s_bt_cap = 0; s_grow_cap = 0; g_ids_cap = g_refs_cap = g_offs_cap = g_bytes_cap = g_census_cap = g_prefix_cap = 0;
         tenant_slot.clear(); free_regions.clear(); dir_h.clear(); names_h.clear(); trie_garbage = 0;
         built = false;
     }
@@ -946,6 +1026,8 @@ private:
     size_t g_ids_cap = 0, g_refs_cap = 0, g_offs_cap = 0, g_bytes_cap = 0;
     unsigned long long* g_census = nullptr; // tenant_stats: four counters per directory slot
     size_t g_census_cap = 0;
+    uint8_t* g_prefix = nullptr; // prefix_census: [four counters per distinct prefix][offsets][parents][prefix bytes]
+    size_t g_prefix_cap = 0;
     uint8_t* f_bytes = nullptr; // find_keys: the batch's key bytes, references and ids (+ the count of malformed keys)
     unsigned long long* f_refs = nullptr;
     uint32_t* f_ids = nullptr;

@@ -233,6 +233,8 @@ struct bmq_engine {
     DevBuf fo_buf; // staging of bmq_fanout_group
     OrderStats order_stats; // bmq_routes_window / bmq_routes_gc_sweep (bmq_order_engine.inc): cumulative, across generations
     double order_last_ms = 0;
+    PrefixStats prefix_stats; // bmq_routes_prefix_census (bmq_prefix_engine.inc): cumulative, across generations
+    double prefix_last_ms = 0;
     // receivers of shared subscriptions (bmq_share.h): member tables + resolve scratch, created by the first call
     std::unique_ptr<Share<DevExec>> dsh;
     std::unique_ptr<Share<HostExec>> hsh;
@@ -2263,3 +2265,4 @@ int32_t bmq_java_string_hash(const uint8_t* utf8, uint32_t len) { return java_st
 #include "bmq_delivery_engine.inc"
 #include "bmq_formats.inc"
 #include "bmq_order_engine.inc"
+#include "bmq_prefix_engine.inc"

@@ -18,6 +18,7 @@
 #include "bmq_fanout_core.h"
 #include "bmq_fanout_kernels.h"
 #include "bmq_order_kernels.h"
+#include "bmq_prefix_kernels.h"
 #include "bmq_retain_build_kernels.h"
 #include "bmq_retain_core.h"
 #include "bmq_retain_snap_kernels.h"
@@ -536,6 +537,13 @@ struct DevExec {
     bool census(const DistIndexMut& ix, uint32_t n, const KeyBoundary& b, unsigned long long* table) {
         if (n == 0) return true;
         hipLaunchKernelGGL(k_b_census, dim3(census_grid(n)), dim3(CENSUS_WAVES * 64), 0, stream, ix, n, b, table);
+        return launched();
+    }
+    // table[4 * table slot ..] += live keys of kref[0, n) per flag, and their bytes, under the deepest prefix of T each has (k_b_prefix_census,
+    // bmq_prefix_kernels.h; T's arrays: exec memory)
+    bool prefix_census(const DistIndexMut& ix, uint32_t n, const PrefixTable& T, unsigned long long* table) {
+        if (n == 0 || T.n == 0) return true;
+        hipLaunchKernelGGL(k_b_prefix_census, dim3(census_grid(n)), dim3(CENSUS_WAVES * 64), 0, stream, ix, n, T, table);
         return launched();
     }
     // ---- fan-out grouping, fast path (bmq_fanout_kernels.h): counting sort that carries its payload ----

@@ -16,6 +16,7 @@
 #include "bmq_delivery_core.h"
 #include "bmq_fanout_core.h"
 #include "bmq_order_core.h"
+#include "bmq_prefix_core.h"
 #include "bmq_retain_build_core.h"
 #include "bmq_retain_core.h"
 #include "bmq_retain_snap_core.h"
@@ -240,6 +241,17 @@ struct HostExec {
             if (d == NONE) return;
             __atomic_fetch_add(table + 4 * (size_t)d + (flag - 1), 1ull, __ATOMIC_RELAXED);
             __atomic_fetch_add(table + 4 * (size_t)d + 3, (unsigned long long)len, __ATOMIC_RELAXED);
+        });
+        return true;
+    }
+    // table[4 * table slot ..] += live keys of kref[0, n) per flag, and their bytes, under the deepest prefix of T each has (k_b_prefix_census on the device)
+    bool prefix_census(const DistIndexMut& ix, uint32_t n, const PrefixTable& T, unsigned long long* table) {
+        par(n, [&](size_t i) {
+            uint32_t flag = 0, len = 0;
+            const uint32_t s = prefix_key_one(ix, (uint32_t)i, T, flag, len);
+            if (s == NONE) return;
+            __atomic_fetch_add(table + 4 * (size_t)s + (flag - 1), 1ull, __ATOMIC_RELAXED);
+            __atomic_fetch_add(table + 4 * (size_t)s + 3, (unsigned long long)len, __ATOMIC_RELAXED);
         });
         return true;
     }

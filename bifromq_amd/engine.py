@@ -13,6 +13,7 @@ from . import _lib
 
 INT_MAX = 2**31 - 1
 BMQ_WINDOW_MAX = 65536  # include/bmq.h
+BMQ_PREFIX_MAX = 65536  # include/bmq.h
 STATUS = {0: "OK", -1: "INVAL", -2: "NODEVICE", -3: "NOSPACE", -4: "NOMEM", -5: "HIP", -6: "RANGE", -7: "STATE"}
 
 
@@ -439,6 +440,22 @@ class Engine:
             raise ValueError("split_at_scale must lie in [0, BMQ_WINDOW_MAX)")
         ids, _ = self.window(prefix, split_at_scale + 1)
         return self.route_key(int(ids[split_at_scale])) if len(ids) > split_at_scale else None
+
+    def prefix_census(self, prefixes: Sequence[bytes] = (), packed: Optional[Tuple[np.ndarray, np.ndarray]] = None) -> np.ndarray:
+        """bmq_routes_prefix_census: uint64 array (n, 4) -- per byte prefix the live keys that start with it with flag 1 / 2 / 3 and the sum
+        of their key lengths (the columns of routes_tenant_stats), all prefixes in one pass over the key store; read-only.  Any order,
+        repeats and nesting allowed; n <= BMQ_PREFIX_MAX."""
+        data, off = pack(list(prefixes)) if packed is None else packed
+        n = len(off) - 1
+        out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        self._check(_lib.lib().bmq_routes_prefix_census(self.h, _ptr(data), _ptr(off), n, _ptr(out)))
+        return out[:n]
+
+    def prefix_census_info(self) -> _lib.PrefixCensusInfo:
+        """bmq_routes_prefix_census_info_get: cumulative counters of this engine's prefix censuses"""
+        out = _lib.PrefixCensusInfo()
+        self._check(_lib.lib().bmq_routes_prefix_census_info_get(self.h, C.byref(out)))
+        return out
 
     def find(self, tenant, topic_filter) -> List[int]:
         t, f = _b(tenant), _b(topic_filter)

@@ -220,6 +220,32 @@ int bmq_routes_gc_sweep(const bmq_engine* e, const uint8_t* start_key, uint32_t 
 typedef struct bmq_window_info { uint32_t struct_size, window_max, bucket_max; uint64_t n_calls, n_candidates, n_rounds, n_bucket_sorts, max_bucket, n_rebucketed; double last_ms; } bmq_window_info;
 int bmq_routes_window_info_get(const bmq_engine* e, bmq_window_info* out);
 
+/* ---- per-prefix census: how many live routes lie under each of a batch of key prefixes ---------------------------------------------
+ * What FanoutSplitHinter.doEstimate asks its KV range per matchRecordKeyPrefix of a mutation batch (bifromq-dist-worker/.../hinter/
+ * FanoutSplitHinter.java:174-178: reader.size([prefix, upperBound(prefix)))), for ALL prefixes of the batch in one pass over the key
+ * store.  Prefix i is prefixes[prefix_off[i] .. prefix_off[i + 1]); out_stats[4 i ..] = live keys under it with flag 1 (normal),
+ * 2 (unordered share), 3 (ordered share), and the sum of their key lengths -- the columns of bmq_routes_tenant_stats.  A live key k
+ * counts for prefix p iff len(k) >= len(p) and k[0, len(p)) == p: a key equal to the prefix counts, the empty prefix counts every
+ * key.  A prefix is compared as bytes: it need not be a well-formed route key nor end at a level or field border, so the granularity
+ * (a tenant, a filter, one route) is the caller's.  Prefixes come in any order; repeats get the same answer; they may nest to any
+ * depth, and a key counts for EVERY prefix that is a prefix of it.  n = 0 returns BMQ_OK; n > BMQ_PREFIX_MAX or a prefix of 16 MiB or
+ * more is BMQ_E_INVAL with nothing written.
+ * Read-only.  The host sorts and de-duplicates the prefixes and links each to its parent (the longest other prefix that is a proper
+ * prefix of it); on the device one lane per key reference finds the last prefix <= its key by binary search, walks up the parent links
+ * to the first one that is a prefix of the key, and the wave adds to that deepest prefix only, reduced per wave as the tenant census is
+ * (bifromq_amd/csrc/bmq_prefix_kernels.h); the sums are then carried from every prefix to its parent.  Only the prefix table goes up and
+ * four counters per distinct prefix come down.  Locks and state are those of bmq_routes_count_in: an open bmq_routes_apply_async batch is
+ * completed first, the SERVING generation answers while a compaction runs (keys mutated since bmq_compact_begin included), the epoch
+ * stays; the persistent matcher leaves only when the call's own device buffers have to grow.  A host-only engine runs the same per-key
+ * function on host threads. */
+#define BMQ_PREFIX_MAX 65536u
+int bmq_routes_prefix_census(const bmq_engine* e, const uint8_t* prefixes, const uint32_t* prefix_off /* n + 1 */, uint32_t n,
+                             uint64_t* out_stats /* 4 * n */);
+/* Cumulative counters of the prefix censuses of this engine: calls, prefixes passed, distinct prefixes, distinct prefixes that have a
+ * parent, key references scanned, the longest chain of parent links seen; last_ms: host time of the last call. */
+typedef struct bmq_prefix_census_info { uint32_t struct_size, prefix_max; uint64_t n_calls, n_prefixes, n_distinct, n_nested, n_keys_scanned, max_chain; double last_ms; } bmq_prefix_census_info;
+int bmq_routes_prefix_census_info_get(const bmq_engine* e, bmq_prefix_census_info* out);
+
 /* Maintenance: re-build the index from its own live routes (the keys are gathered from the HBM key store).  Frees what churn leaves
  * behind until then -- abandoned tenant regions and id lists, trie nodes and dictionary tokens of filters nobody subscribes to any
  * more (bmq_index_info.garbage_bytes) -- and re-numbers the route ids to ranks: a new generation, like bmq_rebuild. */

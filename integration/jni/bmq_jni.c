@@ -30,6 +30,7 @@
 #define NR(name) Java_org_apache_bifromq_retain_store_gpu_NativeRange_##name
 #define NF(name) Java_org_apache_bifromq_routes_gpu_NativeRoutes_##name
 #define NG(name) Java_org_apache_bifromq_routes_gpu_NativeGc_##name
+#define NH(name) Java_org_apache_bifromq_routes_gpu_NativeHinter_##name
 
 static void throw_state(JNIEnv* env, bmq_engine* e, const char* what, int rc) {
     char msg[512];
@@ -153,6 +154,18 @@ JNIEXPORT jint JNICALL NG(routesGcSweep)(JNIEnv* env, jclass c, jlong h, jobject
         out[0] = r.wrapped, out[1] = r.has_next, out[2] = r.next_route_id, out[3] = (int64_t)r.epoch;
     }
     return (jint)r.inspected;
+}
+/* NativeHinter: void routesPrefixCensus(long engine, ByteBuffer prefixes, IntBuffer prefixOff, int n, LongBuffer outStats)
+ * bmq_routes_prefix_census: per byte prefix the live routes that start with it with flag 1 / 2 / 3 and the sum of their key lengths ->
+ * outStats[4 i ..]; all prefixes of a mutation batch in one pass over the key store.  All buffers DIRECT; outStats holds 4 * n longs. */
+JNIEXPORT void JNICALL NH(routesPrefixCensus)(JNIEnv* env, jclass c, jlong h, jobject prefixes, jobject prefixOff, jint n, jobject outStats) {
+    (void)c;
+    if (n < 0 || (n > 0 && (CAP(prefixOff) < (uint64_t)n + 1 || CAP(outStats) < 4u * (uint64_t)n))) { /* (elements: ints, longs) */
+        throw_state(env, ENGINE(h), "routesPrefixCensus (prefixOff holds n + 1 ints, outStats 4 * n longs)", BMQ_E_INVAL);
+        return;
+    }
+    const int rc = bmq_routes_prefix_census(ENGINE(h), (const uint8_t*)ADDR(prefixes), (const uint32_t*)ADDR(prefixOff), (uint32_t)n, (uint64_t*)ADDR(outStats));
+    if (rc != BMQ_OK) throw_state(env, ENGINE(h), "bmq_routes_prefix_census", rc);
 }
 /* NativeGc: int routeKey(long engine, int routeId, ByteBuffer out)   bmq_route_key -> key length, -(needed) if out is too small */
 JNIEXPORT jint JNICALL NG(routeKey)(JNIEnv* env, jclass c, jlong h, jint id, jobject out) {

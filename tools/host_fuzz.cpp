@@ -743,6 +743,31 @@ int main(int argc, char** argv) {
                 }
                 n_census++;
             }
+            // the per-prefix census (bmq_routes_prefix_census: DistIndex::prefix_census, prefix_key_one -- what k_b_prefix_census runs per
+            // lane on the device) over random byte prefixes, nested ones and a repeat included, against the model's keys as std::string
+            // compares them
+            {
+                std::vector<std::string> ps;
+                for (uint32_t i = 0, e = 1 + rnd(40); i < e; i++) ps.push_back(rand_bound());
+                ps.push_back(ps[rnd(ps.size())]);
+                ps.push_back(std::string());
+                std::vector<uint8_t> pb;
+                std::vector<uint32_t> po(1, 0u);
+                for (const std::string& p : ps) pb.insert(pb.end(), p.begin(), p.end()), po.push_back((uint32_t)pb.size());
+                pb.resize(pb.size() + 16, 0);
+                std::vector<uint64_t> got(4 * ps.size(), 77), want(4 * ps.size(), 0);
+                for (auto& e : model) {
+                    const std::string& k = e.first;
+                    const size_t rl = ((size_t)(uint8_t)k[k.size() - 2] << 8) | (uint8_t)k[k.size() - 1];
+                    for (size_t i = 0; i < ps.size(); i++)
+                        if (k.size() >= ps[i].size() && k.compare(0, ps[i].size(), ps[i]) == 0) want[4 * i + (uint8_t)k[k.size() - 3 - rl] - 1]++, want[4 * i + 3] += k.size();
+                }
+                PrefixStats pst;
+                if (!h.prefix_census(pb.data(), po.data(), (uint32_t)ps.size(), got.data(), pst, [] {}) || got != want) {
+                    fprintf(stderr, "round %d: the prefix census differs from the model (%zu prefixes) (%s)\n", round, ps.size(), h.error.c_str());
+                    return 1;
+                }
+            }
             auto key_set = [&](DistIndex<HostExec>& ix, std::set<std::string>& got) {
                 DistIndexStats is;
                 ix.stats(is);
