@@ -25,6 +25,7 @@
 #include "../../include/bmq.h"
 #include "bmq_codec.h"
 #include "bmq_dist_index.h"
+#include "bmq_caps.h"
 #include "bmq_delivery.h"
 #include "bmq_dist_kernels.h"
 #include "bmq_poll_kernel.h"
@@ -243,6 +244,10 @@ struct bmq_engine {
     std::unique_ptr<Delivery<DevExec>> ddl;
     std::unique_ptr<Delivery<HostExec>> hdl;
     DevBuf dl_buf; // staging of bmq_delivery_plan / bmq_delivery_wait
+    // the fan-out caps over a match CSR (bmq_caps.h): scratch of the three passes, created by the first call
+    std::unique_ptr<Caps<DevExec>> dcp;
+    std::unique_ptr<Caps<HostExec>> hcp;
+    DevBuf caps_buf; // staging of bmq_routes_cap_batch; the capped CSR and the events of bmq_delivery_wait_capped
     // multi-GPU exchange inside the library (bmq_exchange.inc): RCCL communicator of this rank, its own stream
     void* comm = nullptr;
     int comm_world = 0, comm_rank = 0;
@@ -1141,6 +1146,7 @@ void bmq_engine_destroy(bmq_engine* e) {
         if (e->ev_lend) (void)hipEventDestroy(e->ev_lend);
         if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
         if (e->ev_join) (void)hipEventDestroy(e->ev_join);
+        e->dcp.reset();
         e->ddl.reset();
         e->dfo.reset();
         e->dsh.reset();
@@ -1151,6 +1157,7 @@ void bmq_engine_destroy(bmq_engine* e) {
         e->dx.tmp = nullptr;
         if (e->stream) (void)hipStreamDestroy(e->stream);
     }
+    e->hcp.reset();
     e->hdl.reset();
     e->hfo.reset(); // (before the index it refers to)
     e->rcmp = bmq_engine::RetainCompaction{}; // (a host-only engine's half-built retain generation: before the executor it refers to)
@@ -2266,3 +2273,4 @@ int32_t bmq_java_string_hash(const uint8_t* utf8, uint32_t len) { return java_st
 #include "bmq_formats.inc"
 #include "bmq_order_engine.inc"
 #include "bmq_prefix_engine.inc"
+#include "bmq_caps_engine.inc"

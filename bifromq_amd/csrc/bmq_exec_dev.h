@@ -19,6 +19,7 @@
 #include "bmq_fanout_kernels.h"
 #include "bmq_order_kernels.h"
 #include "bmq_prefix_kernels.h"
+#include "bmq_caps_kernels.h"
 #include "bmq_retain_build_kernels.h"
 #include "bmq_retain_core.h"
 #include "bmq_retain_snap_kernels.h"
@@ -585,7 +586,7 @@ struct DevExec {
     }
     // ---- optional HIP-event marks between the steps of a pipeline (bmq_set_kernel_timing) ----
     bool marks_on = false;
-    hipEvent_t marks[16] = {}; // 0 .. 7: the resolve and the carry of bmq_share.h, 8 .. 12: the delivery plan
+    hipEvent_t marks[20] = {}; // 0 .. 7: the resolve and the carry of bmq_share.h, 8 .. 12: the delivery plan, 13 .. 16: the fan-out caps
     void mark(int i) {
         if (!marks_on) return;
         if (!marks[i] && hipEventCreate(&marks[i]) != hipSuccess) return;
@@ -642,6 +643,33 @@ struct DevExec {
     bool dl_merge(const DeliveryPlan& P) {
         const uint32_t n = std::max(P.n_rows, P.n_groups + 1);
         hipLaunchKernelGGL(k_dl_merge, grid(n, DL_BLOCK), dim3(DL_BLOCK), 0, stream, P, n);
+        return launched();
+    }
+    // ---- the fan-out caps over a match CSR (bmq_caps.h; kernels: bmq_caps_kernels.h) ----
+    static dim3 caps_grid(unsigned long long n) { return dim3((unsigned)std::min<unsigned long long>((n + CAPS_BLOCK - 1) / CAPS_BLOCK, CAPS_BLOCKS)); }
+    bool caps_classify(const DistIndexMut& ix, const CapsBatch& b) { // row_cnt[] and ctr[] are zeroed before
+        if (b.total == 0) return true;
+        hipLaunchKernelGGL(k_caps_classify, caps_grid(b.total), dim3(CAPS_BLOCK), 0, stream, ix, b);
+        return launched();
+    }
+    bool caps_rows(const CapsBatch& b) {
+        if (b.n_rows == 0) return true;
+        hipLaunchKernelGGL(k_caps_rows, caps_grid(b.n_rows), dim3(CAPS_BLOCK), 0, stream, b);
+        return launched();
+    }
+    bool caps_list(const CapsBatch& b) { // behind the inclusive scan of ev_cnt[]
+        if (b.total == 0) return true;
+        hipLaunchKernelGGL(k_caps_list, caps_grid(b.total), dim3(CAPS_BLOCK), 0, stream, b);
+        return launched();
+    }
+    bool caps_rank(const DistIndexMut& ix, const CapsBatch& b, uint32_t n_work) {
+        if (n_work == 0) return true;
+        hipLaunchKernelGGL(k_caps_rank, grid(n_work, CAPS_BLOCK / 64), dim3(CAPS_BLOCK), 0, stream, ix, b, n_work);
+        return launched();
+    }
+    bool caps_write(const CapsBatch& b) { // behind the inclusive scan of keep[]
+        const uint32_t n = std::max(b.total, b.n_rows + 1);
+        hipLaunchKernelGGL(k_caps_write, caps_grid(n), dim3(CAPS_BLOCK), 0, stream, b, n);
         return launched();
     }
     bool sh_rekey(uint32_t* slot_of, uint32_t id_cap, const uint32_t* new_id, const uint32_t* slot, uint32_t n) {

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "bmq_build_core.h"
+#include "bmq_caps_core.h"
 #include "bmq_delivery_core.h"
 #include "bmq_fanout_core.h"
 #include "bmq_order_core.h"
@@ -256,6 +257,50 @@ struct HostExec {
         return true;
     }
     // ---- receivers of shared subscriptions (bmq_share.h) ----
+    // ---- the fan-out caps over a match CSR (bmq_caps.h): the per-item functions of bmq_caps_core.h; a row's counters belong to one thread ----
+    bool caps_classify(const DistIndexMut& ix, const CapsBatch& b) { // row_cnt[] and ctr[] are zeroed before
+        std::atomic<uint32_t> err{0};
+        par(b.n_rows, [&](size_t r) {
+            uint32_t e = 0;
+            for (uint32_t i = b.row_ptr[r]; i < b.row_ptr[r + 1]; i++) {
+                const uint32_t c = caps_classify_one(ix, b, i, (uint32_t)r, &e);
+                b.cls[i] = (uint8_t)c;
+                if (c == CAPS_PERSISTENT || c == CAPS_GROUP) b.row_cnt[2 * r + (c - CAPS_PERSISTENT)]++;
+            }
+            if (e) err.fetch_or(e);
+        });
+        b.ctr[CAPS_C_ERR] |= err.load();
+        return true;
+    }
+    bool caps_rows(const CapsBatch& b) {
+        for (uint32_t r = 0; r < b.n_rows; r++) {
+            const uint32_t full = caps_row_one(b, r), m = full & 3u;
+            if (full & CAPS_BAD_INDEX) b.ctr[CAPS_C_ERR] |= CAPS_ERR_INDEX;
+            b.ctr[CAPS_C_CLASSIFIED] += m != CAPS_ROW_THROUGH;
+            b.ctr[CAPS_C_RANKED] += m == CAPS_ROW_RANKED;
+            if (m == CAPS_ROW_FALLBACK) b.fb_rows[b.ctr[CAPS_C_FALLBACK]++] = r;
+        }
+        return true;
+    }
+    bool caps_list(const CapsBatch& b) { // behind the inclusive scan of ev_cnt[]
+        if (b.total == 0) return true;
+        b.ctr[CAPS_C_EVENTS] = b.ev_scan[2 * (size_t)b.n_rows - 1];
+        for (uint32_t r = 0; r < b.n_rows; r++)
+            for (uint32_t i = b.row_ptr[r]; i < b.row_ptr[r + 1]; i++)
+                if (caps_list_one(b, i, r)) b.work[b.ctr[CAPS_C_WORK]++] = i;
+        return true;
+    }
+    bool caps_rank(const DistIndexMut& ix, const CapsBatch& b, uint32_t n_work) {
+        par(n_work, [&](size_t item) {
+            const uint32_t p = b.work[item], r = fo_row_of(b.row_ptr, b.n_rows, p);
+            caps_settle_one(b, p, r, caps_rank_one(ix, b, p, r));
+        });
+        return true;
+    }
+    bool caps_write(const CapsBatch& b) { // behind the inclusive scan of keep[]
+        par(std::max(b.total, b.n_rows + 1), [&](size_t i) { caps_write_one(b, (uint32_t)i); });
+        return true;
+    }
     void mark(int) {} // (HIP-event marks of the device executor)
     float mark_ms(int, int) { return 0; }
     bool sh_count(const DistIndexMut& ix, const ShareTables& T, const ShareBatch& b) {

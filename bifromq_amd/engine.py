@@ -782,6 +782,77 @@ class Engine:
             raise self._delivery_error(rc, info)
         return tot.value, info
 
+    # ---- the fan-out caps of MatchedRoutes over a whole match batch (DW/cache/MatchedRoutes.java:87-141) ------------------------------
+    @staticmethod
+    def _caps_table(caps):
+        """(pf, gf) or [(pf, gf), ...] -> (max_pf, max_gf) int32 arrays; what does not fit an int32 is the caller's error"""
+        t = np.asarray(caps, dtype=np.int64).reshape(-1, 2)
+        if t.size and (t.max() > 0x7FFFFFFF or t.min() < -0x80000000):
+            raise ValueError("a fan-out cap outside int32")
+        return np.ascontiguousarray(t[:, 0], dtype=np.int32), np.ascontiguousarray(t[:, 1], dtype=np.int32)
+
+    def _caps_error(self, rc: int, info: "_lib.CapsInfo", n_events: int) -> BmqError:
+        err = BmqError(rc, (_lib.lib().bmq_last_error(self.h) or b"").decode())
+        err.info = info
+        err.n_events = n_events
+        return err
+
+    def routes_cap_batch(self, row_ptr, route_ids, caps, row_caps=None, events_cap: Optional[int] = None, out_cap: Optional[int] = None):
+        """bmq_routes_cap_batch: MatchedRoutes' caps over a match CSR, every row under the table entry row_caps names (None: entry 0);
+        caps = (pf, gf) or a list of such pairs -> (row_ptr, ids, class_counts [n_rows, 2], events [n, 4] int32, info).  events holds at most
+        events_cap events (default: every one), info.n_events counts all."""
+        row = np.ascontiguousarray(row_ptr, dtype=np.uint32)
+        ids = np.ascontiguousarray(route_ids, dtype=np.uint32)
+        pf, gf = self._caps_table(caps)
+        rc_arr = None if row_caps is None else np.ascontiguousarray(row_caps, dtype=np.uint32)
+        n = len(row) - 1
+        if rc_arr is not None and len(rc_arr) != n:
+            raise ValueError("row_caps: one entry per row")
+        if events_cap is None:
+            events_cap = len(ids)
+        if out_cap is None:
+            out_cap = len(ids)
+        o_row, o_ids = np.zeros(n + 1, dtype=np.uint32), np.zeros(max(1, out_cap), dtype=np.uint32)
+        cls, ev = np.zeros((max(n, 1), 2), dtype=np.uint32), np.zeros((max(1, events_cap), 4), dtype=np.int32)
+        nev, info = C.c_uint32(), _lib.CapsInfo()
+        rc = _lib.lib().bmq_routes_cap_batch(self.h, _ptr(row), _ptr(ids), n, _ptr(rc_arr), _ptr(pf), _ptr(gf), len(pf), _ptr(o_row), _ptr(o_ids), out_cap,
+                                             _ptr(cls), _ptr(ev), events_cap, C.byref(nev), C.byref(info))
+        if rc:
+            raise self._caps_error(rc, info, nev.value)
+        return o_row, o_ids[:info.n_kept], cls[:n], ev[:min(nev.value, events_cap)], info
+
+    def routes_cap_device(self, d_row_ptr, d_ids, n_rows, total, d_row_caps, d_max_pf, d_max_gf, n_caps, d_out_row_ptr, d_out_ids, out_cap, d_out_class_counts,
+                          d_out_events, events_cap):
+        """bmq_routes_cap_dev: all d_* are device pointers (ints; d_row_caps, d_out_class_counts, d_out_events may be None) -> (n_events, CapsInfo);
+        BmqError -3 (.info.n_kept ids are needed) if out_cap is too small."""
+        nev, info = C.c_uint32(), _lib.CapsInfo()
+        rc = _lib.lib().bmq_routes_cap_dev(self.h, d_row_ptr, d_ids, n_rows, total, d_row_caps, d_max_pf, d_max_gf, n_caps, d_out_row_ptr, d_out_ids, out_cap,
+                                           d_out_class_counts, d_out_events, events_cap, C.byref(nev), C.byref(info))
+        if rc:
+            raise self._caps_error(rc, info, nev.value)
+        return nev.value, info
+
+    def match_wait_delivery_capped(self, ticket: int, caps, sender_off, sender_hash, nonce: int, out_topic: np.ndarray, out_route: np.ndarray,
+                                   out_aux: np.ndarray, share_sender: np.ndarray, share_member: np.ndarray, group_off: np.ndarray, events_cap: int = 4096):
+        """The wait of a FMT_DELIVERY ticket with the caps applied between the match and the plan; caps: one (pf, gf) per tenant of the batch
+        -> (total ids of the uncapped CSR, DeliveryInfo, events [n, 4] int32, CapsInfo).  BmqError -3 as match_wait_delivery; it carries
+        .events and .caps_info too."""
+        so = np.ascontiguousarray(sender_off, dtype=np.uint32)
+        sh = np.ascontiguousarray(sender_hash, dtype=np.int32)
+        pf, gf = self._caps_table(caps)
+        info, tot, nev, cinfo = _lib.DeliveryInfo(), C.c_uint64(), C.c_uint32(), _lib.CapsInfo()
+        ev = np.zeros((max(1, events_cap), 4), dtype=np.int32)
+        rc = _lib.lib().bmq_delivery_wait_capped(self.h, ticket, _ptr(pf), _ptr(gf), len(pf), _ptr(so), _ptr(sh), nonce & 0xFFFFFFFFFFFFFFFF, _ptr(out_topic),
+                                                 _ptr(out_route), _ptr(out_aux), min(len(out_topic), len(out_route), len(out_aux)), _ptr(share_sender),
+                                                 _ptr(share_member), min(len(share_sender), len(share_member)), _ptr(group_off), len(group_off) - 1,
+                                                 C.byref(info), C.byref(tot), _ptr(ev), events_cap, C.byref(nev), C.byref(cinfo))
+        events = ev[:min(nev.value, events_cap)]
+        if rc:
+            err = self._delivery_error(rc, info)
+            err.events, err.caps_info = events, cinfo
+            raise err
+        return tot.value, info, events, cinfo
+
     def finish(self) -> int:
         total = C.c_uint64()
         self._check(_lib.lib().bmq_match_finish(self.h, C.byref(total)))

@@ -882,6 +882,53 @@ int bmq_delivery_wait(bmq_engine* e, int ticket, const uint32_t* sender_off, con
                             uint32_t* out_route, uint32_t* out_aux, uint32_t row_cap, uint32_t* out_share_sender, uint32_t* out_share_member,
                             uint32_t share_cap, uint32_t* out_group_off, uint32_t group_cap, bmq_delivery_info* out_info, uint64_t* out_total);
 
+/* ---- the fan-out caps of MatchedRoutes over a whole match batch ------------------------------------------------------------- */
+/* bmq_routes_cap for a CSR whose rows carry caps of their own, answered where the CSR lies.  DistWorkerCoProc.batchDist never sees an
+ * uncapped match: every topic's routes come out of a MatchedRoutes (DW/cache/MatchedRoutes.java:87-141) under its tenant's
+ * MaxPersistentFanout / MaxGroupFanout.
+ *   in : row_ptr[n_rows + 1], route_ids[row_ptr[n_rows]]: what bmq_match_batch* returned (rows ascending by id, no repeats);
+ *        the caps table max_persistent_fanout[n_caps] / max_group_fanout[n_caps] (one entry per tenant, say) and row_caps[n_rows], the
+ *        table entry of every row (NULL: every row takes entry 0).  A negative cap or an index >= n_caps: BMQ_E_INVAL, nothing is written.
+ *   out: for row r with caps (pf, gf) exactly what bmq_routes_cap(e, row r, pf, gf) gives: a row no longer than min(pf, gf) is copied
+ *        through (dead ids and all; out_class_counts[2 r], [2 r + 1] == 0xFFFFFFFF); in every other row dead ids are dropped and a class
+ *        with more members than its cap keeps the members with the smallest KEYS (unsigned bytes, a proper prefix first), in the input's
+ *        order; out_class_counts (may be NULL) = the persistent / group routes kept.
+ *   events (out_events may be NULL): 4 int32 each {type 0 = PersistentFanoutThrottled 1 = GroupFanoutThrottled, row, rejected route id,
+ *        max count}.  Rows ascend; inside a row the persistent events come first, in key order, then the group events, in key order (the
+ *        two classes are not interleaved as bmq_routes_cap interleaves them).  *out_n_events counts all of them, also those behind events_cap.
+ *   out_info: n_in / n_kept: ids in / out; n_rows_classified: rows longer than a cap; n_rows_ranked: rows with a class over its cap,
+ *        ordered by key on the device; n_rows_fallback: such rows with a class of more than 4096 members, whose keys were sorted on the
+ *        host instead; n_events; generation: of the route index the ids belong to; ms_*: HIP-event times of the three passes while
+ *        bmq_set_kernel_timing is on, else 0.
+ *   BMQ_E_NOSPACE: out_cap < out_info->n_kept; the events and out_info are valid, the rows are not.
+ * Read-only: nothing is written to the index, nothing is cached per route.  Works on a host-only engine too (the same per-item functions
+ * on host threads).
+ * _dev: every array is a device pointer (the CSR may be what bmq_match_submit_dev left in HBM), total = d_row_ptr[n_rows]; runs on the
+ *   engine stream and returns when the rows are complete.  Needs a device.
+ * bmq_delivery_wait_capped: bmq_delivery_wait with the caps applied in between -- the CSR the batch left in the slot is capped with row_caps =
+ *   the batch's topic_tenant and the plan is made of the capped CSR, neither leaving the GPU.  n_caps must be the batch's tenant count
+ *   (else BMQ_E_INVAL, and the ticket stays in flight); the caps are host arrays.  *out_total = the ids of the UNCAPPED CSR.  BMQ_E_NOSPACE
+ *   as bmq_delivery_wait reports it; the events and out_caps_info are valid then too. */
+typedef struct bmq_caps_info {
+    uint64_t n_in, n_kept;
+    uint32_t n_rows_classified, n_rows_ranked, n_rows_fallback, n_events;
+    uint64_t generation;
+    float ms_classify, ms_rank, ms_write;
+} bmq_caps_info;
+int bmq_routes_cap_batch(bmq_engine* e, const uint32_t* row_ptr, const uint32_t* route_ids, uint32_t n_rows, const uint32_t* row_caps,
+                         const int32_t* max_persistent_fanout, const int32_t* max_group_fanout, uint32_t n_caps, uint32_t* out_row_ptr,
+                         uint32_t* out_route_ids, uint64_t out_cap, uint32_t* out_class_counts, int32_t* out_events, uint32_t events_cap,
+                         uint32_t* out_n_events, bmq_caps_info* out_info);
+int bmq_routes_cap_dev(bmq_engine* e, const uint32_t* d_row_ptr, const uint32_t* d_route_ids, uint32_t n_rows, uint64_t total,
+                       const uint32_t* d_row_caps, const int32_t* d_max_persistent_fanout, const int32_t* d_max_group_fanout, uint32_t n_caps,
+                       uint32_t* d_out_row_ptr, uint32_t* d_out_route_ids, uint64_t out_cap, uint32_t* d_out_class_counts, int32_t* d_out_events,
+                       uint32_t events_cap, uint32_t* out_n_events, bmq_caps_info* out_info);
+int bmq_delivery_wait_capped(bmq_engine* e, int ticket, const int32_t* max_persistent_fanout, const int32_t* max_group_fanout, uint32_t n_caps,
+                             const uint32_t* sender_off, const int32_t* sender_hash, uint64_t nonce, uint32_t* out_topic, uint32_t* out_route,
+                             uint32_t* out_aux, uint32_t row_cap, uint32_t* out_share_sender, uint32_t* out_share_member, uint32_t share_cap,
+                             uint32_t* out_group_off, uint32_t group_cap, bmq_delivery_info* out_info, uint64_t* out_total, int32_t* out_events,
+                             uint32_t events_cap, uint32_t* out_n_events, bmq_caps_info* out_caps_info);
+
 /* ---- dist-server side range pruning ---------------------------------------------------------------------- */
 /* TenantRangeLookupCache.lookup (bifromq-dist/bifromq-dist-server/src/main/java/org/apache/bifromq/dist/server/scheduler/
  * TenantRangeLookupCache.java:62-109) for a batch of topics of ONE tenant against the tenant's candidate KV ranges in boundary
