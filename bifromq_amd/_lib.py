@@ -28,7 +28,7 @@ ABI_SYMBOLS = [
     "bmq_batcher_match_all", "bmq_batcher_submit", "bmq_batcher_stats_get", "bmq_poller_stats_get", "bmq_poller_control",
     "bmq_route_cache_create", "bmq_route_cache_destroy", "bmq_route_cache_get", "bmq_route_cache_get_async", "bmq_route_cache_get_batch", "bmq_batcher_match_batch", "bmq_route_cache_is_cached", "bmq_route_cache_apply",
     "bmq_route_cache_rebuild", "bmq_route_cache_reset", "bmq_route_cache_expire", "bmq_route_cache_stats_get", "bmq_route_cache_tenant_stats_get",
-    "bmq_route_cache_set_caps", "bmq_route_cache_set_event_sink", "bmq_routes_cap", "bmq_fanout_group", "bmq_fanout_group_dev", "bmq_fanout_info_get", "bmq_share_members_apply", "bmq_share_resolve", "bmq_share_resolve_dev", "bmq_share_member", "bmq_share_info_get", "bmq_share_carry_info_get", "bmq_delivery_plan", "bmq_delivery_plan_dev", "bmq_delivery_wait", "bmq_routes_cap_batch", "bmq_routes_cap_dev", "bmq_delivery_wait_capped", "bmq_routes_find", "bmq_routes_window", "bmq_routes_gc_sweep", "bmq_routes_window_info_get", "bmq_routes_prefix_census", "bmq_routes_prefix_census_info_get", "bmq_router_find_by_key", "bmq_router_find_by_boundary", "bmq_retain_range_lookup", "bmq_router_create", "bmq_router_destroy", "bmq_router_lookup_key", "bmq_router_lookup_boundary", "bmq_router_retain_lookup",
+    "bmq_route_cache_set_caps", "bmq_route_cache_set_event_sink", "bmq_routes_cap", "bmq_fanout_group", "bmq_fanout_group_dev", "bmq_fanout_info_get", "bmq_share_members_apply", "bmq_share_resolve", "bmq_share_resolve_dev", "bmq_share_member", "bmq_share_info_get", "bmq_share_carry_info_get", "bmq_delivery_plan", "bmq_delivery_plan_dev", "bmq_delivery_wait", "bmq_routes_cap_batch", "bmq_routes_cap_dev", "bmq_delivery_wait_capped", "bmq_routes_gate_batch", "bmq_routes_gate_dev", "bmq_delivery_wait_gated", "bmq_routes_find", "bmq_routes_window", "bmq_routes_gc_sweep", "bmq_routes_window_info_get", "bmq_routes_prefix_census", "bmq_routes_prefix_census_info_get", "bmq_router_find_by_key", "bmq_router_find_by_boundary", "bmq_retain_range_lookup", "bmq_router_create", "bmq_router_destroy", "bmq_router_lookup_key", "bmq_router_lookup_boundary", "bmq_router_retain_lookup",
 ]
 
 
@@ -130,6 +130,12 @@ class CapsInfo(C.Structure):
     _fields_ = [("n_in", C.c_uint64), ("n_kept", C.c_uint64), ("n_rows_classified", C.c_uint32), ("n_rows_ranked", C.c_uint32),
                 ("n_rows_fallback", C.c_uint32), ("n_events", C.c_uint32), ("generation", C.c_uint64), ("ms_classify", C.c_float),
                 ("ms_rank", C.c_float), ("ms_write", C.c_float)]
+
+
+class GateInfo(C.Structure):
+    _fields_ = [("n_in", C.c_uint64), ("n_kept", C.c_uint64), ("n_rows_single", C.c_uint32), ("n_rows_gated", C.c_uint32),
+                ("n_rows_flagged", C.c_uint32), ("n_rows_ranked", C.c_uint32), ("n_rows_fallback", C.c_uint32), ("generation", C.c_uint64),
+                ("ms_classify", C.c_float), ("ms_rank", C.c_float), ("ms_write", C.c_float)]
 
 
 class GcSweepReply(C.Structure):
@@ -298,6 +304,10 @@ def lib() -> C.CDLL:
             "bmq_routes_cap_dev": (C.c_int, [vp, vp, vp, u32, u64, vp, vp, vp, u32, vp, vp, u64, vp, vp, u32, P(u32), P(CapsInfo)]),
             "bmq_delivery_wait_capped": (C.c_int, [vp, C.c_int, vp, vp, u32, vp, vp, u64, vp, vp, vp, u32, vp, vp, u32, vp, u32, P(DeliveryInfo), P(u64), vp, u32,
                                                    P(u32), P(CapsInfo)]),
+            "bmq_routes_gate_batch": (C.c_int, [vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, u64, vp, vp, vp, vp, P(GateInfo)]),
+            "bmq_routes_gate_dev": (C.c_int, [vp, vp, vp, u32, u64, vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, u64, vp, vp, vp, vp, P(GateInfo)]),
+            "bmq_delivery_wait_gated": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, u32, vp, u32, vp, vp, u64, vp, vp, vp, u32, vp, vp, u32, vp, u32, P(DeliveryInfo), P(u64),
+                                                  vp, u32, P(u32), P(CapsInfo), vp, vp, vp, P(GateInfo)]),
             "bmq_routes_find": (C.c_int, [vp, vp, vp, u32, vp]),
             "bmq_routes_window": (C.c_int, [vp, C.c_char_p, u32, u32, u32, vp, P(u32), P(u32)]),
             "bmq_routes_gc_sweep": (C.c_int, [vp, C.c_char_p, u32, u32, u32, vp, u32, P(GcSweepReply)]),

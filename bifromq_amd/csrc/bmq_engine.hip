@@ -26,6 +26,7 @@
 #include "bmq_codec.h"
 #include "bmq_dist_index.h"
 #include "bmq_caps.h"
+#include "bmq_gate.h"
 #include "bmq_delivery.h"
 #include "bmq_dist_kernels.h"
 #include "bmq_poll_kernel.h"
@@ -248,6 +249,10 @@ struct bmq_engine {
     std::unique_ptr<Caps<DevExec>> dcp;
     std::unique_ptr<Caps<HostExec>> hcp;
     DevBuf caps_buf; // staging of bmq_routes_cap_batch; the capped CSR and the events of bmq_delivery_wait_capped
+    // the submit-time fan-out gate over a match CSR (bmq_gate.h): scratch of the three passes, created by the first call
+    std::unique_ptr<Gate<DevExec>> dgt;
+    std::unique_ptr<Gate<HostExec>> hgt;
+    DevBuf gate_buf; // staging of bmq_routes_gate_batch; the table, the gated CSR, the flags and the meters of bmq_delivery_wait_gated
     // multi-GPU exchange inside the library (bmq_exchange.inc): RCCL communicator of this rank, its own stream
     void* comm = nullptr;
     int comm_world = 0, comm_rank = 0;
@@ -1146,6 +1151,7 @@ void bmq_engine_destroy(bmq_engine* e) {
         if (e->ev_lend) (void)hipEventDestroy(e->ev_lend);
         if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
         if (e->ev_join) (void)hipEventDestroy(e->ev_join);
+        e->dgt.reset();
         e->dcp.reset();
         e->ddl.reset();
         e->dfo.reset();
@@ -1157,6 +1163,7 @@ void bmq_engine_destroy(bmq_engine* e) {
         e->dx.tmp = nullptr;
         if (e->stream) (void)hipStreamDestroy(e->stream);
     }
+    e->hgt.reset();
     e->hcp.reset();
     e->hdl.reset();
     e->hfo.reset(); // (before the index it refers to)
@@ -2274,3 +2281,4 @@ int32_t bmq_java_string_hash(const uint8_t* utf8, uint32_t len) { return java_st
 #include "bmq_order_engine.inc"
 #include "bmq_prefix_engine.inc"
 #include "bmq_caps_engine.inc"
+#include "bmq_gate_engine.inc"

@@ -20,6 +20,7 @@
 #include "bmq_order_kernels.h"
 #include "bmq_prefix_kernels.h"
 #include "bmq_caps_kernels.h"
+#include "bmq_gate_kernels.h"
 #include "bmq_retain_build_kernels.h"
 #include "bmq_retain_core.h"
 #include "bmq_retain_snap_kernels.h"
@@ -586,7 +587,7 @@ struct DevExec {
     }
     // ---- optional HIP-event marks between the steps of a pipeline (bmq_set_kernel_timing) ----
     bool marks_on = false;
-    hipEvent_t marks[20] = {}; // 0 .. 7: the resolve and the carry of bmq_share.h, 8 .. 12: the delivery plan, 13 .. 16: the fan-out caps
+    hipEvent_t marks[24] = {}; // 0 .. 7: the resolve and the carry of bmq_share.h, 8 .. 12: the delivery plan, 13 .. 16: the fan-out caps, 17 .. 20: the fan-out gate
     void mark(int i) {
         if (!marks_on) return;
         if (!marks[i] && hipEventCreate(&marks[i]) != hipSuccess) return;
@@ -670,6 +671,33 @@ struct DevExec {
     bool caps_write(const CapsBatch& b) { // behind the inclusive scan of keep[]
         const uint32_t n = std::max(b.total, b.n_rows + 1);
         hipLaunchKernelGGL(k_caps_write, caps_grid(n), dim3(CAPS_BLOCK), 0, stream, b, n);
+        return launched();
+    }
+    // ---- the submit-time fan-out gate over a match CSR (bmq_gate.h; kernels: bmq_gate_kernels.h) ----
+    bool gate_classify(const DistIndexMut& ix, const GateBatch& b) { // row_cnt[], ctr[] and the meters are zeroed before
+        if (b.c.total == 0) return true;
+        hipLaunchKernelGGL(k_gate_classify, caps_grid(b.c.total), dim3(CAPS_BLOCK), 0, stream, ix, b);
+        return launched();
+    }
+    bool gate_rows(const GateBatch& b) {
+        if (b.c.n_rows == 0) return true;
+        hipLaunchKernelGGL(k_gate_rows, caps_grid(b.c.n_rows), dim3(CAPS_BLOCK), 0, stream, b);
+        return launched();
+    }
+    bool gate_list(const GateBatch& b) {
+        if (b.c.total == 0) return true;
+        hipLaunchKernelGGL(k_gate_list, caps_grid(b.c.total), dim3(CAPS_BLOCK), 0, stream, b);
+        return launched();
+    }
+    bool gate_rank(const DistIndexMut& ix, const GateBatch& b, uint32_t n_work) {
+        if (n_work == 0) return true;
+        hipLaunchKernelGGL(k_gate_rank, grid(n_work, CAPS_BLOCK / 64), dim3(CAPS_BLOCK), 0, stream, ix, b, n_work);
+        return launched();
+    }
+    bool gate_write(const GateBatch& b, bool rows) { // behind the inclusive scan of keep[]; without `rows` only flags, kept counts and meters
+        const uint32_t n = std::max(rows ? std::max(b.c.total, b.c.n_rows + 1) : b.c.n_rows, b.n_gate);
+        if (n == 0) return true;
+        hipLaunchKernelGGL(k_gate_write, caps_grid(n), dim3(CAPS_BLOCK), 0, stream, b, n, rows ? 1u : 0u);
         return launched();
     }
     bool sh_rekey(uint32_t* slot_of, uint32_t id_cap, const uint32_t* new_id, const uint32_t* slot, uint32_t n) {

@@ -14,6 +14,7 @@
 
 #include "bmq_build_core.h"
 #include "bmq_caps_core.h"
+#include "bmq_gate_core.h"
 #include "bmq_delivery_core.h"
 #include "bmq_fanout_core.h"
 #include "bmq_order_core.h"
@@ -299,6 +300,57 @@ struct HostExec {
     }
     bool caps_write(const CapsBatch& b) { // behind the inclusive scan of keep[]
         par(std::max(b.total, b.n_rows + 1), [&](size_t i) { caps_write_one(b, (uint32_t)i); });
+        return true;
+    }
+    // ---- the submit-time fan-out gate over a match CSR (bmq_gate.h): the per-item functions of bmq_gate_core.h; a row's counters belong to one thread ----
+    bool gate_classify(const DistIndexMut& ix, const GateBatch& b) { // row_cnt[], ctr[] and the meters are zeroed before
+        std::atomic<uint32_t> err{0};
+        par(b.c.n_rows, [&](size_t r) {
+            uint32_t e = 0;
+            for (uint32_t i = b.c.row_ptr[r]; i < b.c.row_ptr[r + 1]; i++) {
+                const uint32_t c = gate_classify_one(ix, b, i, &e);
+                b.c.cls[i] = (uint8_t)c;
+                if (c != CAPS_DEAD) b.row_cnt[3 * r + gate_slot_of(c)]++;
+            }
+            if (e) err.fetch_or(e);
+        });
+        b.c.ctr[GATE_C_ERR] |= err.load();
+        return true;
+    }
+    bool gate_rows(const GateBatch& b) {
+        for (uint32_t r = 0; r < b.c.n_rows; r++) {
+            uint32_t t = 0, record = 0;
+            unsigned long long meter = 0;
+            const uint32_t full = gate_row_one(b, r, t, meter, record), m = full & 3u;
+            if (full & CAPS_BAD_INDEX) {
+                b.c.ctr[GATE_C_ERR] |= CAPS_ERR_INDEX;
+                continue;
+            }
+            const uint64_t n = (uint64_t)b.row_cnt[3 * (size_t)r] + b.row_cnt[3 * (size_t)r + 1] + b.row_cnt[3 * (size_t)r + 2];
+            b.c.ctr[GATE_C_SINGLE] += n == 1;
+            b.c.ctr[GATE_C_GATED] += n > 1;
+            b.c.ctr[GATE_C_FLAGGED] += (b.flags[r] & ~(uint32_t)GATE_INLINE) != 0;
+            b.c.ctr[GATE_C_RANKED] += m == CAPS_ROW_RANKED;
+            if (m == CAPS_ROW_FALLBACK) b.c.fb_rows[b.c.ctr[GATE_C_FALLBACK]++] = r;
+            if (record) b.meter_bytes[t] += meter, b.meter_records[t] += record;
+        }
+        return true;
+    }
+    bool gate_list(const GateBatch& b) {
+        for (uint32_t r = 0; r < b.c.n_rows; r++)
+            for (uint32_t i = b.c.row_ptr[r]; i < b.c.row_ptr[r + 1]; i++)
+                if (gate_list_one(b, i, r)) b.c.work[b.c.ctr[GATE_C_WORK]++] = i;
+        return true;
+    }
+    bool gate_rank(const DistIndexMut& ix, const GateBatch& b, uint32_t n_work) {
+        par(n_work, [&](size_t item) {
+            const uint32_t p = b.c.work[item], r = fo_row_of(b.c.row_ptr, b.c.n_rows, p);
+            gate_settle_one(b, p, r, caps_rank_one(ix, b.c, p, r));
+        });
+        return true;
+    }
+    bool gate_write(const GateBatch& b, bool rows) { // behind the inclusive scan of keep[]
+        par(std::max(rows ? std::max(b.c.total, b.c.n_rows + 1) : b.c.n_rows, b.n_gate), [&](size_t i) { gate_write_one(b, (uint32_t)i, rows); });
         return true;
     }
     void mark(int) {} // (HIP-event marks of the device executor)

@@ -853,6 +853,96 @@ class Engine:
             raise err
         return tot.value, info, events, cinfo
 
+    # ---- the submit-time fan-out gate of DeliverExecutorGroup.submit over a whole match batch (DW/DeliverExecutorGroup.java:112-231) --
+    GATE_INLINE, GATE_P_COUNT, GATE_P_BYTES, GATE_NO_P_BANDWIDTH, GATE_NO_T_BANDWIDTH, GATE_GROUP = 1, 2, 4, 8, 16, 32
+
+    @staticmethod
+    def _gate_table(table):
+        """(pf, gf, pb, bw) or [(pf, gf, pb, bw), ...] -> (max_pf, max_gf int32, max_pb int64, bandwidth uint8); what does not fit its
+        type is the caller's error"""
+        rows = [tuple(int(v) for v in table)] if len(table) and not hasattr(table[0], "__len__") else [tuple(int(v) for v in t) for t in table]
+        if any(len(t) != 4 for t in rows):
+            raise ValueError("a gate table entry is (max_persistent_fanout, max_group_fanout, max_persistent_fanout_bytes, bandwidth)")
+        for pf, gf, pb, bw in rows:
+            if not (-2**31 <= pf < 2**31 and -2**31 <= gf < 2**31 and -2**63 <= pb < 2**63 and 0 <= bw < 256):
+                raise ValueError("a gate table value outside its type")
+        col = lambda k, dt: np.array([t[k] for t in rows], dtype=dt)
+        return col(0, np.int32), col(1, np.int32), col(2, np.int64), col(3, np.uint8)
+
+    def _gate_error(self, rc: int, info: "_lib.GateInfo") -> BmqError:
+        err = BmqError(rc, (_lib.lib().bmq_last_error(self.h) or b"").decode())
+        err.info = info
+        return err
+
+    def routes_gate_batch(self, row_ptr, route_ids, pack_bytes, table, row_gate=None, inline_threshold: int = 0, out_cap: Optional[int] = None):
+        """bmq_routes_gate_batch: the gate of DeliverExecutorGroup.submit over a match CSR, every row under the table entry row_gate names
+        (None: entry 0); table = (pf, gf, pb, bw) or a list of such entries -> (row_ptr, ids, flags [n_rows], class_counts [n_rows, 3]
+        persistent / transient / group kept, meter_bytes [n_gate] uint64, meter_records [n_gate], info).  A BmqError -3 carries .info,
+        .flags, .class_counts, .meter_bytes and .meter_records."""
+        row = np.ascontiguousarray(row_ptr, dtype=np.uint32)
+        ids = np.ascontiguousarray(route_ids, dtype=np.uint32)
+        pk = np.ascontiguousarray(pack_bytes, dtype=np.uint32)
+        pf, gf, pb, bw = self._gate_table(table)
+        rg = None if row_gate is None else np.ascontiguousarray(row_gate, dtype=np.uint32)
+        n = len(row) - 1
+        if len(pk) != n or (rg is not None and len(rg) != n):
+            raise ValueError("pack_bytes / row_gate: one entry per row")
+        if out_cap is None:
+            out_cap = len(ids)
+        o_row, o_ids = np.zeros(n + 1, dtype=np.uint32), np.zeros(max(1, out_cap), dtype=np.uint32)
+        fl, cc = np.zeros(max(n, 1), dtype=np.uint32), np.zeros((max(n, 1), 3), dtype=np.uint32)
+        mb, mr = np.zeros(max(len(pf), 1), dtype=np.uint64), np.zeros(max(len(pf), 1), dtype=np.uint32)
+        info = _lib.GateInfo()
+        rc = _lib.lib().bmq_routes_gate_batch(self.h, _ptr(row), _ptr(ids), n, _ptr(pk), _ptr(rg), _ptr(pf), _ptr(gf), _ptr(pb), _ptr(bw), len(pf), inline_threshold,
+                                              _ptr(o_row), _ptr(o_ids), out_cap, _ptr(fl), _ptr(cc), _ptr(mb), _ptr(mr), C.byref(info))
+        if rc:
+            err = self._gate_error(rc, info)
+            err.flags, err.class_counts, err.meter_bytes, err.meter_records = fl[:n], cc[:n], mb[:len(pf)], mr[:len(pf)]
+            raise err
+        return o_row, o_ids[:info.n_kept], fl[:n], cc[:n], mb[:len(pf)], mr[:len(pf)], info
+
+    def routes_gate_device(self, d_row_ptr, d_ids, n_rows, total, d_pack_bytes, d_row_gate, d_max_pf, d_max_gf, d_max_pb, d_bandwidth, n_gate, inline_threshold,
+                           d_out_row_ptr, d_out_ids, out_cap, d_out_flags, d_out_class_counts, d_out_meter_bytes, d_out_meter_records):
+        """bmq_routes_gate_dev: all d_* are device pointers (ints; d_row_gate and d_out_class_counts may be None) -> GateInfo; BmqError -3
+        (.info.n_kept ids are needed) if out_cap is too small."""
+        info = _lib.GateInfo()
+        rc = _lib.lib().bmq_routes_gate_dev(self.h, d_row_ptr, d_ids, n_rows, total, d_pack_bytes, d_row_gate, d_max_pf, d_max_gf, d_max_pb, d_bandwidth, n_gate,
+                                            inline_threshold, d_out_row_ptr, d_out_ids, out_cap, d_out_flags, d_out_class_counts, d_out_meter_bytes, d_out_meter_records,
+                                            C.byref(info))
+        if rc:
+            raise self._gate_error(rc, info)
+        return info
+
+    def match_wait_delivery_gated(self, ticket: int, table, pack_bytes, inline_threshold: int, sender_off, sender_hash, nonce: int, out_topic: np.ndarray,
+                                  out_route: np.ndarray, out_aux: np.ndarray, share_sender: np.ndarray, share_member: np.ndarray, group_off: np.ndarray,
+                                  events_cap: int = 4096):
+        """The wait of a FMT_DELIVERY ticket with the caps and then the gate applied between the match and the plan; table: one
+        (pf, gf, pb, bw) per tenant of the batch, pack_bytes: one per topic -> (total ids of the unthrottled CSR, DeliveryInfo, the caps'
+        events [n, 4] int32, CapsInfo, flags [n_topics], meter_bytes [n_tenants], meter_records [n_tenants], GateInfo).  BmqError -3 as
+        match_wait_delivery; it carries .events, .caps_info, .flags, .meter_bytes, .meter_records and .gate_info too."""
+        so = np.ascontiguousarray(sender_off, dtype=np.uint32)
+        sh = np.ascontiguousarray(sender_hash, dtype=np.int32)
+        pk = np.ascontiguousarray(pack_bytes, dtype=np.uint32)
+        if len(pk) != len(so) - 1:
+            raise ValueError("pack_bytes: one entry per topic")
+        pf, gf, pb, bw = self._gate_table(table)
+        info, tot, nev, cinfo, ginfo = _lib.DeliveryInfo(), C.c_uint64(), C.c_uint32(), _lib.CapsInfo(), _lib.GateInfo()
+        ev = np.zeros((max(1, events_cap), 4), dtype=np.int32)
+        fl = np.zeros(max(len(pk), 1), dtype=np.uint32)
+        mb, mr = np.zeros(max(len(pf), 1), dtype=np.uint64), np.zeros(max(len(pf), 1), dtype=np.uint32)
+        rc = _lib.lib().bmq_delivery_wait_gated(self.h, ticket, _ptr(pf), _ptr(gf), _ptr(pb), _ptr(bw), len(pf), _ptr(pk), inline_threshold, _ptr(so), _ptr(sh),
+                                                nonce & 0xFFFFFFFFFFFFFFFF, _ptr(out_topic), _ptr(out_route), _ptr(out_aux),
+                                                min(len(out_topic), len(out_route), len(out_aux)), _ptr(share_sender), _ptr(share_member),
+                                                min(len(share_sender), len(share_member)), _ptr(group_off), len(group_off) - 1, C.byref(info), C.byref(tot), _ptr(ev),
+                                                events_cap, C.byref(nev), C.byref(cinfo), _ptr(fl), _ptr(mb), _ptr(mr), C.byref(ginfo))
+        events = ev[:min(nev.value, events_cap)]
+        if rc:
+            err = self._delivery_error(rc, info)
+            err.events, err.caps_info, err.gate_info = events, cinfo, ginfo
+            err.flags, err.meter_bytes, err.meter_records = fl[:len(pk)], mb[:len(pf)], mr[:len(pf)]
+            raise err
+        return tot.value, info, events, cinfo, fl[:len(pk)], mb[:len(pf)], mr[:len(pf)], ginfo
+
     def finish(self) -> int:
         total = C.c_uint64()
         self._check(_lib.lib().bmq_match_finish(self.h, C.byref(total)))

@@ -929,6 +929,78 @@ int bmq_delivery_wait_capped(bmq_engine* e, int ticket, const int32_t* max_persi
                              uint32_t* out_group_off, uint32_t group_cap, bmq_delivery_info* out_info, uint64_t* out_total, int32_t* out_events,
                              uint32_t events_cap, uint32_t* out_n_events, bmq_caps_info* out_caps_info);
 
+/* ---- the submit-time fan-out gate of DeliverExecutorGroup.submit over a whole match batch ----------------------------------------- */
+/* What DeliverExecutorGroup.submit (DW/DeliverExecutorGroup.java:112-231) does to every message pack before it calls send, for a whole
+ * CSR, answered where the CSR lies.  submit re-reads MaxPersistentFanout / MaxGroupFanout and reads MaxPersistentFanoutBytes
+ * (Setting.java:62) (:131-133), asks the resource throttler for transient and persistent fan-out bandwidth (:135-139), admits persistent
+ * routes while count < maxCount && bytes < maxBytes, every admitted route adding the pack's estimated size (:152-156), drops every
+ * transient route of a tenant without bandwidth (:190-202), admits groups up to MaxGroupFanout (:206-208), reports ONE event per kind and
+ * pack (:158-186, :193-201, :210-218), meters MqttPersistentFanOutBytes (:122, :229), decides `inline` from routes.size() <
+ * inlineFanOutThreshold (:134) and bypasses all of it for a pack of exactly one route (:115-129).  `routes` is a concurrent hash set
+ * (DW/cache/MatchedRoutes.java:42), so WHICH routes fill the admitted places is unspecified there; the counts, the flags and the metered
+ * bytes depend only on how many routes of each class the row has.  This engine keeps the members with the smallest KEYS (unsigned bytes,
+ * a proper prefix first), in the input's order, as the caps do.  The break at :225 loses nothing: a class throttled once stays throttled.
+ *   in : row_ptr[n_rows + 1], route_ids[row_ptr[n_rows]] (rows ascending by id, no repeats); pack_bytes[n_rows] = SizeUtil.estSizeOf(msgPack);
+ *        the gate table of n_gate entries (one per tenant, say): max_persistent_fanout, max_group_fanout (int32),
+ *        max_persistent_fanout_bytes (int64), bandwidth (uint8: bit 0 = the tenant has transient fan-out bandwidth, bit 1 = persistent);
+ *        row_gate[n_rows], the table entry of every row (NULL: every row takes entry 0); inline_threshold, one per call.  A negative limit,
+ *        a bandwidth above 3 or an index >= n_gate: BMQ_E_INVAL, nothing is written.
+ *   per row, with n live routes of which nP persistent, nT transient, nG groups (dead ids always leave the row), s = pack_bytes[r]:
+ *        n == 0: nothing is kept, flags 0, no meter record.  n == 1: the route is kept whatever the table says, flags = BMQ_GATE_INLINE; a
+ *        persistent route meters s bytes and one record.  n > 1: BMQ_GATE_INLINE iff n < inline_threshold; with A = min(pf, ceil(pb / s))
+ *        (pb == 0: 0; s == 0: pf) and persistent bandwidth min(nP, A) persistent routes are kept and, if nP > A, BMQ_GATE_P_COUNT iff A >= pf,
+ *        BMQ_GATE_P_BYTES iff A * s >= pb (64 bits; both can be set); without persistent bandwidth none is kept and, if nP > 0,
+ *        BMQ_GATE_NO_P_BANDWIDTH when pf > 0 && pb > 0, else P_COUNT iff pf == 0 and P_BYTES iff pb == 0; the transient routes are all kept
+ *        with transient bandwidth, else none and BMQ_GATE_NO_T_BANDWIDTH iff nT > 0; min(nG, gf) groups are kept, BMQ_GATE_GROUP iff nG > gf;
+ *        the meter of the row's entry takes kept persistent routes * s bytes and one record (also when the bytes are 0).
+ *   out: the gated CSR out_row_ptr[n_rows + 1] / out_route_ids; out_row_flags[n_rows]: BMQ_GATE_* bits, one event kind each (P_COUNT =
+ *        PersistentFanoutThrottled, P_BYTES = PersistentFanoutBytesThrottled, NO_P_BANDWIDTH / NO_T_BANDWIDTH = OutOfTenantResource with
+ *        reason TotalPersistentFanOutBytesPerSeconds / TotalTransientFanOutBytesPerSeconds -- the adapter reports it once per publisher of
+ *        the pack --, GROUP = GroupFanoutThrottled); out_class_counts[3 n_rows] (may be NULL): persistent, transient, group routes kept;
+ *        out_meter_bytes[n_gate] (uint64) / out_meter_records[n_gate]: MqttPersistentFanOutBytes per table entry, zeroed by the call.
+ *   out_info: n_in / n_kept: ids in / out; n_rows_single: rows of one live route; n_rows_gated: rows of more; n_rows_flagged: rows with any
+ *        bit but INLINE; n_rows_ranked: rows with a class of which some but not all members stay, ordered by key on the device;
+ *        n_rows_fallback: such rows with a class of more than 4096 members, whose keys were sorted on the host instead; generation: of the
+ *        route index the ids belong to; ms_*: HIP-event times of the three passes while bmq_set_kernel_timing is on, else 0.
+ *   BMQ_E_NOSPACE: out_cap < out_info->n_kept; flags, class counts, meters and out_info are valid, the rows are not.
+ * Read-only: nothing is written to the index.  Locks and state are those of bmq_routes_cap_batch.  Works on a host-only engine too.
+ * _dev: every array is a device pointer, total = d_row_ptr[n_rows]; runs on the engine stream and returns when the rows are complete.
+ * bmq_delivery_wait_gated: bmq_delivery_wait_capped with the gate applied between the caps and the plan -- caps, gate and plan run on the
+ *   slot's CSR without it leaving the GPU.  The same max_persistent_fanout / max_group_fanout serve the caps (per-route events, as
+ *   bmq_delivery_wait_capped reports them) and the gate; row_gate is the batch's topic_tenant, n_gate must be its tenant count (else
+ *   BMQ_E_INVAL, and the ticket stays in flight); pack_bytes[n_topics].  out_row_flags[n_topics], out_meter_bytes / out_meter_records
+ *   [n_gate].  BMQ_E_STATE, BMQ_E_INVAL and BMQ_E_NOSPACE exactly as bmq_delivery_wait_capped; flags, meters and out_gate_info are valid
+ *   with BMQ_E_NOSPACE too. */
+#define BMQ_GATE_INLINE 1u
+#define BMQ_GATE_P_COUNT 2u
+#define BMQ_GATE_P_BYTES 4u
+#define BMQ_GATE_NO_P_BANDWIDTH 8u
+#define BMQ_GATE_NO_T_BANDWIDTH 16u
+#define BMQ_GATE_GROUP 32u
+typedef struct bmq_gate_info {
+    uint64_t n_in, n_kept;
+    uint32_t n_rows_single, n_rows_gated, n_rows_flagged, n_rows_ranked, n_rows_fallback;
+    uint64_t generation;
+    float ms_classify, ms_rank, ms_write;
+} bmq_gate_info;
+int bmq_routes_gate_batch(bmq_engine* e, const uint32_t* row_ptr, const uint32_t* route_ids, uint32_t n_rows, const uint32_t* pack_bytes,
+                          const uint32_t* row_gate, const int32_t* max_persistent_fanout, const int32_t* max_group_fanout,
+                          const int64_t* max_persistent_fanout_bytes, const uint8_t* bandwidth, uint32_t n_gate, uint32_t inline_threshold,
+                          uint32_t* out_row_ptr, uint32_t* out_route_ids, uint64_t out_cap, uint32_t* out_row_flags, uint32_t* out_class_counts,
+                          uint64_t* out_meter_bytes, uint32_t* out_meter_records, bmq_gate_info* out_info);
+int bmq_routes_gate_dev(bmq_engine* e, const uint32_t* d_row_ptr, const uint32_t* d_route_ids, uint32_t n_rows, uint64_t total,
+                        const uint32_t* d_pack_bytes, const uint32_t* d_row_gate, const int32_t* d_max_persistent_fanout,
+                        const int32_t* d_max_group_fanout, const int64_t* d_max_persistent_fanout_bytes, const uint8_t* d_bandwidth, uint32_t n_gate,
+                        uint32_t inline_threshold, uint32_t* d_out_row_ptr, uint32_t* d_out_route_ids, uint64_t out_cap, uint32_t* d_out_row_flags,
+                        uint32_t* d_out_class_counts, uint64_t* d_out_meter_bytes, uint32_t* d_out_meter_records, bmq_gate_info* out_info);
+int bmq_delivery_wait_gated(bmq_engine* e, int ticket, const int32_t* max_persistent_fanout, const int32_t* max_group_fanout,
+                            const int64_t* max_persistent_fanout_bytes, const uint8_t* bandwidth, uint32_t n_gate, const uint32_t* pack_bytes,
+                            uint32_t inline_threshold, const uint32_t* sender_off, const int32_t* sender_hash, uint64_t nonce, uint32_t* out_topic,
+                            uint32_t* out_route, uint32_t* out_aux, uint32_t row_cap, uint32_t* out_share_sender, uint32_t* out_share_member,
+                            uint32_t share_cap, uint32_t* out_group_off, uint32_t group_cap, bmq_delivery_info* out_info, uint64_t* out_total,
+                            int32_t* out_events, uint32_t events_cap, uint32_t* out_n_events, bmq_caps_info* out_caps_info, uint32_t* out_row_flags,
+                            uint64_t* out_meter_bytes, uint32_t* out_meter_records, bmq_gate_info* out_gate_info);
+
 /* ---- dist-server side range pruning ---------------------------------------------------------------------- */
 /* TenantRangeLookupCache.lookup (bifromq-dist/bifromq-dist-server/src/main/java/org/apache/bifromq/dist/server/scheduler/
  * TenantRangeLookupCache.java:62-109) for a batch of topics of ONE tenant against the tenant's candidate KV ranges in boundary
