@@ -1,22 +1,7 @@
-// bmq_caps_engine.inc -- bmq_routes_cap_batch / bmq_routes_cap_dev / bmq_delivery_wait_capped: the fan-out caps of MatchedRoutes over a
-// whole match CSR (bmq_caps_core.h says what they replace in the reference).  Included at the end of bmq_engine.hip, behind
-// bmq_delivery_engine.inc (the capped wait hands its CSR to delivery_run).
+// bmq_caps_engine.inc -- bmq_routes_cap_batch / bmq_routes_cap_dev: the fan-out caps of MatchedRoutes over a whole match CSR
+// (bmq_caps_core.h says what they replace in the reference).  Included at the end of bmq_engine.hip; bmq_delivery_wait_capped
+// (bmq_delivery_engine.inc) runs caps_run in front of the plan.
 namespace {
-// the engine's Caps over whichever executor it has, created by the first call.  A buffer that grows is freed first, and a free waits for
-// every stream of the device: the persistent matcher leaves before.
-template <class F> int with_caps(bmq_engine* e, F&& f) {
-    if (e->device < 0) {
-        if (!e->hcp) e->hcp = std::make_unique<Caps<HostExec>>(e->hx);
-        return f(*e->hcp, *e->hix);
-    }
-    HIPCHK(e, hipSetDevice(e->device));
-    if (!e->dcp) {
-        e->dcp = std::make_unique<Caps<DevExec>>(e->dx);
-        e->dcp->before_free = [e] { poller_stop_locked(e); };
-    }
-    e->dx.marks_on = e->kernel_events;
-    return f(*e->dcp, *e->dix);
-}
 int caps_check_table(bmq_engine* e, const int32_t* max_pf, const int32_t* max_gf, uint32_t n_caps) {
     for (uint32_t t = 0; t < n_caps; t++)
         if (max_pf[t] < 0 || max_gf[t] < 0) return set_err(e, BMQ_E_INVAL, "negative fan-out cap");
@@ -26,7 +11,7 @@ int caps_check_table(bmq_engine* e, const int32_t* max_pf, const int32_t* max_gf
 int caps_run(bmq_engine* e, const uint32_t* row_ptr, const uint32_t* ids, uint32_t n_rows, uint32_t total, const uint32_t* row_caps, const int32_t* max_pf,
              const int32_t* max_gf, uint32_t n_caps, const int32_t* h_pf, const int32_t* h_gf, uint32_t* out_row_ptr, uint32_t* out_ids, uint64_t out_cap,
              uint32_t* out_class_counts, int32_t* out_events, uint32_t events_cap, CapsResult& r, bmq_caps_info* out_info) {
-    const int rc = with_caps(e, [&](auto& cp, auto& ix) {
+    const int rc = with_control(e, e->hcp, e->dcp, [&](auto& cp, auto& ix) {
         out_info->generation = ix.generation;
         return cp.run(ix, row_ptr, ids, n_rows, total, row_caps, max_pf, max_gf, n_caps, h_pf, h_gf, out_row_ptr, out_ids, out_cap, out_class_counts, out_events, events_cap, r)
                    ? (int)BMQ_OK
@@ -84,11 +69,8 @@ extern "C" int bmq_routes_cap_batch(bmq_engine* e, const uint32_t* row_ptr, cons
     if (!e || !out_info) return BMQ_E_INVAL;
     if (out_n_events) *out_n_events = 0;
     if (!row_ptr || !out_row_ptr || (n_caps && (!max_pf || !max_gf))) return set_err(e, BMQ_E_INVAL, "null pointer");
-    if (row_ptr[0] != 0) return set_err(e, BMQ_E_INVAL, "row_ptr[0] != 0");
-    for (uint32_t i = 0; i < n_rows; i++)
-        if (row_ptr[i + 1] < row_ptr[i]) return set_err(e, BMQ_E_INVAL, "row_ptr not ascending");
+    if (int rc_c = check_csr(e, row_ptr, n_rows, 0x3FFFFFF0u)) return rc_c;
     const uint32_t total = row_ptr[n_rows];
-    if (total >= 0x7FFFFFF0u || n_rows >= 0x3FFFFFF0u) return set_err(e, BMQ_E_RANGE, "more than 2^31 (topic, route) pairs in one batch");
     if (total && (!route_ids || !out_route_ids)) return set_err(e, BMQ_E_INVAL, "null pointer");
     if (int rc_t = caps_check_table(e, max_pf, max_gf, n_caps)) return rc_t;
     for (uint32_t i = 0; i < n_rows; i++)
@@ -108,116 +90,25 @@ extern "C" int bmq_routes_cap_batch(bmq_engine* e, const uint32_t* row_ptr, cons
     }
     HIPCHK(e, hipSetDevice(e->device));
     // staging: [row_ptr | ids | row_caps | max_pf | max_gf | out_row_ptr | out_ids | class counts | events]
-    size_t o = 0;
-    auto take = [&](size_t words) {
-        const size_t at = o;
-        o += (words * 4 + 15) & ~(size_t)15;
-        return at;
-    };
+    Stage st;
     const uint32_t ev_cap = out_events ? events_cap : 0u;
     const size_t ids_cap = (size_t)std::min<uint64_t>(out_cap, total);
-    const size_t o_row = take((size_t)n_rows + 1), o_ids = take(total), o_rc = take(row_caps ? n_rows : 0), o_pf = take(n_caps), o_gf = take(n_caps);
-    const size_t o_orow = take((size_t)n_rows + 1), o_oids = take(ids_cap), o_cc = take(out_class_counts ? 2 * (size_t)n_rows : 0), o_ev = take(4 * (size_t)ev_cap);
-    if (o + 16 > e->caps_buf.cap) poller_stop_locked(e);
-    HIPCHK(e, e->caps_buf.ensure(o + 16));
+    const size_t row_ptr4 = 4 * ((size_t)n_rows + 1), rc4 = row_caps ? 4 * (size_t)n_rows : 0, tab4 = 4 * (size_t)n_caps, cc8 = out_class_counts ? 8 * (size_t)n_rows : 0;
+    const size_t o_row = st.take(row_ptr4), o_ids = st.take(4 * (size_t)total), o_rc = st.take(rc4), o_pf = st.take(tab4), o_gf = st.take(tab4), o_orow = st.take(row_ptr4),
+                 o_oids = st.take(4 * ids_cap), o_cc = st.take(cc8), o_ev = st.take(16 * (size_t)ev_cap);
+    if (int rc_b = stage_ensure(e, e->caps_buf, st.end + 16)) return rc_b;
     uint8_t* d = e->caps_buf.as<uint8_t>();
-    hipStream_t s = e->stream;
-    HIPCHK(e, hipMemcpyAsync(d + o_row, row_ptr, 4 * ((size_t)n_rows + 1), hipMemcpyHostToDevice, s));
-    if (total) HIPCHK(e, hipMemcpyAsync(d + o_ids, route_ids, 4 * (size_t)total, hipMemcpyHostToDevice, s));
-    if (row_caps && n_rows) HIPCHK(e, hipMemcpyAsync(d + o_rc, row_caps, 4 * (size_t)n_rows, hipMemcpyHostToDevice, s));
-    if (n_caps) {
-        HIPCHK(e, hipMemcpyAsync(d + o_pf, max_pf, 4 * (size_t)n_caps, hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(d + o_gf, max_gf, 4 * (size_t)n_caps, hipMemcpyHostToDevice, s));
-    }
+    if (int rc_u = stage_up(e, {{d + o_row, row_ptr, row_ptr4}, {d + o_ids, route_ids, 4 * (size_t)total}, {d + o_rc, row_caps, rc4}, {d + o_pf, max_pf, tab4}, {d + o_gf, max_gf, tab4}}))
+        return rc_u;
     const int rc = caps_run(e, (const uint32_t*)(d + o_row), (const uint32_t*)(d + o_ids), n_rows, total, row_caps ? (const uint32_t*)(d + o_rc) : nullptr,
                             (const int32_t*)(d + o_pf), (const int32_t*)(d + o_gf), n_caps, max_pf, max_gf, (uint32_t*)(d + o_orow), (uint32_t*)(d + o_oids), ids_cap,
                             out_class_counts ? (uint32_t*)(d + o_cc) : nullptr, ev_cap ? (int32_t*)(d + o_ev) : nullptr, ev_cap, r, out_info);
     if (rc) return rc;
     if (out_n_events) *out_n_events = r.n_events;
-    const size_t n_ev = std::min<size_t>(r.n_events, ev_cap);
-    if (n_ev) HIPCHK(e, hipMemcpyAsync(out_events, d + o_ev, 16 * n_ev, hipMemcpyDeviceToHost, s));
-    if (!r.overflow) {
-        HIPCHK(e, hipMemcpyAsync(out_row_ptr, d + o_orow, 4 * ((size_t)n_rows + 1), hipMemcpyDeviceToHost, s));
-        if (r.n_kept) HIPCHK(e, hipMemcpyAsync(out_route_ids, d + o_oids, 4 * (size_t)r.n_kept, hipMemcpyDeviceToHost, s));
-        if (out_class_counts && n_rows) HIPCHK(e, hipMemcpyAsync(out_class_counts, d + o_cc, 8 * (size_t)n_rows, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(e, hipStreamSynchronize(s));
+    const size_t fits = r.overflow ? 0 : 1; // (rows that do not fit were not written)
+    if (int rc_d = stage_down(e, {{out_events, d + o_ev, 16 * std::min<size_t>(r.n_events, ev_cap)}, {out_row_ptr, d + o_orow, fits * row_ptr4},
+                                  {out_route_ids, d + o_oids, fits * 4 * (size_t)r.n_kept}, {out_class_counts, d + o_cc, fits * cc8}}))
+        return rc_d;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
     return r.overflow ? caps_nospace(e) : BMQ_OK;
-}
-
-extern "C" int bmq_delivery_wait_capped(bmq_engine* e, int ticket, const int32_t* max_pf, const int32_t* max_gf, uint32_t n_caps, const uint32_t* sender_off,
-                                        const int32_t* sender_hash, uint64_t nonce, uint32_t* out_topic, uint32_t* out_route, uint32_t* out_aux, uint32_t row_cap,
-                                        uint32_t* out_share_sender, uint32_t* out_share_member, uint32_t share_cap, uint32_t* out_group_off, uint32_t group_cap,
-                                        bmq_delivery_info* out_info, uint64_t* out_total, int32_t* out_events, uint32_t events_cap, uint32_t* out_n_events,
-                                        bmq_caps_info* out_caps_info) {
-    if (!e || ticket < 0 || ticket >= BMQ_MAX_TICKETS || !out_info || !out_caps_info || !out_total || !sender_off || (n_caps && (!max_pf || !max_gf)) ||
-        delivery_null_outputs(out_topic, out_route, out_aux, row_cap, out_share_sender, out_share_member, share_cap, out_group_off))
-        return BMQ_E_INVAL;
-    if (out_n_events) *out_n_events = 0;
-    if (e->device < 0) return set_err(e, BMQ_E_NODEVICE, "engine is host-only");
-    bmq_engine::BatchSlot& S = e->slots[1 + ticket];
-    { // refused before the wait: the ticket stays as it was
-        std::lock_guard<std::mutex> g0(e->mu);
-        if (int rc_t = caps_check_table(e, max_pf, max_gf, n_caps)) return rc_t;
-        if (S.submitted && !S.devptr && S.format == BMQ_FMT_DELIVERY && S.last.n_tenants != n_caps)
-            return set_err(e, BMQ_E_INVAL, "n_caps is not the tenant count of the ticket's batch");
-    }
-    std::unique_lock<std::mutex> g(e->mu, std::defer_lock);
-    uint64_t total = 0;
-    int rc = ticket_begin(e, ticket, BMQ_FMT_DELIVERY, false, g, &total);
-    if (!g.owns_lock()) return rc;
-    *out_total = total;
-    *out_info = bmq_delivery_info{};
-    *out_caps_info = bmq_caps_info{};
-    DeliveryResult r;
-    CapsResult cr;
-    if (rc == BMQ_OK && total >= 0x7FFFFFF0ull) rc = set_err(e, BMQ_E_RANGE, "more than 2^31 (topic, route) pairs in one batch");
-    if (rc == BMQ_OK) rc = check_senders(e, sender_off, sender_hash, S.n_rows);
-    if (rc == BMQ_OK) {
-        // the caps over the CSR the batch left in the slot, then the plan of the capped CSR, both on the engine stream; the caps table and the
-        // senders are staged in front of them, the capped CSR and the events lie in the engine's buffer, the plan's outputs in the slot
-        const uint32_t n_topics = S.n_rows, n_senders = sender_off[n_topics], ev_cap = out_events ? events_cap : 0u;
-        size_t o = 0;
-        auto take = [&](size_t words) {
-            const size_t at = o;
-            o += (words * 4 + 15) & ~(size_t)15;
-            return at;
-        };
-        const size_t o_pf = take(n_caps), o_gf = take(n_caps), o_orow = take((size_t)n_topics + 1), o_oids = take((size_t)total), o_ev = take(4 * (size_t)ev_cap);
-        const size_t so_bytes = (4 * ((size_t)n_topics + 1) + 15) & ~(size_t)15;
-        const DeliveryOut out(0, row_cap, share_cap, group_cap);
-        if (so_bytes + 4 * (size_t)n_senders + 16 > e->dl_buf.cap || o + 16 > e->caps_buf.cap) poller_stop_locked(e);
-        if (e->dl_buf.ensure(so_bytes + 4 * (size_t)n_senders + 16) != hipSuccess || e->caps_buf.ensure(o + 16) != hipSuccess || S.g_pairs.ensure(out.end + 64) != hipSuccess)
-            rc = set_err(e, BMQ_E_NOMEM, "out of device memory (capped delivery plan)");
-        uint8_t* in = e->dl_buf.as<uint8_t>();
-        uint8_t* c = e->caps_buf.as<uint8_t>();
-        uint8_t* d = S.g_pairs.as<uint8_t>();
-        if (rc == BMQ_OK) {
-            hipError_t he = hipMemcpyAsync(in, sender_off, 4 * ((size_t)n_topics + 1), hipMemcpyHostToDevice, e->stream);
-            if (he == hipSuccess && n_senders) he = hipMemcpyAsync(in + so_bytes, sender_hash, 4 * (size_t)n_senders, hipMemcpyHostToDevice, e->stream);
-            if (he == hipSuccess && n_caps) he = hipMemcpyAsync(c + o_pf, max_pf, 4 * (size_t)n_caps, hipMemcpyHostToDevice, e->stream);
-            if (he == hipSuccess && n_caps) he = hipMemcpyAsync(c + o_gf, max_gf, 4 * (size_t)n_caps, hipMemcpyHostToDevice, e->stream);
-            if (he != hipSuccess) rc = set_err(e, BMQ_E_HIP, std::string("sender upload: ") + hipGetErrorString(he));
-        }
-        if (rc == BMQ_OK)
-            rc = caps_run(e, S.s_row_ptr.as<uint32_t>(), S.s_ids.as<uint32_t>(), n_topics, (uint32_t)total, S.s_topic_tenant.as<uint32_t>(), (const int32_t*)(c + o_pf),
-                          (const int32_t*)(c + o_gf), n_caps, max_pf, max_gf, (uint32_t*)(c + o_orow), (uint32_t*)(c + o_oids), total, nullptr,
-                          ev_cap ? (int32_t*)(c + o_ev) : nullptr, ev_cap, cr, out_caps_info);
-        if (rc == BMQ_OK) {
-            if (out_n_events) *out_n_events = cr.n_events;
-            const size_t n_ev = std::min<size_t>(cr.n_events, ev_cap);
-            hipError_t he = n_ev ? hipMemcpyAsync(out_events, c + o_ev, 16 * n_ev, hipMemcpyDeviceToHost, e->stream) : hipSuccess;
-            if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-            if (he != hipSuccess) rc = set_err(e, BMQ_E_HIP, std::string("event download: ") + hipGetErrorString(he));
-        }
-        if (rc == BMQ_OK)
-            rc = delivery_run(e, (const uint32_t*)(c + o_orow), (const uint32_t*)(c + o_oids), n_topics, (uint32_t)cr.n_kept, (const uint32_t*)in,
-                              (const uint32_t*)(in + so_bytes), n_senders, nonce, (uint32_t*)(d + out.topic), (uint32_t*)(d + out.route), (uint32_t*)(d + out.aux), row_cap,
-                              (uint32_t*)(d + out.sh_sender), (uint32_t*)(d + out.sh_member), share_cap, (uint32_t*)(d + out.group_off), group_cap, r, out_info);
-        if (rc == BMQ_OK && !r.overflow)
-            rc = download_end(e, g, delivery_download(d, out, r, out_topic, out_route, out_aux, out_share_sender, out_share_member, out_group_off, e->s_out));
-    }
-    ticket_release(S);
-    if (rc) return rc;
-    return r.overflow ? delivery_nospace(e) : BMQ_OK;
 }

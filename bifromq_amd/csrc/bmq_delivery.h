@@ -6,8 +6,7 @@
 // The control owns scratch only: nothing here outlives a call, so nothing is tied to a generation of the route index (the slot -> group
 // scatter is filled afresh from the groups of every batch; the share-deliverer bytes belong to Share and follow its rules).
 #pragma once
-#include <functional>
-
+#include "bmq_control.h"
 #include "bmq_delivery_core.h"
 #include "bmq_fanout.h"
 #include "bmq_share.h"
@@ -22,16 +21,13 @@ struct DeliveryResult {
     float ms_group = 0, ms_resolve = 0, ms_map = 0, ms_merge = 0; // when the executor's marks are on
 };
 
-template <class Exec> class Delivery {
-public:
-    explicit Delivery(Exec& exec) : x(exec) {}
-    ~Delivery() { drop(); }
-    Delivery(const Delivery&) = delete;
-    Delivery& operator=(const Delivery&) = delete;
+template <class Exec> class Delivery : public Control<Exec> {
+    using C = Control<Exec>;
+    using C::x, C::fail, C::xfail, C::ensure;
 
-    std::string error;
-    bool invalid = false;              // the last failure was the caller's input (Share says so)
-    std::function<void()> before_free; // called before exec memory is released (a buffer that grows)
+public:
+    using C::invalid; // (here: Share says so)
+    explicit Delivery(Exec& exec) : C(exec) {}
 
     // All pointers are exec memory.  row_ptr [n_topics + 1] with row_ptr[n_topics] == total, ids [total]; sender_off [n_topics + 1],
     // sender_hash [n_senders]; out_topic / out_route / out_aux [row_cap]; out_share_sender / out_share_member [share_cap];
@@ -51,7 +47,7 @@ public:
         x.mark(8);
         FanoutResult fr;
         for (int attempt = 0;; attempt++) {
-            if (!ensure(g_topic, pair_cap, total) || !ensure(g_route, pair_cap2, total) || !ensure(g_off, goff_cap, (size_t)fgroup_cap + 1) || !ensure(g_rep, grep_cap, fgroup_cap))
+            if (!ensure(g_topic, total) || !ensure(g_route, total) || !ensure(g_off, (size_t)fgroup_cap + 1) || !ensure(g_rep, fgroup_cap))
                 return false;
             if (!fo.group(row_ptr, ids, n_topics, total, g_topic, g_route, g_off, g_rep, fgroup_cap, fr)) return fail(fo.error);
             if (!fr.group_overflow) break;
@@ -81,7 +77,7 @@ public:
         ShareResult sr;
         if (n_shared) {
             for (int attempt = 0;; attempt++) {
-                if (!ensure(r_off, roff_cap, (size_t)sgroup_cap + 1) || !ensure(r_pair, rpair_cap, srow_cap)) return false;
+                if (!ensure(r_off, (size_t)sgroup_cap + 1) || !ensure(r_pair, srow_cap)) return false;
                 const uint32_t cap = std::min<uint32_t>(share_cap, srow_cap);
                 if (!sh.resolve(ix, g_topic + P.s0, g_route + P.s0, n_shared, sender_off, sender_hash, n_topics, n_senders, nonce, r_pair, out_share_sender,
                                 out_share_member, cap, r_off, sgroup_cap, sr)) {
@@ -109,7 +105,7 @@ public:
         const FanoutState st = fo.state(); // (as the call above left it: a grown table, another seed)
         const uint32_t has_unres = P.n_sgroups ? (sr.special & 1u) : 0u;
         if (P.n_sgroups) {
-            if (!ensure(slot_group, slot_cap, st.gt_cap) || !ensure(tgt, tgt_cap, P.n_sgroups) || !ensure(is_new, new_cap, P.n_sgroups) || !ensure(new_scan, scan_cap, P.n_sgroups))
+            if (!ensure(slot_group, st.gt_cap) || !ensure(tgt, P.n_sgroups) || !ensure(is_new, P.n_sgroups) || !ensure(new_scan, P.n_sgroups))
                 return false;
             P.slot_group = slot_group;
             P.tgt = tgt;
@@ -133,7 +129,7 @@ public:
         if (res.overflow) return true;
         if (P.n_rows == 0) return x.copy_in(out_group_off, &z, sizeof(z)) ? true : xfail(); // (ordered shares only, and no topic has a sender)
         // ---- 4. sizes, offsets, rows
-        if (!ensure(share_of, sof_cap, P.n_groups) || !ensure(cnt, cnt_cap, P.n_groups) || !ensure(cnt_scan, cscan_cap, P.n_groups)) return false;
+        if (!ensure(share_of, P.n_groups) || !ensure(cnt, P.n_groups) || !ensure(cnt_scan, P.n_groups)) return false;
         P.share_of = share_of;
         P.cnt = cnt;
         P.cnt_scan = cnt_scan;
@@ -153,41 +149,10 @@ public:
         return true;
     }
 
-    void drop() {
-        for (uint32_t** p : {&g_topic, &g_route, &g_off, &g_rep, &r_pair, &r_off, &slot_group, &tgt, &is_new, &new_scan, &share_of, &cnt, &cnt_scan}) rel(*p);
-        pair_cap = pair_cap2 = goff_cap = grep_cap = rpair_cap = roff_cap = slot_cap = tgt_cap = new_cap = scan_cap = sof_cap = cnt_cap = cscan_cap = 0;
-    }
-
 private:
-    Exec& x;
     uint32_t fgroup_cap = 1024, sgroup_cap = 1024, srow_cap = 4096; // what the two steps are offered; grown to what they report
-    uint32_t *g_topic = nullptr, *g_route = nullptr, *g_off = nullptr, *g_rep = nullptr, *r_pair = nullptr, *r_off = nullptr;
-    uint32_t *slot_group = nullptr, *tgt = nullptr, *is_new = nullptr, *new_scan = nullptr, *share_of = nullptr, *cnt = nullptr, *cnt_scan = nullptr;
-    size_t pair_cap = 0, pair_cap2 = 0, goff_cap = 0, grep_cap = 0, rpair_cap = 0, roff_cap = 0, slot_cap = 0, tgt_cap = 0, new_cap = 0, scan_cap = 0, sof_cap = 0,
-           cnt_cap = 0, cscan_cap = 0;
-
-    template <class T> void rel(T*& p) {
-        if (p) x.release(p);
-        p = nullptr;
-    }
-    bool fail(const std::string& m) {
-        error = m;
-        return false;
-    }
-    bool xfail() { return fail(x.err.empty() ? "exec failure" : x.err); }
-    // grow-only scratch, contents dropped; a buffer in use by the stream is not freed under it, and the free goes through the hook
-    bool ensure(uint32_t*& p, size_t& cap, size_t need) {
-        if (need <= cap && p) return true;
-        if (!x.sync()) return xfail();
-        if (p && before_free) before_free();
-        rel(p);
-        cap = 0;
-        const size_t want = need + need / 4 + 64;
-        p = (uint32_t*)x.alloc(want * sizeof(uint32_t) + 16);
-        if (!p) return fail("out of memory");
-        cap = want;
-        return true;
-    }
+    typename C::template Scratch<uint32_t> g_topic{*this}, g_route{*this}, g_off{*this}, g_rep{*this}, r_pair{*this}, r_off{*this}, slot_group{*this}, tgt{*this}, is_new{*this},
+        new_scan{*this}, share_of{*this}, cnt{*this}, cnt_scan{*this};
 };
 
 } // namespace bmq

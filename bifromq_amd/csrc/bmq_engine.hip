@@ -339,6 +339,51 @@ int upload(bmq_engine* e, DevBuf& b, const void* src, size_t bytes, hipStream_t 
     return BMQ_OK;
 }
 
+// ---- staging of the host-buffer entry points behind the match: 16-byte aligned pieces of one device buffer, sizes in bytes
+struct Stage {
+    size_t end = 0;
+    size_t take(size_t bytes) {
+        const size_t at = end;
+        end += (bytes + 15) & ~(size_t)15;
+        return at;
+    }
+};
+// THE place a staging buffer grows.  A buffer that grows is freed first, and a free waits for every stream of the device: the persistent
+// matcher leaves before (poller_stop_locked returns at once when it is not running).
+int stage_ensure(bmq_engine* e, DevBuf& b, size_t bytes) {
+    if (bytes > b.cap) poller_stop_locked(e);
+    HIPCHK(e, b.ensure(bytes));
+    return BMQ_OK;
+}
+// pieces up / down (s: the engine stream unless given), enqueued; a piece of no bytes is skipped
+struct Piece {
+    void* dst;
+    const void* src;
+    size_t bytes;
+};
+int stage_copy(bmq_engine* e, hipMemcpyKind kind, std::initializer_list<Piece> pieces, hipStream_t s) {
+    for (const Piece& p : pieces)
+        if (p.bytes) HIPCHK(e, hipMemcpyAsync(p.dst, p.src, p.bytes, kind, s ? s : e->stream));
+    return BMQ_OK;
+}
+int stage_up(bmq_engine* e, std::initializer_list<Piece> pieces) { return stage_copy(e, hipMemcpyHostToDevice, pieces, nullptr); }
+int stage_down(bmq_engine* e, std::initializer_list<Piece> pieces, hipStream_t s = nullptr) { return stage_copy(e, hipMemcpyDeviceToHost, pieces, s); }
+// a CSR in host memory: row_ptr [n_rows + 1] from 0, ascending, fewer than 2^31 pairs (and fewer than rows_end rows; 0: no limit on the rows)
+int check_csr(bmq_engine* e, const uint32_t* row_ptr, uint32_t n_rows, uint32_t rows_end = 0) {
+    if (row_ptr[0] != 0) return set_err(e, BMQ_E_INVAL, "row_ptr[0] != 0");
+    for (uint32_t i = 0; i < n_rows; i++)
+        if (row_ptr[i + 1] < row_ptr[i]) return set_err(e, BMQ_E_INVAL, "row_ptr not ascending");
+    if (row_ptr[n_rows] >= 0x7FFFFFF0u || (rows_end && n_rows >= rows_end)) return set_err(e, BMQ_E_RANGE, "more than 2^31 (topic, route) pairs in one batch");
+    return BMQ_OK;
+}
+int check_senders(bmq_engine* e, const uint32_t* sender_off, const int32_t* sender_hash, uint32_t n_topics) {
+    if (sender_off[0] != 0) return set_err(e, BMQ_E_INVAL, "sender_off[0] != 0");
+    for (uint32_t t = 0; t < n_topics; t++)
+        if (sender_off[t + 1] < sender_off[t]) return set_err(e, BMQ_E_INVAL, "sender_off not ascending");
+    if (sender_off[n_topics] && !sender_hash) return set_err(e, BMQ_E_INVAL, "null pointer");
+    return BMQ_OK;
+}
+
 // ---- dist batch ------------------------------------------------------------------------------------------------
 // topics per k_walk / k_expand wave = 2^shift: small batches are spread over more, shorter waves (see k_walk)
 uint32_t tpw_shift_for(uint32_t n_topics) {
@@ -979,6 +1024,22 @@ void ticket_release(bmq_engine::BatchSlot& S) {
 template <class F> static auto with_index(bmq_engine* e, F&& f) { return e->dix ? f(*e->dix) : f(*e->hix); }
 // (serving generation, generation being built) of whichever executor the engine has
 template <class F> static auto with_generations(bmq_engine* e, F&& f) { return e->dix ? f(*e->dix, *e->cmp.next_d) : f(*e->hix, *e->cmp.next_h); }
+// The engine's control of one kind (hp / dp: the one over the host executor / the device executor) with the index it works on, created by
+// the first call.  A buffer of a control that grows is freed first, and a free waits for every stream of the device: the persistent matcher
+// leaves before (it is back with the next singleton call).
+template <class H, class D, class F> static int with_control(bmq_engine* e, std::unique_ptr<H>& hp, std::unique_ptr<D>& dp, F&& f) {
+    if (e->device < 0) {
+        if (!hp) hp = std::make_unique<H>(e->hx);
+        return f(*hp, *e->hix);
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    if (!dp) {
+        dp = std::make_unique<D>(e->dx);
+        dp->before_free = [e] { poller_stop_locked(e); };
+    }
+    e->dx.marks_on = e->kernel_events;
+    return f(*dp, *e->dix);
+}
 // (`also`: the executor of a generation being built, when the caller is the thread that drives it -- bmq_compact_poll works on it with
 // e->mu released, so nobody else may read its error string: ADVICE r5)
 static int index_error(bmq_engine* e, const std::string& msg, bool invalid_input, DevExec* also = nullptr) {
@@ -2276,9 +2337,9 @@ int32_t bmq_java_string_hash(const uint8_t* utf8, uint32_t len) { return java_st
 #include "bmq_exchange.inc"
 #include "bmq_fanout_engine.inc"
 #include "bmq_share_engine.inc"
-#include "bmq_delivery_engine.inc"
 #include "bmq_formats.inc"
 #include "bmq_order_engine.inc"
 #include "bmq_prefix_engine.inc"
 #include "bmq_caps_engine.inc"
 #include "bmq_gate_engine.inc"
+#include "bmq_delivery_engine.inc"

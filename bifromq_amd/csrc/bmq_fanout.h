@@ -6,6 +6,7 @@
 //   bool sort_pairs32(keys_in, keys_out, vals_in, vals_out, n, end_bit)                              stable, ascending
 //   bool scan_flags(in, out, n)                                                                      inclusive sum
 #pragma once
+#include "bmq_control.h"
 #include "bmq_dist_index.h"
 #include "bmq_fanout_core.h"
 
@@ -27,14 +28,14 @@ struct FanoutCounters {
     uint64_t n_reseed = 0;   // group-table resets after a 64-bit hash collision (same size, new seed)
 };
 
-template <class Exec> class Fanout {
-public:
-    Fanout(Exec& exec, DistIndex<Exec>& index) : x(exec), ix(index) {}
-    ~Fanout() { drop(); }
-    Fanout(const Fanout&) = delete;
-    Fanout& operator=(const Fanout&) = delete;
+template <class Exec> class Fanout : public ControlBase<Exec> {
+    using C = ControlBase<Exec>;
+    using C::x, C::rel, C::fail, C::xfail;
 
-    std::string error;
+public:
+    Fanout(Exec& exec, DistIndex<Exec>& index) : C(exec), ix(index) {}
+    ~Fanout() { drop(); }
+
     uint32_t initial_table = 1024; // tests shrink it to force growth
     FanoutCounters ctr;
     uint32_t keys_mapped() const { return used_slots; }
@@ -139,7 +140,6 @@ public:
     }
 
 private:
-    Exec& x;
     DistIndex<Exec>& ix;
     FanoutState st{};
     uint64_t generation = ~0ull;
@@ -262,15 +262,6 @@ private:
         }
     }
 
-    template <class T> void rel(T*& p) {
-        if (p) x.release(p);
-        p = nullptr;
-    }
-    bool fail(const std::string& m) {
-        error = m;
-        return false;
-    }
-    bool xfail() { return fail(x.err.empty() ? "exec failure" : x.err); }
     template <class T> bool fresh(T*& p, size_t n) {
         rel(p);
         p = (T*)x.alloc(n * sizeof(T) + 16);

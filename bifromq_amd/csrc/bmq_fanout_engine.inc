@@ -32,11 +32,8 @@ extern "C" int bmq_fanout_group(bmq_engine* e, const uint32_t* row_ptr, const ui
                                 uint32_t* out_route, uint64_t pair_cap, uint32_t* out_group_off, uint32_t* out_group_rep, uint32_t group_cap,
                                 uint32_t* out_n_groups, uint32_t* out_special) {
     if (!e || !row_ptr || !out_group_off || (group_cap && !out_group_rep)) return BMQ_E_INVAL;
-    if (row_ptr[0] != 0) return set_err(e, BMQ_E_INVAL, "row_ptr[0] != 0");
-    for (uint32_t i = 0; i < n_topics; i++)
-        if (row_ptr[i + 1] < row_ptr[i]) return set_err(e, BMQ_E_INVAL, "row_ptr not ascending");
+    if (int rc_c = check_csr(e, row_ptr, n_topics)) return rc_c;
     const uint32_t total = row_ptr[n_topics];
-    if (total >= 0x7FFFFFF0u) return set_err(e, BMQ_E_RANGE, "more than 2^31 (topic, route) pairs in one batch");
     if (total > pair_cap || (total && (!route_ids || !out_topic || !out_route))) return set_err(e, BMQ_E_NOSPACE, "pair buffers too small");
     std::unique_lock<std::recursive_mutex> api_lock(e->api);
     std::lock_guard<std::mutex> g(e->mu);
@@ -52,31 +49,20 @@ extern "C" int bmq_fanout_group(bmq_engine* e, const uint32_t* row_ptr, const ui
     HIPCHK(e, hipSetDevice(e->device));
     if (!e->dfo) e->dfo = std::make_unique<Fanout<DevExec>>(e->dx, *e->dix);
     // staging: [row_ptr | ids | out_topic | out_route | group_off | group_rep]
-    size_t o = 0;
-    auto take = [&](size_t words) {
-        const size_t at = o;
-        o += (words * 4 + 15) & ~(size_t)15;
-        return at;
-    };
-    const size_t o_row = take((size_t)n_topics + 1), o_ids = take(total), o_ot = take(total), o_or = take(total), o_go = take((size_t)group_cap + 1),
-                 o_gr = take(group_cap);
-    HIPCHK(e, e->fo_buf.ensure(o + 16));
+    Stage st;
+    const size_t o_row = st.take(4 * ((size_t)n_topics + 1)), o_ids = st.take(4 * (size_t)total), o_ot = st.take(4 * (size_t)total), o_or = st.take(4 * (size_t)total),
+                 o_go = st.take(4 * ((size_t)group_cap + 1)), o_gr = st.take(4 * (size_t)group_cap);
+    if (int rc_b = stage_ensure(e, e->fo_buf, st.end + 16)) return rc_b;
     uint8_t* d = e->fo_buf.as<uint8_t>();
-    hipStream_t s = e->stream;
-    HIPCHK(e, hipMemcpyAsync(d + o_row, row_ptr, 4 * ((size_t)n_topics + 1), hipMemcpyHostToDevice, s));
-    if (total) HIPCHK(e, hipMemcpyAsync(d + o_ids, route_ids, 4 * (size_t)total, hipMemcpyHostToDevice, s));
+    if (int rc_u = stage_up(e, {{d + o_row, row_ptr, 4 * ((size_t)n_topics + 1)}, {d + o_ids, route_ids, 4 * (size_t)total}})) return rc_u;
     if (!e->dfo->group((const uint32_t*)(d + o_row), (const uint32_t*)(d + o_ids), n_topics, total, (uint32_t*)(d + o_ot), (uint32_t*)(d + o_or),
                        (uint32_t*)(d + o_go), (uint32_t*)(d + o_gr), group_cap, r))
         return index_error(e, e->dfo->error, false);
-    if (total) {
-        HIPCHK(e, hipMemcpyAsync(out_topic, d + o_ot, 4 * (size_t)total, hipMemcpyDeviceToHost, s));
-        HIPCHK(e, hipMemcpyAsync(out_route, d + o_or, 4 * (size_t)total, hipMemcpyDeviceToHost, s));
-    }
-    if (!r.group_overflow) {
-        HIPCHK(e, hipMemcpyAsync(out_group_off, d + o_go, 4 * ((size_t)r.n_groups + 1), hipMemcpyDeviceToHost, s));
-        if (r.n_groups) HIPCHK(e, hipMemcpyAsync(out_group_rep, d + o_gr, 4 * (size_t)r.n_groups, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(e, hipStreamSynchronize(s));
+    const size_t fits = r.group_overflow ? 0 : 1; // (a group table that is too small is not copied)
+    if (int rc_d = stage_down(e, {{out_topic, d + o_ot, 4 * (size_t)total}, {out_route, d + o_or, 4 * (size_t)total},
+                                  {out_group_off, d + o_go, fits * 4 * ((size_t)r.n_groups + 1)}, {out_group_rep, d + o_gr, fits * 4 * (size_t)r.n_groups}}))
+        return rc_d;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
     return fanout_result(e, r, out_n_groups, out_special);
 }
 

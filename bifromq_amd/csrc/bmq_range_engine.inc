@@ -23,31 +23,20 @@ extern "C" int bmq_range_lookup(bmq_engine* e, const uint8_t* tenant, uint32_t t
     std::lock_guard<std::mutex> g(e->mu);
     HIPCHK(e, hipSetDevice(e->device));
     const size_t tb = topic_off[n_topics], fb = first_off[n_cand], lb = last_off[n_cand];
-    // one staging block: [tenant | topics | topic_off | kind | first | first_off | last | last_off | keep], 16-byte aligned pieces
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += (bytes + 15) & ~(size_t)15;
-        return at;
-    };
-    const size_t o_ten = take(tenant_len + 16), o_top = take(tb + 16), o_toff = take(4 * ((size_t)n_topics + 1)), o_kind = take(n_cand),
-                 o_first = take(fb + 16), o_foff = take(4 * ((size_t)n_cand + 1)), o_last = take(lb + 16), o_loff = take(4 * ((size_t)n_cand + 1)),
-                 o_keep = take((size_t)n_topics * n_cand);
-    HIPCHK(e, e->range_buf.ensure(o));
+    // staging: [tenant | topics | topic_off | kind | first | first_off | last | last_off | keep]
+    Stage st;
+    const size_t o_ten = st.take(tenant_len + 16), o_top = st.take(tb + 16), o_toff = st.take(4 * ((size_t)n_topics + 1)), o_kind = st.take(n_cand), o_first = st.take(fb + 16),
+                 o_foff = st.take(4 * ((size_t)n_cand + 1)), o_last = st.take(lb + 16), o_loff = st.take(4 * ((size_t)n_cand + 1)), o_keep = st.take((size_t)n_topics * n_cand);
+    if (int rc_b = stage_ensure(e, e->range_buf, st.end)) return rc_b;
     uint8_t* d = e->range_buf.as<uint8_t>();
     hipStream_t s = e->stream;
-    if (tenant_len) HIPCHK(e, hipMemcpyAsync(d + o_ten, tenant, tenant_len, hipMemcpyHostToDevice, s));
-    if (tb) HIPCHK(e, hipMemcpyAsync(d + o_top, topics, tb, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(d + o_toff, topic_off, 4 * ((size_t)n_topics + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(d + o_kind, cand_kind, n_cand, hipMemcpyHostToDevice, s));
-    if (fb) HIPCHK(e, hipMemcpyAsync(d + o_first, first, fb, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(d + o_foff, first_off, 4 * ((size_t)n_cand + 1), hipMemcpyHostToDevice, s));
-    if (lb) HIPCHK(e, hipMemcpyAsync(d + o_last, last, lb, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(d + o_loff, last_off, 4 * ((size_t)n_cand + 1), hipMemcpyHostToDevice, s));
+    if (int rc_u = stage_up(e, {{d + o_ten, tenant, tenant_len}, {d + o_top, topics, tb}, {d + o_toff, topic_off, 4 * ((size_t)n_topics + 1)}, {d + o_kind, cand_kind, n_cand},
+                                {d + o_first, first, fb}, {d + o_foff, first_off, 4 * ((size_t)n_cand + 1)}, {d + o_last, last, lb}, {d + o_loff, last_off, 4 * ((size_t)n_cand + 1)}}))
+        return rc_u;
     hipLaunchKernelGGL(bmq::k_range_lookup, dim3((n_topics + 63) / 64), dim3(64), 0, s, d + o_ten, tenant_len, d + o_top, (const uint32_t*)(d + o_toff),
                        n_topics, d + o_kind, d + o_first, (const uint32_t*)(d + o_foff), d + o_last, (const uint32_t*)(d + o_loff), n_cand, d + o_keep);
     HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(out_keep, d + o_keep, (size_t)n_topics * n_cand, hipMemcpyDeviceToHost, s));
+    if (int rc_d = stage_down(e, {{out_keep, d + o_keep, (size_t)n_topics * n_cand}})) return rc_d;
     HIPCHK(e, hipStreamSynchronize(s));
     return BMQ_OK;
 }

@@ -7,9 +7,9 @@
 // Tables are keyed by route id: they belong to ONE generation of the route index and are dropped when it changes -- unless the engine
 // carries them along (bmq_config.share_carry: carry_prepare / carry_finish below move each table to the id its route KEY has next).
 #pragma once
-#include <functional>
 #include <unordered_map>
 
+#include "bmq_control.h"
 #include "bmq_dist_index.h"
 #include "bmq_share_core.h"
 
@@ -25,16 +25,14 @@ struct ShareInfo {
     float ms[5] = {0, 0, 0, 0, 0}; // the last resolve, when the executor's marks are on: count + scan, rows, resolve, sort, heads + scan + groups
 };
 
-template <class Exec> class Share {
-public:
-    explicit Share(Exec& exec) : x(exec) {}
-    ~Share() { drop(); }
-    Share(const Share&) = delete;
-    Share& operator=(const Share&) = delete;
+template <class Exec> class Share : public Control<Exec> {
+    using C = Control<Exec>;
+    using C::x, C::rel, C::fail, C::bad, C::xfail;
 
-    std::string error;
-    bool invalid = false; // the last failure was the caller's input
-    std::function<void()> before_free; // called before exec memory is released (a buffer that grows)
+public:
+    using C::error, C::invalid, C::before_free;
+    explicit Share(Exec& exec) : C(exec) {}
+    ~Share() { drop(); }
 
     // Replaces the member lists of route_ids[0 .. n): members member_off[i] .. member_off[i + 1] of (urls, url_off); an empty list removes
     // the table.  Everything is validated before anything changes.
@@ -404,7 +402,6 @@ private:
         uint64_t size64() const { return (uint64_t)urls.size() * (2 * entries - 1); }
         uint64_t size32() const { return (uint64_t)urls.size() * 3; }
     };
-    Exec& x;
     uint64_t generation = ~0ull;
     std::unordered_map<uint32_t, HostTable> tabs;    // by route id
     std::unordered_map<std::string, uint32_t> sd_num; // subBrokerId NUL delivererKey -> share-deliverer number
@@ -630,19 +627,6 @@ private:
         return true;
     }
 
-    template <class T> void rel(T*& p) {
-        if (p) x.release(p);
-        p = nullptr;
-    }
-    bool fail(const std::string& m) {
-        error = m;
-        return false;
-    }
-    bool bad(const std::string& m) {
-        invalid = true;
-        return fail(m);
-    }
-    bool xfail() { return fail(x.err.empty() ? "exec failure" : x.err); }
     template <class T> bool fresh(T*& p, size_t n) {
         if (p && before_free) before_free();
         rel(p);

@@ -1,21 +1,6 @@
 // bmq_share_engine.inc -- bmq_share_members_apply / bmq_share_resolve / bmq_share_resolve_dev / bmq_share_member / bmq_share_info_get: the
 // receivers of shared subscriptions (bmq_share_core.h says what they replace in the reference).  Included at the end of bmq_engine.hip.
 namespace {
-// the engine's Share over whichever executor it has, created by the first call.  A buffer that grows is freed first, and a free waits for
-// every stream of the device: the persistent matcher leaves before (it is back with the next singleton call).
-template <class F> int with_share(bmq_engine* e, F&& f) {
-    if (e->device < 0) {
-        if (!e->hsh) e->hsh = std::make_unique<Share<HostExec>>(e->hx);
-        return f(*e->hsh, *e->hix);
-    }
-    HIPCHK(e, hipSetDevice(e->device));
-    if (!e->dsh) {
-        e->dsh = std::make_unique<Share<DevExec>>(e->dx);
-        e->dsh->before_free = [e] { poller_stop_locked(e); };
-    }
-    e->dx.marks_on = e->kernel_events;
-    return f(*e->dsh, *e->dix);
-}
 template <class S> int share_error(bmq_engine* e, const S& s) { return index_error(e, s.error, s.invalid); }
 int share_result(bmq_engine* e, const ShareResult& r, uint32_t* out_n_rows, uint32_t* out_n_groups, uint32_t* out_special) {
     if (out_n_rows) *out_n_rows = r.n_rows;
@@ -32,20 +17,20 @@ DistIndex<DevExec>& next_generation(bmq_engine* e, DistIndex<DevExec>&) { return
 DistIndex<HostExec>& next_generation(bmq_engine* e, DistIndex<HostExec>&) { return *e->cmp.next_h; }
 } // namespace
 static void share_carry_prepare(bmq_engine* e, bool copy_bytes) {
-    (void)with_share(e, [&](auto& sh, auto& ix) {
+    (void)with_control(e, e->hsh, e->dsh, [&](auto& sh, auto& ix) {
         if (!sh.carry_prepare(ix, copy_bytes)) e->err = sh.error;
         return 0;
     });
 }
 static void share_carry_finish(bmq_engine* e, bool changed) {
-    (void)with_share(e, [&](auto& sh, auto& ix) {
+    (void)with_control(e, e->hsh, e->dsh, [&](auto& sh, auto& ix) {
         if (!changed) sh.carry_cancel();
         else if (!sh.carry_finish(ix)) e->err = sh.error;
         return 0;
     });
 }
 static void share_carry_swap(bmq_engine* e) {
-    (void)with_share(e, [&](auto& sh, auto& ix) {
+    (void)with_control(e, e->hsh, e->dsh, [&](auto& sh, auto& ix) {
         if (!sh.carry_prepare(ix, false) || !sh.carry_finish(next_generation(e, ix))) e->err = sh.error;
         return 0;
     });
@@ -57,7 +42,7 @@ extern "C" int bmq_share_carry_info_get(const bmq_engine* ce, bmq_share_carry_in
     std::unique_lock<std::recursive_mutex> api_lock(e->api);
     std::lock_guard<std::mutex> g(e->mu);
     memset(out, 0, sizeof(*out));
-    return with_share(e, [&](auto& sh, auto&) {
+    return with_control(e, e->hsh, e->dsh, [&](auto& sh, auto&) {
         const auto& ci = sh.carry_info;
         out->from_generation = ci.from_generation;
         out->to_generation = ci.to_generation;
@@ -81,7 +66,7 @@ extern "C" int bmq_share_members_apply(bmq_engine* e, const uint32_t* route_ids,
     if (int rc_open = complete_apply(e)) return rc_open; // (a batch handed over with bmq_routes_apply_async first)
     if (!e->built) return set_err(e, BMQ_E_STATE, "no index");
     if (e->device >= 0) poller_stop_locked(e); // (the mutation path allocates and frees)
-    return with_share(e, [&](auto& sh, auto& ix) { return sh.apply(ix, route_ids, n, member_off, urls, url_off) ? (int)BMQ_OK : share_error(e, sh); });
+    return with_control(e, e->hsh, e->dsh, [&](auto& sh, auto& ix) { return sh.apply(ix, route_ids, n, member_off, urls, url_off) ? (int)BMQ_OK : share_error(e, sh); });
 }
 
 extern "C" int bmq_share_resolve_dev(bmq_engine* e, const uint32_t* d_pair_topic, const uint32_t* d_pair_route, uint32_t n_pairs,
@@ -98,7 +83,7 @@ extern "C" int bmq_share_resolve_dev(bmq_engine* e, const uint32_t* d_pair_topic
     if (int rc_open = complete_apply(e)) return rc_open; // (a batch handed over with bmq_routes_apply_async first)
     if (!e->built) return set_err(e, BMQ_E_STATE, "no index");
     ShareResult r;
-    const int rc = with_share(e, [&](auto& sh, auto& ix) {
+    const int rc = with_control(e, e->hsh, e->dsh, [&](auto& sh, auto& ix) {
         return sh.resolve(ix, d_pair_topic, d_pair_route, n_pairs, d_sender_off, (const uint32_t*)d_sender_hash, n_topics, n_senders, nonce, d_out_pair,
                           d_out_sender, d_out_member, row_cap, d_out_group_off, group_cap, r)
                    ? (int)BMQ_OK
@@ -114,18 +99,15 @@ extern "C" int bmq_share_resolve(bmq_engine* e, const uint32_t* pair_topic, cons
     if (!e) return BMQ_E_INVAL;
     if (!out_group_off || !sender_off || (n_pairs && (!pair_topic || !pair_route)) || (row_cap && (!out_pair || !out_sender || !out_member)))
         return set_err(e, BMQ_E_INVAL, "null pointer");
-    if (sender_off[0] != 0) return set_err(e, BMQ_E_INVAL, "sender_off[0] != 0");
-    for (uint32_t t = 0; t < n_topics; t++)
-        if (sender_off[t + 1] < sender_off[t]) return set_err(e, BMQ_E_INVAL, "sender_off not ascending");
+    if (int rc_s = check_senders(e, sender_off, sender_hash, n_topics)) return rc_s;
     const uint32_t n_senders = sender_off[n_topics];
-    if (n_senders && !sender_hash) return set_err(e, BMQ_E_INVAL, "null pointer");
     std::unique_lock<std::recursive_mutex> api_lock(e->api);
     std::lock_guard<std::mutex> g(e->mu);
     if (int rc_open = complete_apply(e)) return rc_open; // (a batch handed over with bmq_routes_apply_async first)
     if (!e->built) return set_err(e, BMQ_E_STATE, "no index");
     ShareResult r;
     if (e->device < 0) { // host-only engine: the same per-item functions on host threads, straight on the caller's buffers
-        const int rc = with_share(e, [&](auto& sh, auto& ix) {
+        const int rc = with_control(e, e->hsh, e->dsh, [&](auto& sh, auto& ix) {
             return sh.resolve(ix, pair_topic, pair_route, n_pairs, sender_off, (const uint32_t*)sender_hash, n_topics, n_senders, nonce, out_pair, out_sender,
                               out_member, row_cap, out_group_off, group_cap, r)
                        ? (int)BMQ_OK
@@ -135,25 +117,15 @@ extern "C" int bmq_share_resolve(bmq_engine* e, const uint32_t* pair_topic, cons
     }
     HIPCHK(e, hipSetDevice(e->device));
     // staging: [pair_topic | pair_route | sender_off | sender_hash | out_pair | out_sender | out_member | group_off]
-    size_t o = 0;
-    auto take = [&](size_t words) {
-        const size_t at = o;
-        o += (words * 4 + 15) & ~(size_t)15;
-        return at;
-    };
-    const size_t o_pt = take(n_pairs), o_pr = take(n_pairs), o_so = take((size_t)n_topics + 1), o_sh = take(n_senders), o_op = take(row_cap),
-                 o_os = take(row_cap), o_om = take(row_cap), o_go = take((size_t)group_cap + 1);
-    if (o + 16 > e->sh_buf.cap) poller_stop_locked(e);
-    HIPCHK(e, e->sh_buf.ensure(o + 16));
+    Stage st;
+    const size_t o_pt = st.take(4 * (size_t)n_pairs), o_pr = st.take(4 * (size_t)n_pairs), o_so = st.take(4 * ((size_t)n_topics + 1)), o_sh = st.take(4 * (size_t)n_senders),
+                 o_op = st.take(4 * (size_t)row_cap), o_os = st.take(4 * (size_t)row_cap), o_om = st.take(4 * (size_t)row_cap), o_go = st.take(4 * ((size_t)group_cap + 1));
+    if (int rc_b = stage_ensure(e, e->sh_buf, st.end + 16)) return rc_b;
     uint8_t* d = e->sh_buf.as<uint8_t>();
-    hipStream_t s = e->stream;
-    if (n_pairs) {
-        HIPCHK(e, hipMemcpyAsync(d + o_pt, pair_topic, 4 * (size_t)n_pairs, hipMemcpyHostToDevice, s));
-        HIPCHK(e, hipMemcpyAsync(d + o_pr, pair_route, 4 * (size_t)n_pairs, hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(e, hipMemcpyAsync(d + o_so, sender_off, 4 * ((size_t)n_topics + 1), hipMemcpyHostToDevice, s));
-    if (n_senders) HIPCHK(e, hipMemcpyAsync(d + o_sh, sender_hash, 4 * (size_t)n_senders, hipMemcpyHostToDevice, s));
-    const int rc = with_share(e, [&](auto& sh, auto& ix) {
+    if (int rc_u = stage_up(e, {{d + o_pt, pair_topic, 4 * (size_t)n_pairs}, {d + o_pr, pair_route, 4 * (size_t)n_pairs}, {d + o_so, sender_off, 4 * ((size_t)n_topics + 1)},
+                                {d + o_sh, sender_hash, 4 * (size_t)n_senders}}))
+        return rc_u;
+    const int rc = with_control(e, e->hsh, e->dsh, [&](auto& sh, auto& ix) {
         return sh.resolve(ix, (const uint32_t*)(d + o_pt), (const uint32_t*)(d + o_pr), n_pairs, (const uint32_t*)(d + o_so), (const uint32_t*)(d + o_sh),
                           n_topics, n_senders, nonce, (uint32_t*)(d + o_op), (uint32_t*)(d + o_os), (uint32_t*)(d + o_om), row_cap, (uint32_t*)(d + o_go),
                           group_cap, r)
@@ -161,15 +133,11 @@ extern "C" int bmq_share_resolve(bmq_engine* e, const uint32_t* pair_topic, cons
                    : share_error(e, sh);
     });
     if (rc) return rc;
-    if (!r.overflow) {
-        if (r.n_rows) {
-            HIPCHK(e, hipMemcpyAsync(out_pair, d + o_op, 4 * (size_t)r.n_rows, hipMemcpyDeviceToHost, s));
-            HIPCHK(e, hipMemcpyAsync(out_sender, d + o_os, 4 * (size_t)r.n_rows, hipMemcpyDeviceToHost, s));
-            HIPCHK(e, hipMemcpyAsync(out_member, d + o_om, 4 * (size_t)r.n_rows, hipMemcpyDeviceToHost, s));
-        }
-        HIPCHK(e, hipMemcpyAsync(out_group_off, d + o_go, 4 * ((size_t)r.n_groups + 1), hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(e, hipStreamSynchronize(s));
+    if (!r.overflow)
+        if (int rc_d = stage_down(e, {{out_pair, d + o_op, 4 * (size_t)r.n_rows}, {out_sender, d + o_os, 4 * (size_t)r.n_rows}, {out_member, d + o_om, 4 * (size_t)r.n_rows},
+                                      {out_group_off, d + o_go, 4 * ((size_t)r.n_groups + 1)}}))
+            return rc_d;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
     return share_result(e, r, out_n_rows, out_n_groups, out_special);
 }
 
@@ -181,7 +149,7 @@ extern "C" int bmq_share_member(const bmq_engine* ce, uint32_t route_id, uint32_
     if (int rc_open = complete_apply(e)) return rc_open;
     if (!e->built) return set_err(e, BMQ_E_STATE, "no index");
     std::string url;
-    const int rc = with_share(e, [&](auto& sh, auto& ix) { return sh.member(ix, route_id, index, url) ? (int)BMQ_OK : share_error(e, sh); });
+    const int rc = with_control(e, e->hsh, e->dsh, [&](auto& sh, auto& ix) { return sh.member(ix, route_id, index, url) ? (int)BMQ_OK : share_error(e, sh); });
     if (rc) return rc;
     *out_len = (uint32_t)url.size();
     if (url.size() > cap) return set_err(e, BMQ_E_NOSPACE, "url buffer too small");
@@ -197,7 +165,7 @@ extern "C" int bmq_share_info_get(const bmq_engine* ce, bmq_share_info* out) {
     if (int rc_open = complete_apply(e)) return rc_open;
     memset(out, 0, sizeof(*out));
     ShareInfo si;
-    const int rc = with_share(e, [&](auto& sh, auto& ix) { return sh.info(ix, si) ? (int)BMQ_OK : share_error(e, sh); });
+    const int rc = with_control(e, e->hsh, e->dsh, [&](auto& sh, auto& ix) { return sh.info(ix, si) ? (int)BMQ_OK : share_error(e, sh); });
     if (rc) return rc;
     out->n_tables = si.n_tables;
     out->n_members = si.n_members;

@@ -241,4 +241,19 @@ def test_gpu_gated_delivery_wait():
     with pytest.raises(B.BmqError) as ex:
         eng.match_wait_delivery_gated(t, table, pack, thr, so, sh, 21, *outs())
     assert ex.value.code == -7
+    # a stage that cannot bind is a stage that is skipped: three tickets of the batch, waited for plainly, capped and gated
+    tickets = [eng.match_submit_fmt(*a, eng.FMT_DELIVERY) for _ in range(3)]
+    o = outs()
+    tot, info = eng.match_wait_delivery(tickets[0], so, sh, 21, *o)
+    plain = D.plan_dict(eng, cut(o, info))
+    assert tot == total
+    o = outs()
+    tot, info, ev, cinfo = eng.match_wait_delivery_capped(tickets[1], [(G.INT_MAX, G.INT_MAX)] * len(tenants), so, sh, 21, *o)
+    assert D.plan_dict(eng, cut(o, info)) == plain and tot == total
+    assert cinfo.n_kept == total and cinfo.n_events == 0 and len(ev) == 0
+    o = outs()
+    tot, info, ev, cinfo, fl, mb, mr, ginfo = eng.match_wait_delivery_gated(tickets[2], [(G.INT_MAX, G.INT_MAX, G.LONG_MAX, 3)] * len(tenants), pack, 0, so, sh, 21, *o)
+    assert D.plan_dict(eng, cut(o, info)) == plain and tot == total
+    assert cinfo.n_kept == total and ginfo.n_kept == total and cinfo.n_events == 0 and len(ev) == 0
+    assert fl.tolist() == [G.INLINE if row[i + 1] - row[i] == 1 else 0 for i in range(n)]
     eng.close()

@@ -19,6 +19,9 @@
 //     Fanout::group and Share::resolve over the same CSR: the same rows per DelivererKey in (topic, route, sender) order, special groups last.
 //   * after every step reads in key order (DistIndex::window, ::gc_sweep: bmq_routes_window / bmq_routes_gc_sweep) against the model's map order:
 //     windows from every kind of cursor, sweeps of random step and quota against the reference's loop walked over the map.
+//   * after every step the two filters of that CSR (Caps::run, Gate::run: bmq_caps.h, bmq_gate.h) under random tables against the model: classes from the decoded
+//     keys, the first k of a class by key survive in the input's order (k: the cap; gate_row_rule's kept count); once per run a row with a class of more than
+//     CAPS_RANK_MAX members, which both rank on the host.
 // Build + run: make -C bifromq_amd/csrc fuzz   (tests/test_host.py runs short rounds)
 #include <cstdio>
 #include <algorithm>
@@ -31,11 +34,13 @@
 #include <tuple>
 #include <vector>
 
+#include "../bifromq_amd/csrc/bmq_caps.h"
 #include "../bifromq_amd/csrc/bmq_codec.h"
 #include "../bifromq_amd/csrc/bmq_delivery.h"
 #include "../bifromq_amd/csrc/bmq_dist_index.h"
 #include "../bifromq_amd/csrc/bmq_exec_host.h"
 #include "../bifromq_amd/csrc/bmq_fanout.h"
+#include "../bifromq_amd/csrc/bmq_gate.h"
 #include "../bifromq_amd/csrc/bmq_share.h"
 
 using namespace bmq;
@@ -396,6 +401,120 @@ int main(int argc, char** argv) {
     Share<HostExec> sh_plan(hx); // the tables of the delivery-plan check: given afresh for every CSR (sh above belongs to the carry checks)
     Delivery<HostExec> dl(hx);
     uint64_t dl_rows = 0, dl_merged = 0;
+    // ---- the two filters of a match CSR (Caps::run, bmq_caps.h; Gate::run, bmq_gate.h) against the model: the classes come from the decoded keys, of
+    // every class of a row the first k members by key survive, in the input's order -- k the cap for the caps, the kept count of gate_row_rule for
+    // the gate.  `big`: the one row of the run with a class of more than CAPS_RANK_MAX members (the rank on the host), under limits that bind.
+    Caps<HostExec> cp(hx);
+    Gate<HostExec> gt(hx);
+    uint64_t flt_in = 0, flt_caps_kept = 0, flt_gate_kept = 0, flt_events = 0, flt_host_rows = 0;
+    auto check_filters = [&](int round, DistIndex<HostExec>& ix, const std::map<uint32_t, const std::string*>& by_id, const std::vector<uint32_t>& row, std::vector<uint32_t> ids,
+                             bool big) -> bool {
+        const uint32_t n_rows = (uint32_t)row.size() - 1, total = row[n_rows];
+        ids.resize(total + 4);
+        std::vector<uint8_t> cls(total);
+        for (uint32_t i = 0; i < total; i++) {
+            auto it = by_id.find(ids[i]);
+            cls[i] = CAPS_DEAD;
+            if (it == by_id.end()) continue;
+            RouteKeyParts kp;
+            decode_route_key(*it->second, kp);
+            size_t p = 0;
+            unsigned long long broker = 0;
+            while (p < kp.receiver.size() && kp.receiver[p] >= '0' && kp.receiver[p] <= '9') broker = broker * 10 + (unsigned long long)(kp.receiver[p++] - '0');
+            cls[i] = kp.flag != 1 ? CAPS_GROUP : (broker == 1 && p > 0 ? CAPS_PERSISTENT : CAPS_TRANSIENT);
+        }
+        // of the members of class cl in row r the first k by key stay; `over`: the ids of the others, in key order
+        auto keep_first = [&](uint32_t r, uint32_t cl, uint64_t k, std::vector<uint8_t>& keep, std::vector<uint32_t>* over) {
+            std::vector<std::pair<std::string_view, uint32_t>> m;
+            for (uint32_t i = row[r]; i < row[r + 1]; i++)
+                if (cls[i] == cl) m.push_back({std::string_view(*by_id.at(ids[i])), i});
+            std::sort(m.begin(), m.end());
+            for (size_t j = 0; j < m.size(); j++) {
+                keep[m[j].second] = j < k;
+                if (j >= k && over) over->push_back(ids[m[j].second]);
+            }
+        };
+        auto survivors = [&](const std::vector<uint8_t>& keep, std::vector<uint32_t>& o_row, std::vector<uint32_t>& o_ids) {
+            o_row.assign(1, 0u), o_ids.clear();
+            for (uint32_t r = 0; r < n_rows; r++) {
+                for (uint32_t i = row[r]; i < row[r + 1]; i++)
+                    if (keep[i]) o_ids.push_back(ids[i]);
+                o_row.push_back((uint32_t)o_ids.size());
+            }
+        };
+        const int32_t limits[] = {0, 1, 2, 5, 0x7FFFFFFF};
+        const long long byte_limits[] = {0, 50, 0x7FFFFFFFFFFFFFFFll};
+        const uint32_t n_tab = big ? 1 : 1 + (uint32_t)rnd(3), thr = (uint32_t)rnd(6);
+        std::vector<int32_t> pf(n_tab), gf(n_tab);
+        std::vector<int64_t> pb(n_tab);
+        std::vector<uint8_t> bw(n_tab + 16);
+        for (uint32_t t = 0; t < n_tab; t++)
+            pf[t] = big ? 7 : limits[rnd(5)], gf[t] = big ? 3 : limits[rnd(5)], pb[t] = big ? byte_limits[2] : byte_limits[rnd(3)], bw[t] = big ? 3 : (uint8_t)rnd(4);
+        std::vector<uint32_t> row_tab(n_rows + 4), pack(n_rows + 4);
+        for (uint32_t r = 0; r < n_rows; r++) row_tab[r] = (uint32_t)rnd(n_tab), pack[r] = (uint32_t)rnd(40);
+        std::vector<uint32_t> want_row, want_ids, got_row(n_rows + 4), got_ids(total + 4);
+        std::vector<uint8_t> keep(total);
+        // -- the caps: a row no longer than both caps is copied through as it is; elsewhere dead ids leave, and a class over its cap keeps `cap` members
+        std::vector<int32_t> want_ev, got_ev(4 * (size_t)total + 4);
+        for (uint32_t r = 0; r < n_rows; r++) {
+            const uint32_t t = row_tab[r], n = row[r + 1] - row[r];
+            const bool through = n <= (uint32_t)std::min(pf[t], gf[t]);
+            for (uint32_t i = row[r]; i < row[r + 1]; i++) keep[i] = through || cls[i] != CAPS_DEAD;
+            for (uint32_t k = 0; k < 2 && !through; k++) {
+                const uint32_t cap = (uint32_t)(k == 0 ? pf[t] : gf[t]);
+                if ((uint32_t)std::count(cls.begin() + row[r], cls.begin() + row[r + 1], (uint8_t)(CAPS_PERSISTENT + k)) <= cap) continue;
+                std::vector<uint32_t> over;
+                keep_first(r, CAPS_PERSISTENT + k, cap, keep, &over);
+                for (uint32_t id : over) want_ev.insert(want_ev.end(), {(int32_t)k, (int32_t)r, (int32_t)id, (int32_t)cap});
+            }
+        }
+        survivors(keep, want_row, want_ids);
+        CapsResult cr;
+        if (!cp.run(ix, row.data(), ids.data(), n_rows, total, row_tab.data(), pf.data(), gf.data(), n_tab, pf.data(), gf.data(), got_row.data(), got_ids.data(), total, nullptr,
+                    got_ev.data(), total, cr)) {
+            fprintf(stderr, "round %d: caps failed: %s\n", round, cp.error.c_str());
+            return false;
+        }
+        got_ev.resize(4 * (size_t)std::min<uint32_t>(cr.n_events, total));
+        if (cr.overflow || cr.n_in != total || cr.n_kept != want_ids.size() || !std::equal(want_row.begin(), want_row.end(), got_row.begin()) ||
+            !std::equal(want_ids.begin(), want_ids.end(), got_ids.begin()) || got_ev != want_ev || (big && cr.n_rows_fallback == 0)) {
+            fprintf(stderr, "round %d: the capped CSR differs from the model (%llu vs %zu ids, %u vs %zu events, %u rows ranked on the host)\n", round, (unsigned long long)cr.n_kept,
+                    want_ids.size(), cr.n_events, want_ev.size() / 4, cr.n_rows_fallback);
+            return false;
+        }
+        flt_in += total, flt_caps_kept += cr.n_kept, flt_events += cr.n_events, flt_host_rows += cr.n_rows_fallback;
+        // -- the gate: dead ids leave every row; what stays of a class is the rule's count
+        std::vector<uint32_t> want_fl(n_rows), got_fl(n_rows + 4), want_mr(n_tab, 0u), got_mr(n_tab + 4);
+        std::vector<uint64_t> want_mb(n_tab, 0ull), got_mb(n_tab + 4);
+        for (uint32_t r = 0; r < n_rows; r++) {
+            const uint32_t t = row_tab[r];
+            uint32_t cnt[3] = {0, 0, 0};
+            for (uint32_t i = row[r]; i < row[r + 1]; i++)
+                if (cls[i] != CAPS_DEAD) cnt[gate_slot_of(cls[i])]++;
+            const GateRow o = gate_row_rule(cnt[0], cnt[1], cnt[2], pack[r], (uint32_t)pf[t], (uint32_t)gf[t], (unsigned long long)pb[t], bw[t], thr);
+            for (uint32_t i = row[r]; i < row[r + 1]; i++) keep[i] = cls[i] != CAPS_DEAD && o.keep[gate_slot_of(cls[i])] > 0;
+            for (const uint32_t cl : {(uint32_t)CAPS_PERSISTENT, (uint32_t)CAPS_GROUP}) keep_first(r, cl, o.keep[gate_slot_of(cl)], keep, nullptr);
+            want_fl[r] = o.flags, want_mb[t] += o.meter, want_mr[t] += o.record;
+        }
+        survivors(keep, want_row, want_ids);
+        GateTable T;
+        T.max_pf = pf.data(), T.max_gf = gf.data(), T.max_pb = pb.data(), T.bw = bw.data(), T.n_gate = n_tab;
+        GateResult gr;
+        if (!gt.run(ix, row.data(), ids.data(), n_rows, total, pack.data(), row_tab.data(), T, thr, got_row.data(), got_ids.data(), total, got_fl.data(), nullptr, got_mb.data(),
+                    got_mr.data(), gr)) {
+            fprintf(stderr, "round %d: gate failed: %s\n", round, gt.error.c_str());
+            return false;
+        }
+        if (gr.overflow || gr.n_in != total || gr.n_kept != want_ids.size() || !std::equal(want_row.begin(), want_row.end(), got_row.begin()) ||
+            !std::equal(want_ids.begin(), want_ids.end(), got_ids.begin()) || !std::equal(want_fl.begin(), want_fl.end(), got_fl.begin()) ||
+            !std::equal(want_mb.begin(), want_mb.end(), got_mb.begin()) || !std::equal(want_mr.begin(), want_mr.end(), got_mr.begin()) || (big && gr.n_rows_fallback == 0)) {
+            fprintf(stderr, "round %d: the gated CSR differs from the model (%llu vs %zu ids, %u rows ranked on the host)\n", round, (unsigned long long)gr.n_kept, want_ids.size(),
+                    gr.n_rows_fallback);
+            return false;
+        }
+        flt_gate_kept += gr.n_kept, flt_host_rows += gr.n_rows_fallback;
+        return true;
+    };
     std::map<uint32_t, std::pair<std::string, std::vector<std::string>>> sh_model; // route id -> (its key when the table was given, URLs)
     auto give_tables = [&](int round) -> bool { // fresh tables for up to 40 group routes of the model
         sh.drop();
@@ -1073,6 +1192,7 @@ int main(int argc, char** argv) {
             }
             dl_rows += dr.n_rows;
             dl_merged += dr.n_merged_groups;
+            if (!check_filters(round, h, by_id, row, ids, false)) return 1;
         }
         for (int tq = 0; tq < 150; tq++) {
             const std::string& tn = tq % 25 == 24 ? std::string("nobody") : tenants[rnd(tenants.size())];
@@ -1095,6 +1215,38 @@ int main(int argc, char** argv) {
             }
         }
     }
+    { // once per run: a row whose persistent class has more than CAPS_RANK_MAX members, in an index of its own, beside a short row and an empty one
+        std::set<std::string> ks;
+        for (uint32_t i = 0; i < CAPS_RANK_MAX + 40; i++)
+            ks.insert(encode_route_key("t", "big/" + std::to_string(rnd(1000000)) + "/" + std::to_string(i), 1, "1" + std::string("\0", 1) + "inbox" + std::string("\0d", 2) + "0"));
+        for (uint32_t i = 0; i < 12; i++) ks.insert(encode_route_key("t", "big/g/" + std::to_string(i), (uint8_t)(2 + i % 2), "g" + std::to_string(i)));
+        for (uint32_t i = 0; i < 12; i++) ks.insert(encode_route_key("t", "big/t/" + std::to_string(i), 1, "0" + std::string("\0", 1) + "inbox" + std::string("\0d", 2) + "0"));
+        std::vector<std::string> keys(ks.begin(), ks.end());
+        std::vector<uint8_t> bytes;
+        std::vector<uint32_t> off{0};
+        for (auto& k : keys) {
+            bytes.insert(bytes.end(), k.begin(), k.end());
+            off.push_back((uint32_t)bytes.size());
+        }
+        bytes.resize(bytes.size() + 16, 0);
+        DistIndex<HostExec> big(hx);
+        if (!big.rebuild(bytes.data(), off.data(), (uint32_t)keys.size())) {
+            fprintf(stderr, "the index of the long row: rebuild failed: %s\n", big.error.c_str());
+            return 1;
+        }
+        std::map<uint32_t, const std::string*> by_id; // (ids are the ranks)
+        std::vector<uint32_t> row{0}, ids;
+        for (uint32_t i = 0; i < keys.size(); i++) by_id[i] = &keys[i], ids.push_back(i);
+        std::shuffle(ids.begin(), ids.end(), rng); // the input's order is not the keys'
+        ids.push_back((uint32_t)keys.size() + 5); // (an id never handed out)
+        row.push_back((uint32_t)ids.size());
+        row.push_back((uint32_t)ids.size());
+        for (uint32_t i = 0; i < 9; i++) ids.push_back(i * 7);
+        row.push_back((uint32_t)ids.size());
+        if (!check_filters(rounds, big, by_id, row, ids, true)) return 1;
+    }
+    printf("caps and gate: %llu ids in, %llu / %llu kept, %llu events, %llu rows ranked on the host\n", (unsigned long long)flt_in, (unsigned long long)flt_caps_kept,
+           (unsigned long long)flt_gate_kept, (unsigned long long)flt_events, (unsigned long long)flt_host_rows);
     DistIndexStats st;
     h.stats(st);
     printf("layout v3: %llu of the %llu nodes the checks discovered through a '+' edge below a non-root node lay beside their parent\n", (unsigned long long)plus_stat[0], (unsigned long long)plus_stat[1]);
