@@ -22,7 +22,7 @@ ABI_SYMBOLS = [
     "bmq_route_key_decode", "bmq_java_string_hash", "bmq_range_lookup", "bmq_comm_unique_id", "bmq_comm_init", "bmq_comm_destroy", "bmq_exchange_fanout",
     "bmq_exchange_csr", "bmq_exchange_wait", "bmq_partition_batch_dev", "bmq_retain_message_key", "bmq_retain_filter_route", "bmq_retain_rebuild", "bmq_retain_rebuild_ex", "bmq_retain_apply", "bmq_retain_apply_ex", "bmq_retain_topic",
     "bmq_retain_topic_info", "bmq_retain_find_all", "bmq_retain_expired", "bmq_retain_apply_batch", "bmq_retain_compact", "bmq_retain_compact_begin", "bmq_retain_compact_build", "bmq_retain_compact_swap", "bmq_retain_compact_abort", "bmq_retain_compact_info_get", "bmq_retain_info_get", "bmq_retain_build_info_get",
-    "bmq_retain_live_ids", "bmq_retain_topics", "bmq_retain_tenant_counts", "bmq_retain_message_keys", "bmq_retain_remove_ids", "bmq_retain_keys_prepare", "bmq_retain_keys_by_id", "bmq_retain_keys_match",
+    "bmq_retain_live_ids", "bmq_retain_topics", "bmq_retain_tenant_counts", "bmq_retain_message_keys", "bmq_retain_remove_ids", "bmq_retain_keys_prepare", "bmq_retain_keys_by_id", "bmq_retain_keys_match", "bmq_retain_plan", "bmq_retain_plan_commit",
     "bmq_retain_count_in", "bmq_retain_ids_in", "bmq_retain_compact_begin_in", "bmq_retain_import",
     "bmq_retain_match_batch", "bmq_retain_match_batch_dev", "bmq_retain_match_limited", "bmq_batcher_create", "bmq_batcher_destroy",
     "bmq_batcher_match_all", "bmq_batcher_submit", "bmq_batcher_stats_get", "bmq_poller_stats_get", "bmq_poller_control",
@@ -94,6 +94,11 @@ class RetainInfo(C.Structure):
     _fields_ = [("n_topics", C.c_uint64), ("n_tenants", C.c_uint64), ("id_bound", C.c_uint64), ("loaded_topics", C.c_uint64),
                 ("loaded_removed", C.c_uint64), ("added_ids", C.c_uint64), ("overlay_nodes", C.c_uint64), ("epoch", C.c_uint64),
                 ("generation", C.c_uint64)]
+
+
+class RetainPlanInfo(C.Structure):
+    _fields_ = [("generation", C.c_uint64), ("epoch", C.c_uint64), ("n_groups", C.c_uint64), ("n_add", C.c_uint64), ("n_update", C.c_uint64),
+                ("n_remove", C.c_uint64), ("n_none", C.c_uint64), ("key_bytes", C.c_uint64), ("ms", C.c_double)]
 
 
 class RetainBuildInfo(C.Structure):
@@ -205,6 +210,8 @@ def lib() -> C.CDLL:
             "bmq_retain_keys_prepare": (C.c_int, [vp, P(u64)]),
             "bmq_retain_keys_by_id": (C.c_int, [vp, vp, u32, vp, u64, vp]),
             "bmq_retain_keys_match": (C.c_int, [vp, vp, vp, u32, vp, vp, vp, u32, vp, u64, vp, vp, u64, P(u64), vp, vp, vp, u64, P(u64)]),
+            "bmq_retain_plan": (C.c_int, [vp, vp, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, u64, P(RetainPlanInfo)]),
+            "bmq_retain_plan_commit": (C.c_int, [vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, u64, u64, vp]),
             "bmq_routes_import": (C.c_int, [vp, vp, C.c_uint8, C.c_char_p, u32, C.c_char_p, u32, P(u64), P(u64)]),
             "bmq_compact_poll": (C.c_int, [vp, u32, P(u32)]),
             "bmq_compact_swap": (C.c_int, [vp, P(u64), P(u64)]),

@@ -2343,3 +2343,4 @@ int32_t bmq_java_string_hash(const uint8_t* utf8, uint32_t len) { return java_st
 #include "bmq_caps_engine.inc"
 #include "bmq_gate_engine.inc"
 #include "bmq_delivery_engine.inc"
+#include "bmq_rplan_engine.inc"

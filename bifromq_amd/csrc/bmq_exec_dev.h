@@ -24,6 +24,7 @@
 #include "bmq_retain_build_kernels.h"
 #include "bmq_retain_core.h"
 #include "bmq_retain_snap_kernels.h"
+#include "bmq_rplan_kernels.h"
 #include "bmq_share_kernels.h"
 
 namespace bmq {
@@ -936,6 +937,21 @@ struct DevExec {
     }
     bool r_key_write(const RetainMut& m, const RetainKeyStore& ks, const uint32_t* ids, uint32_t n, const unsigned long long* offs, uint8_t* out) {
         hipLaunchKernelGGL(k_r_key_write, grid(n, 256), dim3(256), 0, stream, m, ks, ids, n, offs, out);
+        return launched();
+    }
+    // ---- the plan of a batch of retain ops (bmq_rplan_kernels.h): find, group, classify, the 64-bit scan of the key lengths; then the keys ----
+    bool rp_plan(const RetainMut& m, const RplanBatch& b, bool have_index, unsigned long long* offs) {
+        hipLaunchKernelGGL(k_rp_find, grid(b.n, 64), dim3(64), 0, stream, m, b, have_index ? 1u : 0u);
+        hipLaunchKernelGGL(k_rp_group, grid(b.n, RPK), dim3(RPK), 0, stream, b, b.table_mask);
+        hipLaunchKernelGGL(k_rp_classify, grid((unsigned long long)b.n + 1, RPK), dim3(RPK), 0, stream, b);
+        if (!launched()) return false;
+        size_t bytes = 0;
+        if (!BMQ_X(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, b.key_len, offs, (int)b.n + 1, stream))) return false;
+        if (!ensure_tmp(bytes)) return false;
+        return BMQ_X(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, b.key_len, offs, (int)b.n + 1, stream));
+    }
+    bool rp_key_write(const RplanBatch& b, const unsigned long long* offs, uint8_t* out) {
+        hipLaunchKernelGGL(k_rp_key_write, grid(b.n, RPK), dim3(RPK), 0, stream, b, offs, out);
         return launched();
     }
     // ---- snapshot of the retained-topic index and the next generation's per-id arrays (bmq_retain_snap_kernels.h) ----

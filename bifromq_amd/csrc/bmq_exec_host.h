@@ -22,6 +22,7 @@
 #include "bmq_retain_build_core.h"
 #include "bmq_retain_core.h"
 #include "bmq_retain_snap_core.h"
+#include "bmq_rplan_core.h"
 #include "bmq_share_core.h"
 
 namespace bmq {
@@ -504,6 +505,32 @@ struct HostExec {
     }
     bool r_key_write(const RetainMut& m, const RetainKeyStore& ks, const uint32_t* ids, uint32_t n, const unsigned long long* offs, uint8_t* out) {
         par(n, [&](size_t i) { key_write_one(m, ks, ids[i], out + offs[i], offs[i + 1] - offs[i]); });
+        return true;
+    }
+    // ---- the plan of a batch of retain ops (bmq_rplan_core.h): the passes of DevExec::rp_plan, one after the other ----
+    bool rp_plan(const RetainMut& m, const RplanBatch& b, bool have_index, unsigned long long* offs) {
+        par(b.n, [&](size_t i) { rp_find_one(m, b, (uint32_t)i, have_index); });
+        par(b.n, [&](size_t i) { rp_group_one(b, (uint32_t)i, b.table_mask); });
+        std::atomic<uint32_t> acts[4];
+        for (auto& a : acts) a.store(0);
+        par(b.n, [&](size_t i) {
+            uint32_t dt = 0;
+            int32_t dv = 0;
+            const uint32_t a = rp_classify_one(b, (uint32_t)i, dt, dv);
+            if (a <= RP_REMOVE) acts[a].fetch_add(1, std::memory_order_relaxed);
+            if (dv) atom_add(&b.delta[dt], dv);
+        });
+        for (uint32_t a = 0; a < 4; a++) b.ctr[RP_C_ACTION + a] += acts[a].load();
+        b.key_len[b.n] = 0ull;
+        unsigned long long run = 0;
+        for (size_t i = 0; i <= b.n; i++) {
+            offs[i] = run;
+            run += b.key_len[i];
+        }
+        return true;
+    }
+    bool rp_key_write(const RplanBatch& b, const unsigned long long* offs, uint8_t* out) {
+        par(b.n, [&](size_t i) { rp_key_write_one(b, (uint32_t)i, offs, out); });
         return true;
     }
     // ---- bulk load of the retained-topic index (bmq_retain_build_core.h): one call per stage, in the order of RetainBuild::build ----

@@ -11,6 +11,7 @@
 
 #include "bmq_retain_core.h"
 #include "bmq_retain_snap_core.h"
+#include "bmq_rplan_core.h"
 
 namespace bmq {
 
@@ -112,6 +113,7 @@ public:
         return v;
     }
     const unsigned long long* expire_at() const { return d_expire_at; }
+    RetainMut mut_view() const { return mut(); } // (the emulator harness of the plan kernels runs them on this instance's arrays)
 
     // ---- one batch of ops (host buffers).  out_ids (may be null): the id of every op's topic, NONE for a no-op / superseded op ----
     bool apply(const uint8_t* tenants, const uint32_t* tenant_off, uint32_t n_tenants, const uint32_t* op_tenant, const uint8_t* topics,
@@ -378,6 +380,84 @@ public:
         if (!cout(out_off, offs, 8 * ((size_t)n + 1))) return xfail();
         nospace = total > cap || (total && !out);
         if (!nospace && total && !cout(out, bytes, total)) return xfail();
+        return true;
+    }
+
+    // ---- the plan of a batch of retain ops (bmq_rplan_core.h): the pre-commit half of RetainStoreCoProc.batchRetain for a whole batch, on
+    // the executor's stream behind whatever is in flight.  Reads the index only (an instance that holds none answers "not retained" for
+    // every topic).  The caller checked op_tenant[i] < n_tenants.  Two waits: one for everything but the key bytes -- the key offsets say how
+    // many there are --, one for the bytes if they fit.
+    struct PlanOut {               // host memory; every pointer may be null
+        uint8_t *code, *action;    // [n]
+        uint32_t *winner, *topic_id; // [n]
+        int32_t* delta;            // [n_tenants]
+        unsigned long long* key_off; // [n + 1]
+        uint8_t* keys;
+        uint64_t keys_cap;
+        uint64_t by_action[4] = {0, 0, 0, 0}; // winners with RP_NONE .. RP_REMOVE
+        uint64_t key_bytes = 0;
+        bool nospace = false;      // keys_cap < key_bytes: everything but the key bytes was written
+    };
+    bool plan(const uint8_t* tenants, const uint32_t* tenant_off, uint32_t n_tenants, const uint32_t* op_tenant, const uint8_t* topics, const uint32_t* topic_off,
+              const uint8_t* clear, uint32_t n, uint32_t min_table, PlanOut& o) {
+        error.clear();
+        const size_t tb = tenant_off[n_tenants], pb = topic_off[n];
+        const uint32_t slots = min_table ? pow2_at_least((uint64_t)n) : std::max<uint32_t>(8u, pow2_at_least(2ull * n));
+        // inputs | zeroed scratch and results (table, last, delta, ctr) | scratch (rep_of, key_len) | results, copied out in one piece
+        const size_t off_t = 0, off_to = align16(off_t + tb + 16), off_ot = align16(off_to + 4 * ((size_t)n_tenants + 1)), off_p = align16(off_ot + 4 * (size_t)n),
+                     off_po = align16(off_p + pb + 16), off_cl = align16(off_po + 4 * ((size_t)n + 1)), off_zero = align16(off_cl + n),
+                     off_tab = off_zero, off_last = align16(off_tab + 4 * (size_t)slots), off_rep = align16(off_last + 4 * (size_t)n),
+                     off_len = align16(off_rep + 4 * (size_t)n), off_res = align16(off_len + 8 * ((size_t)n + 1)),
+                     off_koff = off_res, off_win = align16(off_koff + 8 * ((size_t)n + 1)), off_found = align16(off_win + 4 * (size_t)n),
+                     off_delta = align16(off_found + 4 * (size_t)n), off_ctr = align16(off_delta + 4 * (size_t)n_tenants), off_code = align16(off_ctr + 4 * RP_C_N),
+                     off_act = align16(off_code + n), total = align16(off_act + n);
+        if (!ensure(p_buf, p_cap, total)) return false;
+        if (!cin(p_buf + off_t, tenants, tb) || !cin(p_buf + off_to, tenant_off, 4 * ((size_t)n_tenants + 1)) || (op_tenant && !cin(p_buf + off_ot, op_tenant, 4 * (size_t)n)) ||
+            !cin(p_buf + off_p, topics, pb) || !cin(p_buf + off_po, topic_off, 4 * ((size_t)n + 1)) || !cin(p_buf + off_cl, clear, n) ||
+            !x.zero(p_buf + off_zero, off_rep - off_zero) || !x.zero(p_buf + off_delta, off_code - off_delta))
+            return xfail();
+        RplanBatch b{};
+        b.tenants = p_buf + off_t;
+        b.tenant_off = (const uint32_t*)(p_buf + off_to);
+        b.n_tenants = n_tenants;
+        b.op_tenant = op_tenant ? (const uint32_t*)(p_buf + off_ot) : nullptr;
+        b.topics = p_buf + off_p;
+        b.topic_off = (const uint32_t*)(p_buf + off_po);
+        b.clear = p_buf + off_cl;
+        b.n = n;
+        b.table = (uint32_t*)(p_buf + off_tab);
+        b.table_mask = slots - 1;
+        b.rep_of = (uint32_t*)(p_buf + off_rep);
+        b.last = (uint32_t*)(p_buf + off_last);
+        b.found = (uint32_t*)(p_buf + off_found);
+        b.code = p_buf + off_code;
+        b.action = p_buf + off_act;
+        b.winner = (uint32_t*)(p_buf + off_win);
+        b.delta = (int32_t*)(p_buf + off_delta);
+        b.key_len = (unsigned long long*)(p_buf + off_len);
+        b.ctr = (uint32_t*)(p_buf + off_ctr);
+        unsigned long long* d_koff = (unsigned long long*)(p_buf + off_koff);
+        p_host.resize(total - off_res);
+        if (!x.rp_plan(mut(), b, ready, d_koff) || !cout(p_host.data(), p_buf + off_res, total - off_res)) return xfail(); // waits for the passes
+        const uint8_t* r = p_host.data() - off_res;
+        uint32_t ctr[RP_C_N];
+        memcpy(ctr, r + off_ctr, sizeof(ctr));
+        if (ctr[RP_C_ERR] & RPERR_TENANT) return fail("malformed retain op (tenant index)");
+        if (ctr[RP_C_ERR]) return fail("the group table of the retain plan ran full (" + std::to_string(ctr[RP_C_ERR]) + ")");
+        unsigned long long kb = 0;
+        memcpy(&kb, r + off_koff + 8 * (size_t)n, 8);
+        o.key_bytes = kb;
+        for (uint32_t a = 0; a < 4; a++) o.by_action[a] = ctr[RP_C_ACTION + a];
+        if (o.code) memcpy(o.code, r + off_code, n);
+        if (o.action) memcpy(o.action, r + off_act, n);
+        if (o.winner) memcpy(o.winner, r + off_win, 4 * (size_t)n);
+        if (o.topic_id) memcpy(o.topic_id, r + off_found, 4 * (size_t)n);
+        if (o.delta) memcpy(o.delta, r + off_delta, 4 * (size_t)n_tenants);
+        if (o.key_off) memcpy(o.key_off, r + off_koff, 8 * ((size_t)n + 1));
+        o.nospace = kb > o.keys_cap || (kb && !o.keys);
+        if (o.nospace || kb == 0) return true;
+        if (!ensure(k_out, k_out_cap, (size_t)kb + 16)) return false;
+        if (!x.rp_key_write(b, d_koff, k_out) || !cout(o.keys, k_out, kb)) return xfail();
         return true;
     }
 
@@ -668,7 +748,7 @@ public:
     void drop() {
         for (void* p : {(void*)d_expire_at, (void*)d_ts, (void*)d_expiry, (void*)d_id_node, (void*)d_id_tnode, (void*)d_dead, (void*)d_rank, (void*)d_last,
                         (void*)d_nodes, (void*)d_edges, (void*)d_pool, (void*)d_ctr, (void*)d_stage, (void*)q_buf, (void*)o_buf, (void*)k_ids, (void*)k_off,
-                        (void*)k_out})
+                        (void*)k_out, (void*)p_buf})
             if (p) x.release(p);
         drop_key_store(); // (its ids are the ranks of the generation that ends here)
         d_expire_at = d_ts = nullptr;
@@ -680,9 +760,9 @@ public:
         d_edges = nullptr;
         d_pool = nullptr;
         d_ctr = nullptr;
-        d_stage = q_buf = o_buf = k_ids = k_off = k_out = nullptr;
+        d_stage = q_buf = o_buf = k_ids = k_off = k_out = p_buf = nullptr;
         id_cap = ov_cap = pool_cap = edge_slots = 0;
-        stage_cap = q_cap = o_cap = k_ids_cap = k_off_cap = k_out_cap = 0;
+        stage_cap = q_cap = o_cap = k_ids_cap = k_off_cap = k_out_cap = p_cap = 0;
         ready = false;
     }
 
@@ -712,6 +792,9 @@ private:
     bool ks_ready = false;
     uint8_t *k_ids = nullptr, *k_off = nullptr, *k_out = nullptr;
     size_t k_ids_cap = 0, k_off_cap = 0, k_out_cap = 0;
+    uint8_t* p_buf = nullptr; // staging, scratch and results of plan()
+    size_t p_cap = 0;
+    std::vector<uint8_t> p_host;
 
     void drop_key_store() {
         for (void* p : {(void*)ks_topics, (void*)ks_tenants, (void*)ks_topic_off, (void*)ks_tenant_lo, (void*)ks_tenant_off})

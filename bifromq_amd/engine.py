@@ -182,6 +182,22 @@ def java_string_hash(s) -> int:
     return _lib.lib().bmq_java_string_hash(b, len(b))
 
 
+PLAN_NONE, PLAN_ADD, PLAN_UPDATE, PLAN_REMOVE, PLAN_SUPERSEDED = range(5)  # BMQ_PLAN_* of include/bmq.h
+
+
+class RetainPlan:
+    """what bmq_retain_plan returns for a batch of n ops (Engine.retain_plan)"""
+
+    def __init__(self, code, action, winner, topic_id, delta, key_off, key_bytes: bytes, info):
+        self.code, self.action, self.winner, self.topic_id, self.delta = code, action, winner, topic_id, delta
+        self.key_off, self.key_bytes, self.info = key_off, key_bytes, info
+
+    @property
+    def keys(self) -> List[bytes]:
+        off = self.key_off.tolist()
+        return [self.key_bytes[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+
 class Engine:
     """One engine per KV range replica (cf. DistWorkerCoProc's SubscriptionCache)."""
 
@@ -1161,6 +1177,63 @@ class Engine:
             self._check(rc)
             raw = out.tobytes()
             return [raw[int(off[i]):int(off[i + 1])] for i in range(n)]
+
+    def retain_plan(self, tenants: Sequence, op_tenant, ops: Sequence = (), packed_topics=None, clear=None, keys_cap: int = 0) -> "RetainPlan":
+        """bmq_retain_plan: the pre-commit half of RetainStoreCoProc.batchRetain for a batch, read-only.  ops: (topic, clear) pairs -- or
+        packed_topics + clear for large batches.  -> RetainPlan: code / action / winner / topic_id per op, delta per tenant-table entry, the
+        winners' retainMessageKeys (key_off[n + 1] into key_bytes; .keys lists them, b"" for an op without one) and the info."""
+        tdata, toff = pack(tenants)
+        if packed_topics is None:
+            data, off = pack([o[0] for o in ops])
+            clear = [1 if o[1] else 0 for o in ops]
+        else:
+            data, off = packed_topics
+        cl = np.ascontiguousarray(clear, dtype=np.uint8)
+        n = len(off) - 1
+        assert len(cl) == n
+        ot = None if op_tenant is None else np.ascontiguousarray(op_tenant, dtype=np.uint32)
+        assert ot is None or len(ot) == n
+        code, action = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint8)
+        winner, ids = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        delta = np.zeros(max(len(tenants), 1), dtype=np.int32)
+        koff = np.zeros(n + 1, dtype=np.uint64)
+        info = _lib.RetainPlanInfo()
+        kcap = keys_cap or max(4096, 64 * n)
+        while True:
+            keys = np.zeros(kcap, dtype=np.uint8)
+            rc = _lib.lib().bmq_retain_plan(self.h, _ptr(tdata), _ptr(toff), len(tenants), _ptr(ot), _ptr(data), _ptr(off), _ptr(cl), n, _ptr(code), _ptr(action),
+                                            _ptr(winner), _ptr(ids), _ptr(delta), _ptr(koff), _ptr(keys), kcap, C.byref(info))
+            if rc == -3 and int(koff[n]) > kcap:
+                kcap = int(koff[n]) + 16
+                continue
+            self._check(rc)
+            return RetainPlan(code[:n], action[:n], winner[:n], ids[:n], delta[:len(tenants)], koff, keys[:int(koff[n])].tobytes(), info)
+
+    def retain_plan_commit(self, tenants: Sequence, op_tenant, ops: Sequence, plan: "RetainPlan", packed_topics=None, timestamps=None, expiry=None):
+        """bmq_retain_plan_commit: the post-commit closure of batchRetain for the ops the plan was made of -> the topic id of every winner
+        that changed the index (0xFFFFFFFF otherwise).  BmqError STATE if the index has changed since the plan."""
+        tdata, toff = pack(tenants)
+        data, off = pack([o[0] for o in ops]) if packed_topics is None else packed_topics
+        n = len(off) - 1
+        assert len(plan.action) == n
+        ot = None if op_tenant is None else np.ascontiguousarray(op_tenant, dtype=np.uint32)
+        act = np.ascontiguousarray(plan.action, dtype=np.uint8)
+        ts = None if timestamps is None else np.ascontiguousarray(timestamps, dtype=np.uint64)
+        ex = None if expiry is None else np.ascontiguousarray(expiry, dtype=np.uint32)
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        self._check(_lib.lib().bmq_retain_plan_commit(self.h, _ptr(tdata), _ptr(toff), len(tenants), _ptr(ot), _ptr(data), _ptr(off), n, _ptr(act), _ptr(ts), _ptr(ex),
+                                                      plan.info.generation, plan.info.epoch, _ptr(out)))
+        return out[:n]
+
+    def batch_retain(self, tenants: Sequence, op_tenant, ops: Sequence, kv_commit, timestamps=None, expiry=None):
+        """RetainStoreCoProc.batchRetain around a KV commit: plan, kv_commit(puts, deletes) -- puts: [(key, op index)], deletes: [key] --,
+        then the index mutation.  -> (plan, topic ids of retain_plan_commit)"""
+        plan = self.retain_plan(tenants, op_tenant, ops)
+        keys = plan.keys
+        puts = [(keys[i], i) for i in range(len(keys)) if plan.action[i] in (PLAN_ADD, PLAN_UPDATE)]
+        deletes = [keys[i] for i in range(len(keys)) if plan.action[i] == PLAN_REMOVE]
+        kv_commit(puts, deletes)
+        return plan, self.retain_plan_commit(tenants, op_tenant, ops, plan, timestamps=timestamps, expiry=expiry)
 
     def retain_match_keys(self, tenants: Sequence, filter_tenant, filters: Sequence, limits, now_ms: int = 0, packed_filters=None, keys_cap: int = 0):
         """bmq_retain_keys_match: retain_match_limited plus retainMessageKey of every kept id, composed on the device ->

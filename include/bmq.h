@@ -1339,6 +1339,46 @@ int bmq_retain_match_batch_dev(bmq_engine* e, const uint8_t* d_tenants, const ui
                                const uint32_t* d_filter_off, uint32_t n_filters, uint32_t* d_out_row_ptr,
                                uint32_t* d_out_topic_ids, uint64_t out_capacity, uint64_t* d_out_total);
 
+/* The two native halves of RetainStoreCoProc.batchRetain around the KV commit (RS/RetainStoreCoProc.java:193-255), for a whole batch of
+ * (tenant, topic, message) ops.  Topics are bytes, taken literally ('+' and '#' are levels like any other, as for bmq_retain_apply*);
+ * clear[i] != 0 says that the message's payload is empty.  There is no `now`: an expired topic that has not been collected is still
+ * retained, as index.match returns it (:213).
+ *   bmq_retain_plan         the pre-commit half, read-only, on the engine stream behind whatever is in flight (locks and state of
+ *                           bmq_retain_keys_by_id: the serving generation answers while a retain compaction runs, the epoch stays).  Ops
+ *                           with equal tenant BYTES and equal topic BYTES form a group whose LAST op is the winner, as
+ *                           BatchRetainCallHelper.makeBatch keeps the last request per topic (two tenant-table entries with the same bytes
+ *                           are one tenant).  Per op i, with w = the winner of its group and `present` = the topic has a live id now:
+ *                             out_code[i]     clear[w] ? 1 (CLEARED) : 0 (RETAINED)   -- RetainResult.Code, RetainStoreCoProc.proto:50-53
+ *                             out_winner[i]   w
+ *                             out_action[i]   i != w: BMQ_PLAN_SUPERSEDED; else clear[w] ? (present ? REMOVE : NONE) : (present ? UPDATE : ADD)
+ *                             out_topic_id[i] the live id if present (every op of the group), else 0xFFFFFFFF
+ *                             key i           retainMessageKey(tenant, topic) if i == w and the action is not NONE (the KV put of an ADD /
+ *                                             UPDATE, the KV delete of a REMOVE), else empty: out_key_off[n + 1] / out_keys
+ *                             out_delta[t]    += 1 per ADD, -= 1 per REMOVE, filed under the winner's op_tenant (the topic-count change)
+ *                           BMQ_E_INVAL (a tenant index out of range among them): no output is written.  BMQ_E_NOSPACE: keys_cap <
+ *                           out_key_off[n]; everything except the key bytes is written.  n == 0: BMQ_OK, nothing is launched.  Host-only
+ *                           engines run the same functions on host threads.
+ *   bmq_retain_plan_commit  the post-commit closure (:240-255), with the op arrays of the plan and its out_action: BMQ_E_STATE and no
+ *                           change if (generation, epoch) are not bmq_retain_info's any more; otherwise the winners with ADD / UPDATE go
+ *                           through bmq_retain_apply_batch as adds (with their stamps), those with REMOVE as removes.  out_topic_ids[i]
+ *                           (may be NULL) = the topic's id for the winners that changed the index, else 0xFFFFFFFF. */
+enum { BMQ_PLAN_NONE = 0, BMQ_PLAN_ADD = 1, BMQ_PLAN_UPDATE = 2, BMQ_PLAN_REMOVE = 3, BMQ_PLAN_SUPERSEDED = 4 };
+typedef struct bmq_retain_plan_info {
+    uint64_t generation, epoch; /* of the index the plan was made on: what bmq_retain_plan_commit takes */
+    uint64_t n_groups;          /* distinct (tenant, topic) pairs = winners */
+    uint64_t n_add, n_update, n_remove, n_none;
+    uint64_t key_bytes;
+    double ms;                  /* host clock around the call */
+} bmq_retain_plan_info;
+int bmq_retain_plan(const bmq_engine* e, const uint8_t* tenants, const uint32_t* tenant_off, uint32_t n_tenants,
+                    const uint32_t* op_tenant /* NULL: tenant 0 */, const uint8_t* topics, const uint32_t* topic_off, const uint8_t* clear,
+                    uint32_t n, uint8_t* out_code, uint8_t* out_action, uint32_t* out_winner, uint32_t* out_topic_id /* each [n], may be NULL */,
+                    int32_t* out_delta /* [n_tenants], may be NULL */, uint64_t* out_key_off /* [n + 1] */, uint8_t* out_keys, uint64_t keys_cap,
+                    bmq_retain_plan_info* out_info /* may be NULL */);
+int bmq_retain_plan_commit(bmq_engine* e, const uint8_t* tenants, const uint32_t* tenant_off, uint32_t n_tenants, const uint32_t* op_tenant,
+                           const uint8_t* topics, const uint32_t* topic_off, uint32_t n, const uint8_t* action, const uint64_t* timestamp_hlc,
+                           const uint32_t* expiry_seconds, uint64_t generation, uint64_t epoch, uint32_t* out_topic_ids /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -606,6 +606,39 @@ JNIEXPORT jlong JNICALL NK(retainKeysPrepare)(JNIEnv* env, jclass c, jlong h) {
     }
     return (jlong)bytes;
 }
+/* ---- the two native halves of RetainStoreCoProc.batchRetain around the KV commit: NativeRetainPlan.java ---- */
+#define NP(name) Java_org_apache_bifromq_retain_store_gpu_NativeRetainPlan_##name
+/* long retainPlan(long engine, ByteBuffer tenants, IntBuffer tenantOff, int nTenants, IntBuffer opTenant (null: tenant 0), ByteBuffer topics,
+ *                 IntBuffer topicOff, ByteBuffer clear, int n, ByteBuffer outCode, ByteBuffer outAction, IntBuffer outWinner, IntBuffer outTopicId,
+ *                 IntBuffer outDelta, LongBuffer outKeyOff, ByteBuffer outKeys, long[] info8)
+ * info8 = {generation, epoch, groups, add, update, remove, none, key bytes} -> key bytes, or -(needed) when outKeys is too small (everything else is written) */
+JNIEXPORT jlong JNICALL NP(retainPlan)(JNIEnv* env, jclass c, jlong h, jobject tenants, jobject tenantOff, jint nTenants, jobject opTenant, jobject topics, jobject topicOff,
+                                       jobject clear, jint n, jobject outCode, jobject outAction, jobject outWinner, jobject outTopicId, jobject outDelta, jobject outKeyOff,
+                                       jobject outKeys, jlongArray info8) {
+    (void)c;
+    bmq_retain_plan_info pi = {0};
+    const int rc = bmq_retain_plan(ENGINE(h), (const uint8_t*)ADDR(tenants), (const uint32_t*)ADDR(tenantOff), (uint32_t)nTenants, (const uint32_t*)ADDR(opTenant),
+                                   (const uint8_t*)ADDR(topics), (const uint32_t*)ADDR(topicOff), (const uint8_t*)ADDR(clear), (uint32_t)n, (uint8_t*)ADDR(outCode),
+                                   (uint8_t*)ADDR(outAction), (uint32_t*)ADDR(outWinner), (uint32_t*)ADDR(outTopicId), (int32_t*)ADDR(outDelta), (uint64_t*)ADDR(outKeyOff),
+                                   (uint8_t*)ADDR(outKeys), CAP(outKeys), &pi);
+    if (info8 && (rc == BMQ_OK || rc == BMQ_E_NOSPACE)) {
+        const jlong v[8] = {(jlong)pi.generation, (jlong)pi.epoch, (jlong)pi.n_groups, (jlong)pi.n_add, (jlong)pi.n_update, (jlong)pi.n_remove, (jlong)pi.n_none, (jlong)pi.key_bytes};
+        (*env)->SetLongArrayRegion(env, info8, 0, 8, v);
+    }
+    return result_of(env, ENGINE(h), "bmq_retain_plan", rc, pi.key_bytes);
+}
+/* void retainPlanCommit(long engine, <the op arrays of retainPlan>, ByteBuffer action, LongBuffer timestampHlc, IntBuffer expirySeconds (both null: no stamps),
+ *                       long generation, long epoch, IntBuffer outTopicIds (may be null))
+ * the post-commit closure; throws IllegalStateException when the index has changed since the plan (nothing is applied then) */
+JNIEXPORT void JNICALL NP(retainPlanCommit)(JNIEnv* env, jclass c, jlong h, jobject tenants, jobject tenantOff, jint nTenants, jobject opTenant, jobject topics, jobject topicOff,
+                                            jint n, jobject action, jobject timestampHlc, jobject expirySeconds, jlong generation, jlong epoch, jobject outTopicIds) {
+    (void)c;
+    const int rc = bmq_retain_plan_commit(ENGINE(h), (const uint8_t*)ADDR(tenants), (const uint32_t*)ADDR(tenantOff), (uint32_t)nTenants, (const uint32_t*)ADDR(opTenant),
+                                          (const uint8_t*)ADDR(topics), (const uint32_t*)ADDR(topicOff), (uint32_t)n, (const uint8_t*)ADDR(action),
+                                          (const uint64_t*)ADDR(timestampHlc), (const uint32_t*)ADDR(expirySeconds), (uint64_t)generation, (uint64_t)epoch,
+                                          (uint32_t*)ADDR(outTopicIds));
+    if (rc != BMQ_OK) throw_state(env, ENGINE(h), "bmq_retain_plan_commit", rc);
+}
 /* long retainRemoveIds(long engine, IntBuffer ids, int n, long generation)     the post-commit half of gc, by id -> topics removed; throws if the
  * generation has changed (the ids belong to the one before) or an id was never handed out */
 JNIEXPORT jlong JNICALL NS(retainRemoveIds)(JNIEnv* env, jclass c, jlong h, jobject ids, jint n, jlong generation) {
